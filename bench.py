@@ -10,7 +10,13 @@ HBM.  Multi-GPU: every rank scores its own batch (independent islands, no
 collective in the data path) -> weak scaling; the driver launches one
 process per GPU via torch.distributed.run.
 
-Reported beside the value:
+A plain run sets up, warms up, times --steps steps and prints the record
+(value, ms_per_step, the roofline's achieved side from the same steps' HIP
+events); --dump-outputs DIR also writes the last step's keys as DIR/*.npy
+(dump_outputs), the same from run to run for the same arguments.  Every
+other leg below takes runs of its own and needs --full.
+
+Reported beside the value (--full):
   roofline      the dominant kernel (eval_cvrp_words2, word-interleaved
                 tours: the layout the GA / ACO kernels emit) timed with HIP
                 events on the stream it runs on.  It is LDS-gather bound, so
@@ -60,6 +66,9 @@ GUIDE_LDS_GATHER_PEAK = 256 * 256 * 2.4e9 / 8
 # the driver keeps a bounded tail of stdout: the LAST line (the one it parses) stays
 # under this many bytes; every detailed leg is printed on an earlier stdout line
 FINAL_LINE_MAX = 8192
+# --dump-outputs: tours sampled from the scored batch, and the sample's seed
+DUMP_SAMPLE = 1 << 20
+DUMP_SEED = 0xD0
 HEADLINE_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
                  "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config")
 
@@ -71,6 +80,16 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--candidates", type=int, default=16 * 1024 * 1024)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every side leg: the rows-layout pass, the "
+                         "measured LDS-gather ceiling (roofline peak / frac), the equal-time "
+                         "quality cells, the island leg, cpu_baseline, the other configs, the "
+                         "search lines and cfg 1 (~6 min); without it the run is setup, warm-up, "
+                         "the timed steps and the record.  The options below only shape --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (the "
+                         "keys of the scored batch, as the float64 fields unvisited / primary / "
+                         "secondary of a fixed seeded sample of 2^20 tours) to DIR/*.npy")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
                     help="target CPU work for the cpu_baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -295,6 +314,28 @@ def make_batch(ctx, C, n, seed, dtype=None):
     Philox-seeded") as uint8 rows, generated on the device."""
     import torch
     return ctx.random_tours(C, n, seed, stream_id=0xBE7C, dtype=dtype or torch.uint8)
+
+
+def dump_outputs(keys, out_dir, sample=DUMP_SAMPLE):
+    """--dump-outputs: the timed path's result (the int64 keys of the batch its
+    last step scored) as float64 arrays, one per key field (oracle/spec.py
+    pack_key: unvisited << 56 | primary << 28 | secondary; every field is
+    below 2^28, so float64 holds it exactly).  A batch larger than `sample`
+    is cut to a fixed sample of tour indices (sorted, drawn without
+    replacement from numpy's default_rng(DUMP_SEED)), the same in every run
+    with the same --candidates: 3 x 8 B x 2^20 = 24 MiB."""
+    C = int(keys.shape[0])
+    if C > sample:
+        import torch
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(C, sample, replace=False))
+        keys = keys[torch.from_numpy(idx).to(keys.device)]
+    k = keys.cpu().numpy().view(np.uint64)
+    os.makedirs(out_dir, exist_ok=True)
+    mask = np.uint64(2**28 - 1)
+    for name, field in (("keys_unvisited", k >> np.uint64(56)),
+                        ("keys_primary", (k >> np.uint64(28)) & mask),
+                        ("keys_secondary", k & mask)):
+        np.save(os.path.join(out_dir, name + ".npy"), field.astype(np.float64))
 
 
 def cpu_model() -> str:
@@ -1236,7 +1277,6 @@ def main():
     perms = make_batch(ctx, C, n, args.seed * 1000 + rank)
     words = ctx.to_words(perms, n)           # word-interleaved layout, resident in HBM
     keys = torch.empty(C, dtype=torch.int64, device=dev)
-    keys_rows = torch.empty(C, dtype=torch.int64, device=dev)
     assert ctx.eval_path(perms) == 0, "expected the packed-LDS row kernel"
     stream = torch.cuda.current_stream(dev)
 
@@ -1272,14 +1312,22 @@ def main():
     wall, kernel_ms = timed(lambda: ctx.eval_words(words, n, out=keys), args.steps, args.warmup,
                             world > 1)
     value = C * args.steps * world / wall
-    rows_wall, rows_ms = timed(lambda: ctx.eval(perms, out=keys_rows), max(3, args.steps // 4),
-                               1, False)
-    r_gather = ctx.probe_lds_gather(slots=inst.N * inst.N) if rank == 0 else None
+    if args.dump_outputs and rank == 0:
+        progress(f"writing the last step's keys to {args.dump_outputs}")
+        dump_outputs(keys, args.dump_outputs)
+    # a plain run ends here with the record; every side leg below needs --full
+    full = args.full
+    keys_rows = rows_ms = r_gather = None
+    if full:
+        keys_rows = torch.empty(C, dtype=torch.int64, device=dev)
+        rows_wall, rows_ms = timed(lambda: ctx.eval(perms, out=keys_rows),
+                                   max(3, args.steps // 4), 1, False)
+        r_gather = ctx.probe_lds_gather(slots=inst.N * inst.N) if rank == 0 else None
     qual = None
     # The quality comparison is an N=1 side measurement: at N>1 the headline
     # stays a collective-free weak-scaling line (island exchange is covered by
     # the gloo tests, tests/test_islands_cpu.py).
-    if args.quality_seconds > 0 and world == 1:
+    if full and args.quality_seconds > 0 and world == 1:
         try:
             progress("cfg-2 equal-time SA / GA / ACO")
             qual = quality(ctx, inst, args.quality_seconds, world, rank, dist,
@@ -1295,7 +1343,7 @@ def main():
             qual = {"error": traceback.format_exc(limit=3)}
 
     xq = tdq = None
-    if args.x1000_quality_seconds > 0 and world == 1:
+    if full and args.x1000_quality_seconds > 0 and world == 1:
         try:
             progress("X-1000 equal-time cells")
             xq = equal_time_cells(ctx, args.x1000_quality_seconds, dist,
@@ -1318,7 +1366,7 @@ def main():
         except Exception:
             xlong = {"error": traceback.format_exc(limit=3)}
     hetq = None
-    if args.td_quality_seconds > 0 and world == 1:
+    if full and args.td_quality_seconds > 0 and world == 1:
         try:
             progress("TD-200 equal-time cells")
             tdq = equal_time_cells(ctx, args.td_quality_seconds, dist,
@@ -1337,7 +1385,7 @@ def main():
             hetq = {"error": traceback.format_exc(limit=3)}
 
     isl = None
-    if args.island_epochs > 0:
+    if full and args.island_epochs > 0:
         # after every other device use of the matrix instance: it loads its own
         progress("island leg")
         isl = island_leg(ctx, torch, dev, world, rank, dist, epochs=args.island_epochs,
@@ -1373,14 +1421,14 @@ def main():
                        "tour_layout": "words [n/4][C] u32 (the layout GA/ACO emit)",
                        "per_rank_batch": C, "parallelism": f"islands{world}"},
             "roofline": {"bound": "lds_gather", "achieved": evals_s * G, "peak": r_gather,
-                         "unit": "gathers/s", "frac": evals_s * G / r_gather,
+                         "unit": "gathers/s", "frac": evals_s * G / r_gather if r_gather else None,
                          "frac_vs_guide_peak": evals_s * G / GUIDE_LDS_GATHER_PEAK,
                          "guide_peak": GUIDE_LDS_GATHER_PEAK,
                          "peak_source": "measured random ds_read_b64 ceiling "
                                         "(vrpms_probe_lds_gather, 1024-lane WGs, 2/CU); the "
                                         "guide's conflict-free ds_read_b64 rate is ~19.7 T/s",
                          "G_per_eval": G, "issued_per_eval": n,
-                         "frac_issued": evals_s * n / r_gather,
+                         "frac_issued": evals_s * n / r_gather if r_gather else None,
                          # launch_words2's auto grid: two tours per lane, one
                          # 1024-lane workgroup per CU
                          "traffic": pmc_traffic("eval_cvrp_words2",
@@ -1390,13 +1438,15 @@ def main():
             "hbm_roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
                              "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                              "bytes_per_launch": bytes_per_launch},
-            "rows_layout": {"kernel": "eval_cvrp_rows2", "evals_per_s": C / (rows_ms * 1e-3),
-                            "kernel_ms": rows_ms,
-                            "lds_gather_frac": C / (rows_ms * 1e-3) * G / r_gather},
         }
         import numpy as np
-        same = bool(torch.equal(keys, keys_rows))
-        out["rows_vs_words_identical"] = same
+        if full:
+            out["rows_layout"] = {"kernel": "eval_cvrp_rows2", "evals_per_s": C / (rows_ms * 1e-3),
+                                  "kernel_ms": rows_ms,
+                                  "lds_gather_frac": C / (rows_ms * 1e-3) * G / r_gather}
+            out["rows_vs_words_identical"] = bool(torch.equal(keys, keys_rows))
+        else:
+            out["roofline"]["peak_source"] += "; measured by --full only"
         if qual is not None:
             out["quality"] = qual
         if xq is not None:
@@ -1409,13 +1459,13 @@ def main():
             out["quality_tdvrp200_het"] = hetq
         if isl is not None:
             out["islands"] = isl
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             progress("cpu baseline")
             cb, ref, S = cpu_baseline(inst, perms, args.cpu_seconds)
             got = keys[:S].cpu().numpy().view(np.uint64)
             cb["parity_on_sample"] = bool((got == ref[0]).all())
             out["cpu_baseline"] = cb
-        if world == 1 and not args.no_other_configs:
+        if full and world == 1 and not args.no_other_configs:
             del perms, words
             try:   # secondary lines must never cost the headline line
                 progress("other configs (cfg 3-5, API legs)")
@@ -1431,7 +1481,8 @@ def main():
                 out["cfg1_main_py"] = cfg1_leg()
             except Exception:
                 out["cfg1_main_py"] = {"error": traceback.format_exc(limit=3)}
-        out["quality_summary"] = quality_summary(out)
+        if full:
+            out["quality_summary"] = quality_summary(out)
         # details first, one leg per line; the LAST line is the compact record
         # the driver parses (<= FINAL_LINE_MAX bytes)
         for ln in detail_lines(out):

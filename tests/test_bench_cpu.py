@@ -62,6 +62,46 @@ def test_detail_lines_hold_every_leg():
     assert not legs & set(bench.HEADLINE_KEYS)
 
 
+def test_a_plain_run_is_the_default_and_full_is_an_option():
+    bench = _bench()
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_holds_the_key_fields_exactly(tmp_path):
+    """--dump-outputs: float64 fields that rebuild every sampled key bit for
+    bit, the same fixed sample in every call, a small batch whole."""
+    import numpy as np
+    import torch
+    bench = _bench()
+    rng = np.random.default_rng(3)
+    k = (rng.integers(0, 4, 1000, dtype=np.uint64) << np.uint64(56)) \
+        | (rng.integers(0, 2**28, 1000, dtype=np.uint64) << np.uint64(28)) \
+        | rng.integers(0, 2**28, 1000, dtype=np.uint64)
+    k[0] = (np.uint64(255) << np.uint64(56)) | np.uint64(2**56 - 1)     # every field at its cap
+    keys = torch.from_numpy(k.view(np.int64))
+
+    def load(d):
+        f = {n: np.load(d / f"keys_{n}.npy") for n in ("unvisited", "primary", "secondary")}
+        assert sorted(p.name for p in d.iterdir()) == sorted(f"keys_{n}.npy" for n in f)
+        assert all(a.dtype == np.float64 for a in f.values())
+        return (f["unvisited"].astype(np.uint64) << np.uint64(56)) \
+            | (f["primary"].astype(np.uint64) << np.uint64(28)) | f["secondary"].astype(np.uint64)
+
+    bench.dump_outputs(keys, str(tmp_path / "all"))
+    assert (load(tmp_path / "all") == k).all()
+    bench.dump_outputs(keys, str(tmp_path / "a"), sample=64)
+    bench.dump_outputs(keys, str(tmp_path / "b"), sample=64)
+    a, b = load(tmp_path / "a"), load(tmp_path / "b")
+    assert a.shape == (64,) and (a == b).all()
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(1000, 64, replace=False))
+    assert len(set(idx.tolist())) == 64 and (a == k[idx]).all()
+    # the default sample stays far below the 64 MB a dump may take
+    assert 3 * 8 * bench.DUMP_SAMPLE <= 32 << 20
+
+
 STUB = textwrap.dedent("""
     import json, os, sys, time
     r = int(os.environ["RANK"])
