@@ -283,6 +283,20 @@ int vrpms_aco_iteration(vrpms_ctx* ctx, const vrpms_aco_params* p, uint32_t* d_t
 int vrpms_bf_run(vrpms_ctx* ctx, int32_t n, uint64_t rank_begin, uint64_t rank_end,
                  uint64_t* d_out, void* stream);
 
+/* Exact TSP by Held-Karp subset dynamic programming (spec A14): customers
+ * 1..n (1 <= n <= min(24, N-1)) of the loaded TSP instance, static matrix
+ * only (H = 1; it may be asymmetric), node 0 the start node.  The caller owns
+ * the table: vrpms_tsp_dp_workspace gives its size in bytes (host only, no
+ * context; 2^n rows of 16 words for n <= 16, of 32 words above: 2 GiB at
+ * n = 24).  vrpms_tsp_dp_run enqueues one launch per subset cardinality on
+ * `stream` and writes d_tour[n] -- the lexicographically smallest optimal
+ * tour, the same tie rule as vrpms_bf_run's smallest rank -- and d_key[0],
+ * its A8 key.  VRPMS_EINVAL for a CVRP or hour-indexed instance, n out of
+ * range or a workspace smaller than vrpms_tsp_dp_workspace's. */
+int vrpms_tsp_dp_workspace(int32_t n, uint64_t* bytes);
+int vrpms_tsp_dp_run(vrpms_ctx* ctx, int32_t n, void* d_work, uint64_t work_bytes,
+                     int16_t* d_tour, uint64_t* d_key, void* stream);
+
 /* Throughput mode (BASELINE.json config 5: many concurrent TSP requests):
  * R independent static TSP requests, each with its own int32 [N][N] matrix
  * (d_mats [R][N][N], node 0 = start node), ONE WORKGROUP PER REQUEST: 4 SA

@@ -300,6 +300,21 @@ class Context:
         k, r = out.cpu().tolist()
         return k & (2**64 - 1), r & (2**64 - 1)
 
+    def tsp_dp(self, n: int):
+        """Held-Karp optimum over customers 1..n of the loaded static TSP
+        instance -> (key, lexicographically smallest optimal tour).  The
+        table (vrpms_tsp_dp_workspace: 2 GiB at n = 24) is a torch tensor, so
+        it returns to torch's allocator cache after the call."""
+        torch = _torch()
+        nbytes = ctypes.c_uint64()
+        check(self.lib.vrpms_tsp_dp_workspace(int(n), ctypes.byref(nbytes)))
+        work = torch.empty(nbytes.value, dtype=torch.uint8, device=self.dev)
+        tour = torch.empty(int(n), dtype=torch.int16, device=self.dev)
+        key = torch.empty(1, dtype=torch.int64, device=self.dev)
+        check(self.lib.vrpms_tsp_dp_run(self._ctx, int(n), work.data_ptr(), nbytes.value,
+                                        tour.data_ptr(), key.data_ptr(), self.stream()))
+        k = key.cpu().item()     # synchronises: the table may be released after it
+        return k & (2**64 - 1), [int(c) for c in tour.cpu().tolist()]
 
     def tsp_batch_sa(self, mats, steps: int, inv_t0: float, inv_alpha: float, seed: int):
         """One workgroup per request: mats int32 [R][N][N] on the device ->

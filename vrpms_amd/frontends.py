@@ -608,7 +608,7 @@ def _http_worker_main(w, arena, lo, hi, host, port, submit_qs, done_q, store, ba
                 return
             parts = path.split("/")
             if method == "POST" and len(parts) == 4 and parts[1] == "solve" and \
-                    parts[2] in ("tsp", "vrp") and parts[3] in service.TITLES:
+                    parts[3] in service.INLINE_ALGORITHMS.get(parts[2], ()):
                 # the remote front-end's inline route (vrpms_amd.remote), run by
                 # an owner's App.solve_inline
                 key = ("solve:" + parts[2], parts[3])

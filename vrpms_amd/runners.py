@@ -253,6 +253,12 @@ def brute_force(ctx: Context, n: int, rank_begin: int = 0, rank_end: int | None 
     return key, unrank(rank, n) if rank != 2**64 - 1 else None
 
 
+def held_karp(ctx: Context, n: int):
+    """Exact optimum by subset dynamic programming (static TSP, n <= 24) ->
+    (key, tour): the same key and tour as brute_force wherever both run."""
+    return ctx.tsp_dp(n)
+
+
 def unrank(rank: int, n: int):
     """Lexicographic rank -> permutation of 1..n (host-side index arithmetic)."""
     avail = list(range(1, n + 1))

@@ -33,6 +33,10 @@ from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
 
 TITLES = {"bf": "Brute Force", "ga": "Genetic Algorithm", "sa": "Simulated Annealing",
           "aco": "Ant Colony Optimization"}
+# algorithms of the inline route POST /solve/<problem>/<algo>: the endpoints'
+# and, for the TSP, the exact Held-Karp solver "dp" (it has no /api endpoint:
+# the eight endpoints are the reference's wire contract)
+INLINE_ALGORITHMS = {"tsp": tuple(TITLES) + ("dp",), "vrp": tuple(TITLES)}
 
 # (body key, params key) in the order the reference checks them
 # (api/parameters.py:4-15 and 34-44); 'auth' is the only optional one
@@ -365,7 +369,7 @@ class App:
         knobs = dict(knobs)
         mt = multi_threaded(knobs.get("multi_threaded"))
         islands = n > self.island_min_n if mt is None else mt
-        if len(self.devices) > 1 and algorithm != "bf" and islands:
+        if len(self.devices) > 1 and algorithm not in ("bf", "dp") and islands:
             held = sorted(set(self.devices))   # each lock once, in one global order
             for d in held:
                 self.locks[d].acquire()
@@ -470,7 +474,9 @@ class App:
 
     def solve_inline(self, problem: str, algorithm: str, raw: bytes):
         """POST /solve/{tsp,vrp}/<algo>: the instance inline (no DB) -- what a
-        host without a GPU sends to the GPU box (vrpms_amd.remote).  Body: the
+        host without a GPU sends to the GPU box (vrpms_amd.remote).  <algo> is
+        an endpoint name or, for tsp only, "dp" (exact Held-Karp, up to 24
+        customers on a static matrix: INLINE_ALGORITHMS).  Body: the
         solve_tsp / solve_vrp arguments in the request's camelCase names
         ("durations" is the DB's `matrix` payload); response as the
         handlers': {"success": true, "message": result} or a 400 error list."""
@@ -481,7 +487,7 @@ class App:
         except ValueError as e:
             return 400, {"success": False,
                          "errors": [{"what": "Invalid request", "reason": str(e)}]}
-        if problem not in ("tsp", "vrp") or algorithm not in TITLES:
+        if algorithm not in INLINE_ALGORITHMS.get(problem, ()):
             return 400, {"success": False, "errors": [
                 {"what": "Invalid request", "reason": f"no solver /solve/{problem}/{algorithm}"}]}
         names = (["durations", "customers", "startNode", "startTime"] if problem == "tsp" else

@@ -11,7 +11,8 @@ and adds the two calls the eight handler TODO slots make:
       -> {'durationMax': int, 'durationSum': int,
           'vehicles': [{'tour': [0, ..., 0], 'duration': int}, ...]}
                                                        api/vrp/ga/index.py:48-53
-`algorithm` is the endpoint name: 'bf', 'ga', 'sa' or 'aco'.  All search
+`algorithm` is the endpoint name: 'bf', 'ga', 'sa' or 'aco', or 'dp' (TSP
+only: the exact Held-Karp subset DP, spec A14).  All search
 and scoring runs in the gfx950 kernels (vrpms_amd.core); this module only
 builds the compact instance and maps results
 back to matrix indices.  Node ids in results are matrix row indices
@@ -30,7 +31,7 @@ import numpy as np
 from . import runners
 from .core import CVRP, OBJ_MAX, OBJ_SUM, TSP, Context
 
-ALGORITHMS = ("bf", "ga", "sa", "aco")
+ALGORITHMS = ("bf", "ga", "sa", "aco", "dp")
 # exhaustive search over n! giant tours: 13! = 6.2 G tours is ~0.1 s at the
 # measured ~64 G evals/s of bf_kernel on one MI355X (bench "search.bf") on a
 # static matrix; an hour-indexed one prices every edge at its departure
@@ -38,6 +39,9 @@ ALGORITHMS = ("bf", "ga", "sa", "aco")
 # vrpms_bf_run itself accepts n <= 15 (nibble-packed tours)
 BF_MAX_CUSTOMERS = 13
 BF_MAX_CUSTOMERS_TD = 11
+# Held-Karp (A14, static TSP only): O(2^n n^2) steps over a table of 2^n rows,
+# 2 GiB at 24 customers (vrpms_tsp_dp_workspace)
+DP_MAX_CUSTOMERS = 24
 # SA on tours of more than SA_WINDOW_MIN_N customers samples A11 windowed
 # moves (second position within SA_WINDOW of the first)
 SA_WINDOW, SA_WINDOW_MIN_N = 32, 150
@@ -196,6 +200,18 @@ def _runner(ctx: Context, ci: CompactInstance, algorithm: str, seed: int, knobs:
     raise ValueError(f"unknown algorithm {algorithm!r}; expected one of {ALGORITHMS}")
 
 
+def _check_dp(ci: CompactInstance):
+    """A14's domain, checked on the host before any device is touched."""
+    if ci.problem != TSP:
+        raise ValueError("dp solves the TSP only")
+    if ci.n > DP_MAX_CUSTOMERS:
+        raise ValueError(f"dp (Held-Karp) supports at most {DP_MAX_CUSTOMERS} customers "
+                         f"({ci.n} given)")
+    if ci.durations.shape[0] != 1:
+        raise ValueError("dp (Held-Karp) needs a static duration matrix: with hour-indexed "
+                         "durations the earliest arrival per (subset, node) is not an exact state")
+
+
 def search_islands(ci: CompactInstance, algorithm: str, devices, seed: int = 0,
                    time_limit: float | None = None, objective: int = OBJ_SUM, **knobs):
     """The island model inside one process: one SA / GA / ACO
@@ -205,7 +221,7 @@ def search_islands(ci: CompactInstance, algorithm: str, devices, seed: int = 0,
     island."""
     import torch
     from . import islands
-    if ci.n <= 1 or algorithm == "bf":
+    if ci.n <= 1 or algorithm in ("bf", "dp"):
         raise ValueError("search_islands: SA / GA / ACO on two or more customers")
     rs, epochs = [], 1
     for d, dev in enumerate(devices):
@@ -226,10 +242,14 @@ def search(ctx: Context, ci: CompactInstance, algorithm: str, seed: int = 0,
            time_limit: float | None = None, **knobs):
     """Run one algorithm on the loaded instance -> (key, compact giant tour)."""
     n = ci.n
+    if algorithm == "dp":
+        _check_dp(ci)
     if n == 0:
         return None, []
     if n == 1:
         return None, [1]
+    if algorithm == "dp":
+        return runners.held_karp(ctx, n)
     if algorithm == "bf":
         cap = BF_MAX_CUSTOMERS if ci.durations.shape[0] == 1 else BF_MAX_CUSTOMERS_TD
         if n > cap:
@@ -269,10 +289,12 @@ def _remote():
 def _searched(ci, algorithm, seed, time_limit, device, devices, objective, knobs):
     """(context holding the instance, compact tour): one device, or the
     island model across `devices` (two or more) for SA / GA / ACO."""
-    if devices is not None and len(devices) > 1 and algorithm != "bf" and ci.n > 1:
+    if devices is not None and len(devices) > 1 and algorithm not in ("bf", "dp") and ci.n > 1:
         _, tour = search_islands(ci, algorithm, list(devices), seed=seed, time_limit=time_limit,
                                  objective=objective, **knobs)
         return context(devices[0]), tour
+    if algorithm == "dp" and devices:
+        device = devices[0]
     ctx = context(device)
     load(ctx, ci, objective)
     _, tour = search(ctx, ci, algorithm, seed=seed, time_limit=time_limit, **knobs)
@@ -282,12 +304,20 @@ def _searched(ci, algorithm, seed, time_limit, device, devices, objective, knobs
 def solve_tsp(algorithm: str, durations, customers, start_node, start_time=0, *, seed: int = 0,
               time_limit: float | None = None, device: int = 0, devices=None, **knobs) -> dict:
     """Result dict of the TSP TODO slot (api/tsp/ga/index.py:40-44).
-    `devices` (two or more): SA / GA / ACO as an island model across them."""
+    `devices` (two or more): SA / GA / ACO as an island model across them;
+    "dp" runs on the first of them, "bf" on `device`.  "dp" (exact, at most DP_MAX_CUSTOMERS
+    customers, static matrix) ignores `seed` and `time_limit`, as "bf" does;
+    its domain is checked before any device or remote is touched."""
+    ci = None
+    if algorithm == "dp":
+        ci = compact_tsp(durations, customers, start_node, start_time)
+        _check_dp(ci)
     rem = _remote()
     if rem is not None:
         return rem.solve_tsp(algorithm, durations, customers, start_node, start_time, seed=seed,
                              time_limit=time_limit, **knobs)
-    ci = compact_tsp(durations, customers, start_node, start_time)
+    if ci is None:
+        ci = compact_tsp(durations, customers, start_node, start_time)
     ctx, tour = _searched(ci, algorithm, seed, time_limit, device, devices, OBJ_SUM, knobs)
     _, dur = _decode(ctx, tour)
     vehicle = [ci.nodes[0]] + [ci.nodes[c] for c in tour] + [ci.nodes[0]]
@@ -300,6 +330,9 @@ def solve_vrp(algorithm: str, durations, locations, capacities, start_times,
               devices=None, with_unvisited: bool = False, **knobs) -> dict:
     """Result dict of the VRP TODO slot (api/vrp/ga/index.py:48-53); A7 shapes.
     `devices` (two or more): SA / GA / ACO as an island model across them."""
+    if algorithm == "dp":
+        raise ValueError("dp solves the TSP only (the greedy split of a giant tour does not "
+                         "decompose over subsets); use bf, sa, ga or aco for the VRP")
     rem = _remote()
     if rem is not None:
         out = rem.solve_vrp(algorithm, durations, locations, capacities, start_times,
