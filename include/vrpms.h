@@ -297,6 +297,25 @@ int vrpms_tsp_dp_workspace(int32_t n, uint64_t* bytes);
 int vrpms_tsp_dp_run(vrpms_ctx* ctx, int32_t n, void* d_work, uint64_t work_bytes,
                      int16_t* d_tour, uint64_t* d_key, void* stream);
 
+/* Exact small-fleet CVRP by subset partition dynamic programming (spec A15):
+ * customers 1..n (1 <= n <= min(20, N-1)) of the loaded CVRP instance, static
+ * matrix only (H = 1; it may be asymmetric), node 0 the depot, the K <= 64
+ * vehicles, their capacities, the demands and the objective as loaded.
+ * Minimises (unvisited, primary) exactly over all A10 separator tours; the
+ * secondary field is whatever the returned solution has.  The caller owns the
+ * workspace: vrpms_vrp_sp_workspace gives its size in bytes (host only, no
+ * context: the Held-Karp table of vrpms_tsp_dp_workspace plus K + 3 arrays of
+ * 2^n words).  vrpms_vrp_sp_run enqueues the Held-Karp layers, then one
+ * launch per vehicle, on `stream` and writes d_tour[n + K] -- route 0, a
+ * separator 0, route 1, 0, ..., route K-1, 0, then the unserved customers in
+ * ascending order -- and d_key[0], the A8 key of that tour.  VRPMS_EINVAL,
+ * with nothing launched, for a TSP or hour-indexed instance, n out of range,
+ * more than 64 vehicles or a workspace smaller than vrpms_vrp_sp_workspace's
+ * or not 4-byte aligned. */
+int vrpms_vrp_sp_workspace(int32_t n, int32_t K, uint64_t* bytes);
+int vrpms_vrp_sp_run(vrpms_ctx* ctx, int32_t n, void* d_work, uint64_t work_bytes,
+                     int16_t* d_tour, uint64_t* d_key, void* stream);
+
 /* Throughput mode (BASELINE.json config 5: many concurrent TSP requests):
  * R independent static TSP requests, each with its own int32 [N][N] matrix
  * (d_mats [R][N][N], node 0 = start node), ONE WORKGROUP PER REQUEST: 4 SA

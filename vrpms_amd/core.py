@@ -316,6 +316,24 @@ class Context:
         k = key.cpu().item()     # synchronises: the table may be released after it
         return k & (2**64 - 1), [int(c) for c in tour.cpu().tolist()]
 
+    def vrp_sp(self, n: int):
+        """Set-partitioning optimum (spec A15) over customers 1..n of the
+        loaded static CVRP instance, its vehicles and objective -> (key,
+        tour of n + K tokens: route 0, separator, ..., route K-1, separator,
+        then the unserved customers).  The workspace
+        (vrpms_vrp_sp_workspace) is a torch tensor, so it returns to torch's
+        allocator cache after the call."""
+        torch = _torch()
+        nbytes = ctypes.c_uint64()
+        check(self.lib.vrpms_vrp_sp_workspace(int(n), int(self.K), ctypes.byref(nbytes)))
+        work = torch.empty(nbytes.value, dtype=torch.uint8, device=self.dev)
+        tour = torch.empty(int(n) + self.K, dtype=torch.int16, device=self.dev)
+        key = torch.empty(1, dtype=torch.int64, device=self.dev)
+        check(self.lib.vrpms_vrp_sp_run(self._ctx, int(n), work.data_ptr(), nbytes.value,
+                                        tour.data_ptr(), key.data_ptr(), self.stream()))
+        k = key.cpu().item()     # synchronises: the workspace may be released after it
+        return k & (2**64 - 1), [int(c) for c in tour.cpu().tolist()]
+
     def tsp_batch_sa(self, mats, steps: int, inv_t0: float, inv_alpha: float, seed: int):
         """One workgroup per request: mats int32 [R][N][N] on the device ->
         (best tours int16 [R][N-1], best keys int64 [R])."""

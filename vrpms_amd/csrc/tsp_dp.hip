@@ -30,6 +30,8 @@
 //                         Gosper's next-same-popcount mask.
 //   tsp_dp_walk_kernel    one wavefront: the last layer (g[all][0]) and the
 //                         forward walk; writes the tour and the A8 key.
+// tsp_dp_fill (the init and layer launches) is shared with vrp_sp.hip, whose
+// route costs are this table's rows (tsp_dp.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,29 +39,14 @@
 
 #include "common.hpp"
 #include "ctx.hpp"
+#include "tsp_dp.hpp"
 
 namespace vrpms {
 
-constexpr int kDpMaxN = 24;
-constexpr int kDpNodes = kDpMaxN + 1;
 constexpr int kDpLd = 33;        // LDS row stride of the transposed matrix (words)
 constexpr int kDpMinChunk = 16;  // subsets per lane group at least: amortises the unrank
 
-struct DpBinom {
-  uint32_t v[kDpNodes][kDpNodes];  // v[c][t] = C(c, t), 0 for t > c
-};
-
-constexpr DpBinom dp_make_binom() {
-  DpBinom b{};
-  for (int c = 0; c < kDpNodes; ++c) {
-    b.v[c][0] = 1;
-    for (int t = 1; t <= c; ++t) b.v[c][t] = b.v[c - 1][t - 1] + b.v[c - 1][t];
-  }
-  return b;
-}
-
 __constant__ DpBinom kDpBinom = dp_make_binom();
-static constexpr DpBinom kDpBinomHost = dp_make_binom();
 
 struct DpArgs {
   const int32_t* D;  // [N][N] static matrix of the loaded instance
@@ -72,12 +59,6 @@ struct DpArgs {
 __global__ void tsp_dp_init_kernel(DpArgs a, int npad) {
   const int l = threadIdx.x;
   if (l < npad) a.g[l] = l < a.n ? (uint32_t)a.D[(int64_t)(l + 1) * a.N] : 0xffffffffu;
-}
-
-// the next larger mask with the same number of set bits (Gosper)
-VRPMS_DEV uint32_t dp_next_mask(uint32_t m) {
-  const uint32_t c = m & (0u - m), r = m + c;
-  return (((r ^ m) >> 2) >> __builtin_ctz(c)) | r;
 }
 
 template <int NPAD>
@@ -166,7 +147,30 @@ __global__ __launch_bounds__(64) void tsp_dp_walk_kernel(DpArgs a, int npad, int
   if (l == 0) *key = pack_key(0, total, 0);
 }
 
-static int dp_npad(int n) { return n > 16 ? 32 : 16; }
+int tsp_dp_fill(vrpms_ctx* ctx, int n, uint32_t* g, hipStream_t s) {
+  const Instance& in = ctx->inst;
+  const int npad = dp_npad(n);
+  DpArgs a{in.mat32, in.N, n, 0, 1, 1, g};
+  tsp_dp_init_kernel<<<1, 64, 0, s>>>(a, npad);
+  VRPMS_HIP(hipGetLastError());
+  // two rounds of a full chip of lane groups per layer, each group at least
+  // kDpMinChunk consecutive subsets
+  const uint64_t groups_per_block = 256 / npad;
+  const uint64_t groups_target = (uint64_t)ctx->num_cus * 8 * groups_per_block * 2;
+  for (int k = 1; k < n; ++k) {
+    a.k = k;
+    a.count = kDpBinomHost.v[n][k];
+    a.chunk = (uint32_t)std::max<uint64_t>(kDpMinChunk, (a.count + groups_target - 1) / groups_target);
+    const uint64_t groups = ((uint64_t)a.count + a.chunk - 1) / a.chunk;
+    const unsigned blocks = (unsigned)((groups + groups_per_block - 1) / groups_per_block);
+    if (npad == 16)
+      tsp_dp_layer_kernel<16><<<blocks, 256, 0, s>>>(a);
+    else
+      tsp_dp_layer_kernel<32><<<blocks, 256, 0, s>>>(a);
+    VRPMS_HIP(hipGetLastError());
+  }
+  return VRPMS_OK;
+}
 
 }  // namespace vrpms
 
@@ -204,25 +208,9 @@ extern "C" int vrpms_tsp_dp_run(vrpms_ctx* ctx, int32_t n, void* d_work, uint64_
     return fail(VRPMS_EINVAL, "vrpms_tsp_dp_run: workspace must be 4-byte aligned");
   VRPMS_HIP(hipSetDevice(ctx->device));
   hipStream_t s = (hipStream_t)stream;
-  DpArgs a{in.mat32, in.N, n, 0, 1, 1, static_cast<uint32_t*>(d_work)};
-  tsp_dp_init_kernel<<<1, 64, 0, s>>>(a, npad);
-  VRPMS_HIP(hipGetLastError());
-  // two rounds of a full chip of lane groups per layer, each group at least
-  // kDpMinChunk consecutive subsets
-  const uint64_t groups_per_block = 256 / npad;
-  const uint64_t groups_target = (uint64_t)ctx->num_cus * 8 * groups_per_block * 2;
-  for (int k = 1; k < n; ++k) {
-    a.k = k;
-    a.count = kDpBinomHost.v[n][k];
-    a.chunk = (uint32_t)std::max<uint64_t>(kDpMinChunk, (a.count + groups_target - 1) / groups_target);
-    const uint64_t groups = ((uint64_t)a.count + a.chunk - 1) / a.chunk;
-    const unsigned blocks = (unsigned)((groups + groups_per_block - 1) / groups_per_block);
-    if (npad == 16)
-      tsp_dp_layer_kernel<16><<<blocks, 256, 0, s>>>(a);
-    else
-      tsp_dp_layer_kernel<32><<<blocks, 256, 0, s>>>(a);
-    VRPMS_HIP(hipGetLastError());
-  }
+  const int rc = tsp_dp_fill(ctx, n, static_cast<uint32_t*>(d_work), s);
+  if (rc != VRPMS_OK) return rc;
+  const DpArgs a{in.mat32, in.N, n, n, 0, 1, static_cast<uint32_t*>(d_work)};
   tsp_dp_walk_kernel<<<1, 64, 0, s>>>(a, npad, d_tour, d_key);
   VRPMS_HIP(hipGetLastError());
   return VRPMS_OK;

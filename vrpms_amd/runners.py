@@ -259,6 +259,13 @@ def held_karp(ctx: Context, n: int):
     return ctx.tsp_dp(n)
 
 
+def set_partition(ctx: Context, n: int):
+    """Exact optimum of (unvisited, primary) over all separator tours of the
+    loaded static CVRP instance (n <= 20, K <= 64; spec A15) -> (key, tour
+    of n + K tokens)."""
+    return ctx.vrp_sp(n)
+
+
 def unrank(rank: int, n: int):
     """Lexicographic rank -> permutation of 1..n (host-side index arithmetic)."""
     avail = list(range(1, n + 1))

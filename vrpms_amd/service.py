@@ -34,9 +34,10 @@ from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
 TITLES = {"bf": "Brute Force", "ga": "Genetic Algorithm", "sa": "Simulated Annealing",
           "aco": "Ant Colony Optimization"}
 # algorithms of the inline route POST /solve/<problem>/<algo>: the endpoints'
-# and, for the TSP, the exact Held-Karp solver "dp" (it has no /api endpoint:
-# the eight endpoints are the reference's wire contract)
-INLINE_ALGORITHMS = {"tsp": tuple(TITLES) + ("dp",), "vrp": tuple(TITLES)}
+# and the exact solvers, "dp" (Held-Karp) for the TSP and "sp" (set
+# partitioning) for the VRP (they have no /api endpoint: the eight endpoints
+# are the reference's wire contract)
+INLINE_ALGORITHMS = {"tsp": tuple(TITLES) + ("dp",), "vrp": tuple(TITLES) + ("sp",)}
 
 # (body key, params key) in the order the reference checks them
 # (api/parameters.py:4-15 and 34-44); 'auth' is the only optional one
@@ -369,7 +370,7 @@ class App:
         knobs = dict(knobs)
         mt = multi_threaded(knobs.get("multi_threaded"))
         islands = n > self.island_min_n if mt is None else mt
-        if len(self.devices) > 1 and algorithm not in ("bf", "dp") and islands:
+        if len(self.devices) > 1 and algorithm not in ("bf", "dp", "sp") and islands:
             held = sorted(set(self.devices))   # each lock once, in one global order
             for d in held:
                 self.locks[d].acquire()
@@ -476,7 +477,9 @@ class App:
         """POST /solve/{tsp,vrp}/<algo>: the instance inline (no DB) -- what a
         host without a GPU sends to the GPU box (vrpms_amd.remote).  <algo> is
         an endpoint name or, for tsp only, "dp" (exact Held-Karp, up to 24
-        customers on a static matrix: INLINE_ALGORITHMS).  Body: the
+        customers on a static matrix), or, for vrp only, "sp" (exact set
+        partitioning, up to solver.SP_MAX_CUSTOMERS customers and 64 vehicles
+        on a static matrix: INLINE_ALGORITHMS).  Body: the
         solve_tsp / solve_vrp arguments in the request's camelCase names
         ("durations" is the DB's `matrix` payload); response as the
         handlers': {"success": true, "message": result} or a 400 error list."""

@@ -12,7 +12,8 @@ and adds the two calls the eight handler TODO slots make:
           'vehicles': [{'tour': [0, ..., 0], 'duration': int}, ...]}
                                                        api/vrp/ga/index.py:48-53
 `algorithm` is the endpoint name: 'bf', 'ga', 'sa' or 'aco', or 'dp' (TSP
-only: the exact Held-Karp subset DP, spec A14).  All search
+only: the exact Held-Karp subset DP, spec A14), or 'sp' (VRP only: the exact
+subset partition DP over all separator tours, spec A15).  All search
 and scoring runs in the gfx950 kernels (vrpms_amd.core); this module only
 builds the compact instance and maps results
 back to matrix indices.  Node ids in results are matrix row indices
@@ -31,7 +32,7 @@ import numpy as np
 from . import runners
 from .core import CVRP, OBJ_MAX, OBJ_SUM, TSP, Context
 
-ALGORITHMS = ("bf", "ga", "sa", "aco", "dp")
+ALGORITHMS = ("bf", "ga", "sa", "aco", "dp", "sp")
 # exhaustive search over n! giant tours: 13! = 6.2 G tours is ~0.1 s at the
 # measured ~64 G evals/s of bf_kernel on one MI355X (bench "search.bf") on a
 # static matrix; an hour-indexed one prices every edge at its departure
@@ -42,6 +43,13 @@ BF_MAX_CUSTOMERS_TD = 11
 # Held-Karp (A14, static TSP only): O(2^n n^2) steps over a table of 2^n rows,
 # 2 GiB at 24 customers (vrpms_tsp_dp_workspace)
 DP_MAX_CUSTOMERS = 24
+# set partitioning (A15, static VRP only): 3^n steps per vehicle.  The kernel
+# accepts 20 customers; the cap here is a time budget, the largest n <= 20
+# whose median Context.vrp_sp time at K = 8 on one MI355X is at most 1 s:
+# measured 0.090 s at n = 20 (tools/sp_rate.py), so it is the
+# kernel's own limit.  vrpms_vrp_sp_run accepts K <= 64
+SP_MAX_CUSTOMERS = 20
+SP_MAX_VEHICLES = 64
 # SA on tours of more than SA_WINDOW_MIN_N customers samples A11 windowed
 # moves (second position within SA_WINDOW of the first)
 SA_WINDOW, SA_WINDOW_MIN_N = 32, 150
@@ -212,6 +220,22 @@ def _check_dp(ci: CompactInstance):
                          "durations the earliest arrival per (subset, node) is not an exact state")
 
 
+def _check_sp(ci: CompactInstance):
+    """A15's domain, checked on the host before any device is touched."""
+    if ci.problem != CVRP:
+        raise ValueError('sp solves the VRP only; use "dp" for the exact TSP')
+    if ci.n > SP_MAX_CUSTOMERS:
+        raise ValueError(f"sp (set partitioning) supports at most {SP_MAX_CUSTOMERS} customers "
+                         f"({ci.n} given)")
+    if len(ci.capacities) > SP_MAX_VEHICLES:
+        raise ValueError(f"sp (set partitioning) supports at most {SP_MAX_VEHICLES} vehicles "
+                         f"({len(ci.capacities)} given)")
+    if ci.durations.shape[0] != 1:
+        raise ValueError("sp (set partitioning) needs a static duration matrix: with "
+                         "hour-indexed durations a route's duration depends on its start time "
+                         "and the earliest arrival per (subset, node) is not an exact state")
+
+
 def search_islands(ci: CompactInstance, algorithm: str, devices, seed: int = 0,
                    time_limit: float | None = None, objective: int = OBJ_SUM, **knobs):
     """The island model inside one process: one SA / GA / ACO
@@ -221,7 +245,7 @@ def search_islands(ci: CompactInstance, algorithm: str, devices, seed: int = 0,
     island."""
     import torch
     from . import islands
-    if ci.n <= 1 or algorithm in ("bf", "dp"):
+    if ci.n <= 1 or algorithm in ("bf", "dp", "sp"):
         raise ValueError("search_islands: SA / GA / ACO on two or more customers")
     rs, epochs = [], 1
     for d, dev in enumerate(devices):
@@ -244,8 +268,12 @@ def search(ctx: Context, ci: CompactInstance, algorithm: str, seed: int = 0,
     n = ci.n
     if algorithm == "dp":
         _check_dp(ci)
+    if algorithm == "sp":
+        _check_sp(ci)
     if n == 0:
         return None, []
+    if algorithm == "sp":
+        return runners.set_partition(ctx, n)
     if n == 1:
         return None, [1]
     if algorithm == "dp":
@@ -289,11 +317,11 @@ def _remote():
 def _searched(ci, algorithm, seed, time_limit, device, devices, objective, knobs):
     """(context holding the instance, compact tour): one device, or the
     island model across `devices` (two or more) for SA / GA / ACO."""
-    if devices is not None and len(devices) > 1 and algorithm not in ("bf", "dp") and ci.n > 1:
+    if devices is not None and len(devices) > 1 and algorithm not in ("bf", "dp", "sp") and ci.n > 1:
         _, tour = search_islands(ci, algorithm, list(devices), seed=seed, time_limit=time_limit,
                                  objective=objective, **knobs)
         return context(devices[0]), tour
-    if algorithm == "dp" and devices:
+    if algorithm in ("dp", "sp") and devices:
         device = devices[0]
     ctx = context(device)
     load(ctx, ci, objective)
@@ -309,6 +337,9 @@ def solve_tsp(algorithm: str, durations, customers, start_node, start_time=0, *,
     customers, static matrix) ignores `seed` and `time_limit`, as "bf" does;
     its domain is checked before any device or remote is touched."""
     ci = None
+    if algorithm == "sp":
+        raise ValueError('sp solves the VRP only (set partitioning over a fleet); use "dp" for '
+                         'the exact TSP')
     if algorithm == "dp":
         ci = compact_tsp(durations, customers, start_node, start_time)
         _check_dp(ci)
@@ -329,10 +360,20 @@ def solve_vrp(algorithm: str, durations, locations, capacities, start_times,
               objective: str = "sum", time_limit: float | None = None, device: int = 0,
               devices=None, with_unvisited: bool = False, **knobs) -> dict:
     """Result dict of the VRP TODO slot (api/vrp/ga/index.py:48-53); A7 shapes.
-    `devices` (two or more): SA / GA / ACO as an island model across them."""
+    `devices` (two or more): SA / GA / ACO as an island model across them.
+    "sp" (exact over all separator tours: at most SP_MAX_CUSTOMERS customers
+    and SP_MAX_VEHICLES vehicles, static matrix) minimises (unvisited,
+    primary) only; it runs on the first of `devices`, ignores `seed` and
+    `time_limit`, and its domain is checked before any device or remote is
+    touched."""
     if algorithm == "dp":
         raise ValueError("dp solves the TSP only (the greedy split of a giant tour does not "
                          "decompose over subsets); use bf, sa, ga or aco for the VRP")
+    ci = None
+    if algorithm == "sp":
+        ci = compact_vrp(durations, locations, capacities, start_times, ignored_customers,
+                         completed_customers)
+        _check_sp(ci)
     rem = _remote()
     if rem is not None:
         out = rem.solve_vrp(algorithm, durations, locations, capacities, start_times,
@@ -344,8 +385,9 @@ def solve_vrp(algorithm: str, durations, locations, capacities, start_times,
                                            completed_customers)
             out["unvisited"] = [c for c in nodes[1:] if c not in served]
         return out
-    ci = compact_vrp(durations, locations, capacities, start_times, ignored_customers,
-                     completed_customers)
+    if ci is None:
+        ci = compact_vrp(durations, locations, capacities, start_times, ignored_customers,
+                         completed_customers)
     ctx, tour = _searched(ci, algorithm, seed, time_limit, device, devices,
                           OBJ_MAX if objective == "max" else OBJ_SUM, knobs)
     K = len(ci.capacities)
