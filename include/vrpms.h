@@ -316,6 +316,26 @@ int vrpms_vrp_sp_workspace(int32_t n, int32_t K, uint64_t* bytes);
 int vrpms_vrp_sp_run(vrpms_ctx* ctx, int32_t n, void* d_work, uint64_t work_bytes,
                      int16_t* d_tour, uint64_t* d_key, void* stream);
 
+/* Exact time-dependent TSP by time-expanded subset dynamic programming (spec
+ * A16): customers 1..n (1 <= n <= min(20, N-1)) of the loaded TSP instance,
+ * H = 1 or H = 24 (the matrix may be asymmetric, non-metric and non-FIFO),
+ * node 0 the start node, the instance's start time.  `horizon` >= 0 is an
+ * upper bound in minutes on the tour duration: the optimum is found if it is
+ * at most `horizon`, and key and tour do not depend on `horizon` then.  The
+ * caller owns the table: vrpms_tsp_tdp_workspace gives its size in bytes (host
+ * only, no context): 2^n * n rows of W = (start_time % 60 + horizon) / 60 + 1
+ * uint64 words (one hour of clock bits each), W <= 512.  vrpms_tsp_tdp_run
+ * enqueues one launch per subset cardinality on `stream` and writes d_tour[n]
+ * -- the optimal tour whose reversed sequence is lexicographically smallest --
+ * and d_key[0], its A8 key; when no tour fits the horizon d_key[0] is
+ * UINT64_MAX and d_tour all zeros.  VRPMS_EINVAL, with nothing launched, for a
+ * CVRP instance, H other than 1 or 24, n out of range, a negative horizon, one
+ * that needs more than 512 words, or a workspace smaller than
+ * vrpms_tsp_tdp_workspace's or not 8-byte aligned. */
+int vrpms_tsp_tdp_workspace(int32_t n, int32_t start_time, int32_t horizon, uint64_t* bytes);
+int vrpms_tsp_tdp_run(vrpms_ctx* ctx, int32_t n, int32_t horizon, void* d_work,
+                      uint64_t work_bytes, int16_t* d_tour, uint64_t* d_key, void* stream);
+
 /* Throughput mode (BASELINE.json config 5: many concurrent TSP requests):
  * R independent static TSP requests, each with its own int32 [N][N] matrix
  * (d_mats [R][N][N], node 0 = start node), ONE WORKGROUP PER REQUEST: 4 SA

@@ -54,6 +54,7 @@ class Context:
         self._ctx = ptr
         self.problem = None
         self.N = self.H = self.K = 0
+        self.start_times = []
         self.objective = OBJ_SUM
         # (group, world) once islands.init_comm agreed on a communicator
         self.island_comm_group = None
@@ -114,6 +115,7 @@ class Context:
             d_cap.data_ptr() if d_cap is not None else None,
             d_st.data_ptr(), K, int(objective), self.stream()))
         self.problem, self.N, self.H, self.K, self.objective = problem, N, H, K, objective
+        self.start_times = [int(t) for t in st]
 
     # -- scoring ------------------------------------------------------------
     def eval(self, perms, n: int | None = None, with_parts: bool = False, out=None):
@@ -332,6 +334,27 @@ class Context:
         check(self.lib.vrpms_vrp_sp_run(self._ctx, int(n), work.data_ptr(), nbytes.value,
                                         tour.data_ptr(), key.data_ptr(), self.stream()))
         k = key.cpu().item()     # synchronises: the workspace may be released after it
+        return k & (2**64 - 1), [int(c) for c in tour.cpu().tolist()]
+
+    def tsp_tdp(self, n: int, horizon: int):
+        """Time-expanded subset DP (spec A16) over customers 1..n of the
+        loaded TSP instance (H = 1 or 24) -> (key, the optimal tour whose
+        reversed sequence is lexicographically smallest), the optimum among
+        tours of at most `horizon` minutes; (2**64 - 1, zeros) if there is
+        none.  The table (vrpms_tsp_tdp_workspace) is a torch tensor, so it
+        returns to torch's allocator cache after the call."""
+        torch = _torch()
+        nbytes = ctypes.c_uint64()
+        start = self.start_times[0] if self.start_times else 0
+        check(self.lib.vrpms_tsp_tdp_workspace(int(n), int(start), int(horizon),
+                                               ctypes.byref(nbytes)))
+        work = torch.empty(nbytes.value, dtype=torch.uint8, device=self.dev)
+        tour = torch.empty(int(n), dtype=torch.int16, device=self.dev)
+        key = torch.empty(1, dtype=torch.int64, device=self.dev)
+        check(self.lib.vrpms_tsp_tdp_run(self._ctx, int(n), int(horizon), work.data_ptr(),
+                                         nbytes.value, tour.data_ptr(), key.data_ptr(),
+                                         self.stream()))
+        k = key.cpu().item()     # synchronises: the table may be released after it
         return k & (2**64 - 1), [int(c) for c in tour.cpu().tolist()]
 
     def tsp_batch_sa(self, mats, steps: int, inv_t0: float, inv_alpha: float, seed: int):

@@ -266,6 +266,38 @@ def set_partition(ctx: Context, n: int):
     return ctx.vrp_sp(n)
 
 
+def nearest_neighbour_duration(durations, n: int, start_time: int = 0) -> int:
+    """Duration of the nearest-neighbour tour over customers 1..n under the A3
+    clock (each edge priced at its departure hour, ties to the lowest index):
+    an upper bound on the optimum, computed on the host."""
+    D = np.asarray(durations, dtype=np.int64)
+    if D.ndim == 2:
+        D = D[None]
+    H = D.shape[0]
+    t, cur, left = int(start_time), 0, list(range(1, n + 1))
+    while left:
+        row = D[(t // 60) % H, cur]
+        nxt = min(left, key=lambda c: (int(row[c]), c))
+        t += int(row[nxt])
+        cur = nxt
+        left.remove(nxt)
+    return t + int(D[(t // 60) % H, cur, 0]) - int(start_time)
+
+
+def time_expanded(ctx: Context, n: int, durations, start_time: int, upper_bound: int | None = None):
+    """Exact optimum of the loaded TSP instance (H = 1 or 24, n <= 20) by the
+    time-expanded subset DP (spec A16) -> (key, tour).  `durations` and
+    `start_time` are the loaded instance's; `upper_bound` (minutes) bounds the
+    tour duration and defaults to the nearest-neighbour tour's.  Key and tour
+    do not depend on the bound as long as it is at least the optimum."""
+    if upper_bound is None:
+        upper_bound = nearest_neighbour_duration(durations, n, start_time)
+    key, tour = ctx.tsp_tdp(n, int(upper_bound))
+    if key == 2**64 - 1:
+        raise ValueError(f"no tour within upper_bound = {int(upper_bound)} minutes")
+    return key, tour
+
+
 def unrank(rank: int, n: int):
     """Lexicographic rank -> permutation of 1..n (host-side index arithmetic)."""
     avail = list(range(1, n + 1))

@@ -35,9 +35,10 @@ TITLES = {"bf": "Brute Force", "ga": "Genetic Algorithm", "sa": "Simulated Annea
           "aco": "Ant Colony Optimization"}
 # algorithms of the inline route POST /solve/<problem>/<algo>: the endpoints'
 # and the exact solvers, "dp" (Held-Karp) for the TSP and "sp" (set
-# partitioning) for the VRP (they have no /api endpoint: the eight endpoints
-# are the reference's wire contract)
-INLINE_ALGORITHMS = {"tsp": tuple(TITLES) + ("dp",), "vrp": tuple(TITLES) + ("sp",)}
+# partitioning) for the VRP, and "tdp" (time-expanded subset DP, hour-indexed
+# matrices) for the TSP (they have no /api endpoint: the eight endpoints are
+# the reference's wire contract)
+INLINE_ALGORITHMS = {"tsp": tuple(TITLES) + ("dp", "tdp"), "vrp": tuple(TITLES) + ("sp",)}
 
 # (body key, params key) in the order the reference checks them
 # (api/parameters.py:4-15 and 34-44); 'auth' is the only optional one
@@ -54,13 +55,15 @@ _COMMON = {
 # search knobs of solver.solve_tsp / solve_vrp that the /solve route accepts
 # in its "knobs" object (vrpms_amd.remote forwards them): name -> type
 INLINE_KNOBS = {"steps": int, "separators": int, "window": int, "chains": int,
-                "window_types": int, "pop": int, "islands": int, "colonies": int, "ants": int}
+                "window_types": int, "pop": int, "islands": int, "colonies": int, "ants": int,
+                "upper_bound": int}
 # their accepted ranges (inclusive): a value from the network outside them is a
 # 400, never an allocation (islands = 10**6 or chains = 2**30 would
 # exhaust device memory while the request holds every device lock)
 KNOB_RANGES = {"steps": (1, 10**8), "separators": (0, 4096), "window": (0, 65535),
                "chains": (1, 1 << 16), "window_types": (0, 7), "pop": (2, 4096),
-               "islands": (1, 4096), "colonies": (1, 4096), "ants": (1, 4096)}
+               "islands": (1, 4096), "colonies": (1, 4096), "ants": (1, 4096),
+               "upper_bound": (0, 2**31 - 1)}
 
 
 def check_knob(name, value):
@@ -370,7 +373,7 @@ class App:
         knobs = dict(knobs)
         mt = multi_threaded(knobs.get("multi_threaded"))
         islands = n > self.island_min_n if mt is None else mt
-        if len(self.devices) > 1 and algorithm not in ("bf", "dp", "sp") and islands:
+        if len(self.devices) > 1 and algorithm not in ("bf", "dp", "sp", "tdp") and islands:
             held = sorted(set(self.devices))   # each lock once, in one global order
             for d in held:
                 self.locks[d].acquire()
@@ -477,8 +480,9 @@ class App:
         """POST /solve/{tsp,vrp}/<algo>: the instance inline (no DB) -- what a
         host without a GPU sends to the GPU box (vrpms_amd.remote).  <algo> is
         an endpoint name or, for tsp only, "dp" (exact Held-Karp, up to 24
-        customers on a static matrix), or, for vrp only, "sp" (exact set
-        partitioning, up to solver.SP_MAX_CUSTOMERS customers and 64 vehicles
+        customers on a static matrix) or "tdp" (exact time-expanded DP, up to
+        solver.TDP_MAX_CUSTOMERS customers, hour-indexed matrices too; knob
+        "upper_bound"), or, for vrp only, "sp" (exact set partitioning, up to solver.SP_MAX_CUSTOMERS customers and 64 vehicles
         on a static matrix: INLINE_ALGORITHMS).  Body: the
         solve_tsp / solve_vrp arguments in the request's camelCase names
         ("durations" is the DB's `matrix` payload); response as the

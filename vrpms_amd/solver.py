@@ -13,7 +13,8 @@ and adds the two calls the eight handler TODO slots make:
                                                        api/vrp/ga/index.py:48-53
 `algorithm` is the endpoint name: 'bf', 'ga', 'sa' or 'aco', or 'dp' (TSP
 only: the exact Held-Karp subset DP, spec A14), or 'sp' (VRP only: the exact
-subset partition DP over all separator tours, spec A15).  All search
+subset partition DP over all separator tours, spec A15), or 'tdp' (TSP only:
+the exact time-expanded subset DP for hour-indexed matrices, spec A16).  All search
 and scoring runs in the gfx950 kernels (vrpms_amd.core); this module only
 builds the compact instance and maps results
 back to matrix indices.  Node ids in results are matrix row indices
@@ -32,7 +33,7 @@ import numpy as np
 from . import runners
 from .core import CVRP, OBJ_MAX, OBJ_SUM, TSP, Context
 
-ALGORITHMS = ("bf", "ga", "sa", "aco", "dp", "sp")
+ALGORITHMS = ("bf", "ga", "sa", "aco", "dp", "sp", "tdp")
 # exhaustive search over n! giant tours: 13! = 6.2 G tours is ~0.1 s at the
 # measured ~64 G evals/s of bf_kernel on one MI355X (bench "search.bf") on a
 # static matrix; an hour-indexed one prices every edge at its departure
@@ -50,6 +51,18 @@ DP_MAX_CUSTOMERS = 24
 # kernel's own limit.  vrpms_vrp_sp_run accepts K <= 64
 SP_MAX_CUSTOMERS = 20
 SP_MAX_VEHICLES = 64
+# time-expanded subset DP (A16, TSP, static or hour-indexed): 2^n n^2 / 4 W
+# word steps over a table of 2^n n W words, W the hours from the start to the
+# upper bound.  The kernel accepts 20 customers; the cap here follows
+# SP_MAX_CUSTOMERS' rule, the largest n <= 20 whose median Context.tsp_tdp time
+# on the synth.td_cvrp-derived family is at most 1 s on one MI355X and whose
+# table is within TDP_MAX_WORKSPACE: measured 0.018 s at n = 20 with a 12.3 GiB
+# table (tools/tdp_rate.py), so it is the kernel's own limit.
+# TDP_MAX_WORKSPACE is a policy cap: one request does not claim a large share
+# of a shared card.  TDP_MAX_WORDS is the kernel's row limit (W <= 512 hours)
+TDP_MAX_CUSTOMERS = 20
+TDP_MAX_WORKSPACE = 16 << 30
+TDP_MAX_WORDS = 512
 # SA on tours of more than SA_WINDOW_MIN_N customers samples A11 windowed
 # moves (second position within SA_WINDOW of the first)
 SA_WINDOW, SA_WINDOW_MIN_N = 32, 150
@@ -236,6 +249,38 @@ def _check_sp(ci: CompactInstance):
                          "and the earliest arrival per (subset, node) is not an exact state")
 
 
+def tdp_workspace_bytes(n: int, start_time: int, upper_bound: int) -> int:
+    """vrpms_tsp_tdp_workspace's formula: 2^n n rows of W uint64 words."""
+    return (1 << n) * n * ((int(start_time) % 60 + int(upper_bound)) // 60 + 1) * 8
+
+
+def _check_tdp(ci: CompactInstance, upper_bound=None):
+    """A16's domain and the workspace policy, checked on the host before any
+    device is touched -> the upper bound the run uses (None for n <= 1)."""
+    if ci.problem != TSP:
+        raise ValueError("tdp solves the TSP only")
+    if ci.n > TDP_MAX_CUSTOMERS:
+        raise ValueError(f"tdp (time-expanded DP) supports at most {TDP_MAX_CUSTOMERS} customers "
+                         f"({ci.n} given)")
+    if upper_bound is not None and int(upper_bound) < 0:
+        raise ValueError("tdp: upper_bound must be non-negative (minutes)")
+    if ci.n <= 1:
+        return None
+    start = int(ci.start_times[0])
+    if upper_bound is None:
+        upper_bound = runners.nearest_neighbour_duration(ci.durations, ci.n, start)
+    upper_bound = int(upper_bound)
+    need = tdp_workspace_bytes(ci.n, start, upper_bound)
+    if need > TDP_MAX_WORKSPACE:
+        raise ValueError(f"tdp (time-expanded DP) would need a table of {need} bytes for {ci.n} "
+                         f"customers and an upper bound of {upper_bound} minutes; the cap is "
+                         f"{TDP_MAX_WORKSPACE} bytes")
+    if (start % 60 + upper_bound) // 60 + 1 > TDP_MAX_WORDS or start + upper_bound >= 2**31:
+        raise ValueError(f"tdp (time-expanded DP) supports an upper bound of at most "
+                         f"{TDP_MAX_WORDS} hours from the start ({upper_bound} minutes given)")
+    return upper_bound
+
+
 def search_islands(ci: CompactInstance, algorithm: str, devices, seed: int = 0,
                    time_limit: float | None = None, objective: int = OBJ_SUM, **knobs):
     """The island model inside one process: one SA / GA / ACO
@@ -245,7 +290,7 @@ def search_islands(ci: CompactInstance, algorithm: str, devices, seed: int = 0,
     island."""
     import torch
     from . import islands
-    if ci.n <= 1 or algorithm in ("bf", "dp", "sp"):
+    if ci.n <= 1 or algorithm in ("bf", "dp", "sp", "tdp"):
         raise ValueError("search_islands: SA / GA / ACO on two or more customers")
     rs, epochs = [], 1
     for d, dev in enumerate(devices):
@@ -270,6 +315,8 @@ def search(ctx: Context, ci: CompactInstance, algorithm: str, seed: int = 0,
         _check_dp(ci)
     if algorithm == "sp":
         _check_sp(ci)
+    if algorithm == "tdp":
+        bound = _check_tdp(ci, knobs.get("upper_bound"))
     if n == 0:
         return None, []
     if algorithm == "sp":
@@ -278,6 +325,8 @@ def search(ctx: Context, ci: CompactInstance, algorithm: str, seed: int = 0,
         return None, [1]
     if algorithm == "dp":
         return runners.held_karp(ctx, n)
+    if algorithm == "tdp":
+        return runners.time_expanded(ctx, n, ci.durations, int(ci.start_times[0]), bound)
     if algorithm == "bf":
         cap = BF_MAX_CUSTOMERS if ci.durations.shape[0] == 1 else BF_MAX_CUSTOMERS_TD
         if n > cap:
@@ -317,11 +366,11 @@ def _remote():
 def _searched(ci, algorithm, seed, time_limit, device, devices, objective, knobs):
     """(context holding the instance, compact tour): one device, or the
     island model across `devices` (two or more) for SA / GA / ACO."""
-    if devices is not None and len(devices) > 1 and algorithm not in ("bf", "dp", "sp") and ci.n > 1:
+    if devices is not None and len(devices) > 1 and algorithm not in ("bf", "dp", "sp", "tdp") and ci.n > 1:
         _, tour = search_islands(ci, algorithm, list(devices), seed=seed, time_limit=time_limit,
                                  objective=objective, **knobs)
         return context(devices[0]), tour
-    if algorithm in ("dp", "sp") and devices:
+    if algorithm in ("dp", "sp", "tdp") and devices:
         device = devices[0]
     ctx = context(device)
     load(ctx, ci, objective)
@@ -335,7 +384,11 @@ def solve_tsp(algorithm: str, durations, customers, start_node, start_time=0, *,
     `devices` (two or more): SA / GA / ACO as an island model across them;
     "dp" runs on the first of them, "bf" on `device`.  "dp" (exact, at most DP_MAX_CUSTOMERS
     customers, static matrix) ignores `seed` and `time_limit`, as "bf" does;
-    its domain is checked before any device or remote is touched."""
+    its domain is checked before any device or remote is touched.  "tdp"
+    (exact, at most TDP_MAX_CUSTOMERS customers, static or hour-indexed matrix)
+    does the same; its knob `upper_bound` (minutes, default the
+    nearest-neighbour tour's duration) bounds the tour duration, and the table
+    it implies must fit TDP_MAX_WORKSPACE."""
     ci = None
     if algorithm == "sp":
         raise ValueError('sp solves the VRP only (set partitioning over a fleet); use "dp" for '
@@ -343,6 +396,9 @@ def solve_tsp(algorithm: str, durations, customers, start_node, start_time=0, *,
     if algorithm == "dp":
         ci = compact_tsp(durations, customers, start_node, start_time)
         _check_dp(ci)
+    if algorithm == "tdp":
+        ci = compact_tsp(durations, customers, start_node, start_time)
+        _check_tdp(ci, knobs.get("upper_bound"))
     rem = _remote()
     if rem is not None:
         return rem.solve_tsp(algorithm, durations, customers, start_node, start_time, seed=seed,
@@ -369,6 +425,10 @@ def solve_vrp(algorithm: str, durations, locations, capacities, start_times,
     if algorithm == "dp":
         raise ValueError("dp solves the TSP only (the greedy split of a giant tour does not "
                          "decompose over subsets); use bf, sa, ga or aco for the VRP")
+    if algorithm == "tdp":
+        raise ValueError("tdp solves the TSP only: per-vehicle start times (one table per "
+                         "vehicle) and the capacity split are out of spec A16's scope; use bf, "
+                         "sa, ga or aco for a time-dependent VRP")
     ci = None
     if algorithm == "sp":
         ci = compact_vrp(durations, locations, capacities, start_times, ignored_customers,
