@@ -336,6 +336,41 @@ int vrpms_tsp_tdp_workspace(int32_t n, int32_t start_time, int32_t horizon, uint
 int vrpms_tsp_tdp_run(vrpms_ctx* ctx, int32_t n, int32_t horizon, void* d_work,
                       uint64_t work_bytes, int16_t* d_tour, uint64_t* d_key, void* stream);
 
+/* Exact time-dependent CVRP by time-expanded partition dynamic programming
+ * (spec A17): customers 1..n (1 <= n <= min(20, N-1)) of the loaded CVRP
+ * instance, H = 1 or H = 24 (the matrix may be asymmetric, non-metric and
+ * non-FIFO), node 0 the depot, the K <= 64 vehicles in their given order with
+ * their capacities and start times (vehicle k leaves at start_times[k], no
+ * waiting anywhere), the demands and the objective as loaded.  Minimises
+ * (unvisited, primary) exactly over all A10 separator tours; the secondary
+ * field is whatever the returned solution has.  `horizon` >= 0 is an upper
+ * bound in minutes on the duration of every single route: if it is at least
+ * the optimum's primary, key and tour are those of any larger horizon.  Below
+ * that the answer is the optimum among solutions whose every route fits
+ * `horizon`, which may leave more customers unvisited: the caller owns that
+ * promise.  The caller owns the workspace: vrpms_vrp_tdsp_workspace gives its
+ * size in bytes (host only, no context) for G distinct start times, the
+ * largest being max_start: one A16 table of 2^n * n rows of
+ * W = (min(59, max_start) + horizon) / 60 + 1 uint64 words (W <= 512; every
+ * start's own row width is at most that), then G + K + 2 arrays of 2^n uint32
+ * (the G route tables, demand, capacity-masked routes, f_1..f_K), then 8 K + 16
+ * bytes for the chosen route sets.  vrpms_vrp_tdsp_run enqueues, per distinct
+ * start time, the A16 layers and the route kernel, then one launch per
+ * vehicle, on `stream`; it then SYNCHRONISES `stream` once to read the K
+ * chosen (route set, duration) pairs back, because the launches that rebuild
+ * each route's tour are shaped by them, and enqueues those.  d_tour[n + K] --
+ * route 0, a separator 0, ..., route K-1, 0, then the unserved customers in
+ * ascending order, each route A16's tie-ruled tour of its customers from its
+ * vehicle's start time -- and d_key[0], the A8 key of that tour, are written on
+ * `stream`.  VRPMS_EINVAL, with nothing launched, for a TSP instance, H other
+ * than 1 or 24, n or K out of range, a negative horizon, one that needs more
+ * than 512 words, or a workspace smaller than vrpms_vrp_tdsp_workspace's or not
+ * 8-byte aligned. */
+int vrpms_vrp_tdsp_workspace(int32_t n, int32_t K, int32_t G, int32_t max_start,
+                             int32_t horizon, uint64_t* bytes);
+int vrpms_vrp_tdsp_run(vrpms_ctx* ctx, int32_t n, int32_t horizon, void* d_work,
+                       uint64_t work_bytes, int16_t* d_tour, uint64_t* d_key, void* stream);
+
 /* Throughput mode (BASELINE.json config 5: many concurrent TSP requests):
  * R independent static TSP requests, each with its own int32 [N][N] matrix
  * (d_mats [R][N][N], node 0 = start node), ONE WORKGROUP PER REQUEST: 4 SA

@@ -97,6 +97,8 @@ SIGNATURES = {
     "vrpms_vrp_sp_run": (_c.c_int, [_vp, _i32, _vp, _u64, _vp, _vp, _vp]),
     "vrpms_tsp_tdp_workspace": (_c.c_int, [_i32, _i32, _i32, _c.POINTER(_u64)]),
     "vrpms_tsp_tdp_run": (_c.c_int, [_vp, _i32, _i32, _vp, _u64, _vp, _vp, _vp]),
+    "vrpms_vrp_tdsp_workspace": (_c.c_int, [_i32, _i32, _i32, _i32, _i32, _c.POINTER(_u64)]),
+    "vrpms_vrp_tdsp_run": (_c.c_int, [_vp, _i32, _i32, _vp, _u64, _vp, _vp, _vp]),
     "vrpms_probe_lds_gather": (_c.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "vrpms_probe_l2_gather": (_c.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "vrpms_tsp_batch_sa": (_c.c_int, [_vp, _vp, _i32, _i32, _c.POINTER(SaParams), _vp, _vp,

@@ -357,6 +357,34 @@ class Context:
         k = key.cpu().item()     # synchronises: the table may be released after it
         return k & (2**64 - 1), [int(c) for c in tour.cpu().tolist()]
 
+    def vrp_tdsp(self, n: int, horizon: int):
+        """Time-expanded partition DP (spec A17) over customers 1..n of the
+        loaded CVRP instance (H = 1 or 24), its vehicles, capacities, start
+        times and objective -> (key, tour of n + K tokens in vrp_sp's format,
+        every route the tie-ruled optimal tour of its customers from its
+        vehicle's start time): the optimum among solutions whose every route
+        takes at most `horizon` minutes, so the optimum outright when
+        `horizon` is at least its primary; a smaller `horizon` may leave more
+        customers unvisited, and the caller owns that promise.  The call
+        synchronises the stream once on the way (vrpms_vrp_tdsp_run).  The
+        workspace (vrpms_vrp_tdsp_workspace) is a torch tensor freed before
+        the return."""
+        torch = _torch()
+        nbytes = ctypes.c_uint64()
+        starts = self.start_times or [0]
+        check(self.lib.vrpms_vrp_tdsp_workspace(int(n), int(self.K), len(set(starts)),
+                                                int(max(starts)), int(horizon),
+                                                ctypes.byref(nbytes)))
+        work = torch.empty(nbytes.value, dtype=torch.uint8, device=self.dev)
+        tour = torch.empty(int(n) + self.K, dtype=torch.int16, device=self.dev)
+        key = torch.empty(1, dtype=torch.int64, device=self.dev)
+        check(self.lib.vrpms_vrp_tdsp_run(self._ctx, int(n), int(horizon), work.data_ptr(),
+                                          nbytes.value, tour.data_ptr(), key.data_ptr(),
+                                          self.stream()))
+        k = key.cpu().item()     # synchronises: the workspace may be released after it
+        del work
+        return k & (2**64 - 1), [int(c) for c in tour.cpu().tolist()]
+
     def tsp_batch_sa(self, mats, steps: int, inv_t0: float, inv_alpha: float, seed: int):
         """One workgroup per request: mats int32 [R][N][N] on the device ->
         (best tours int16 [R][N-1], best keys int64 [R])."""

@@ -367,6 +367,8 @@ int vrpms_set_instance(vrpms_ctx* ctx, int32_t problem, const int32_t* d_dur, in
   std::vector<int32_t> caps(K);
   VRPMS_HIP(hipMemcpyAsync(st, ctx->d_stats, sizeof(st), hipMemcpyDeviceToHost, s));
   VRPMS_HIP(hipMemcpyAsync(caps.data(), in.cap, (size_t)K * 4, hipMemcpyDeviceToHost, s));
+  in.h_start.resize(K);
+  VRPMS_HIP(hipMemcpyAsync(in.h_start.data(), in.start, (size_t)K * 4, hipMemcpyDeviceToHost, s));
   VRPMS_HIP(hipStreamSynchronize(s));
   if (st[0] < 0) return fail(VRPMS_EINVAL, "vrpms_set_instance: negative duration in matrix");
   if (problem == VRPMS_CVRP) {

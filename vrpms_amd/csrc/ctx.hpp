@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <vector>
 
 #include "../../include/vrpms.h"
 
@@ -31,6 +32,7 @@ struct Instance {
   int32_t* dem = nullptr;      // [N]
   int32_t* cap = nullptr;      // [K]
   int32_t* start = nullptr;    // [K]
+  std::vector<int32_t> h_start;  // host copy of start (vrp_tdsp.hip: one table per distinct value)
   int pack_w = 0;              // field width of ret/out in the packed hi word
   // "prefix-ret" layout for a uniform fleet (eval_cvrp_packed MODE 1):
   // lo = dem(b) << S + dur(a,b) + ret(b) - ret(a) (mod 2^32), hi = out(b) + ret(b) | dem(b) << S

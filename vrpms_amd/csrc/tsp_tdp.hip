@@ -40,6 +40,13 @@
 //                         the walk back through the table; writes the tour and
 //                         the A8 key (UINT64_MAX and a zero tour if no tour
 //                         fits the horizon).
+//
+// tsp_tdp_fill / tsp_tdp_walk (tsp_tdp.hpp) enqueue these for an explicit
+// start time and a node map (local customer bit c -> compact node), so
+// vrp_tdsp.hip builds one table per vehicle start time and re-walks single
+// routes over their own customers; vrpms_tsp_tdp_run passes the instance's
+// start and the identity map.  The map is applied where the matrix is staged
+// into LDS and in the init and walk kernels' direct reads.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -48,11 +55,10 @@
 #include "common.hpp"
 #include "ctx.hpp"
 #include "tsp_dp.hpp"
+#include "tsp_tdp.hpp"
 
 namespace vrpms {
 
-constexpr int kTdpMaxN = 20;
-constexpr int kTdpMaxWords = 512;      // hours per row: 4 wavefronts' accumulators + the matrix < 64 KiB of LDS
 constexpr int kTdpMaxWaves = 16;       // wavefronts per workgroup of the layer kernel: 16, 8 or 4 (tdp_lds_bytes)
 constexpr size_t kTdpLdsLimit = 64 * 1024;
 constexpr uint64_t kTdpMask60 = (1ull << 60) - 1;
@@ -69,6 +75,8 @@ struct TdpArgs {
   uint32_t chunk;      // consecutive ranks per wavefront
   uint64_t last_mask;  // bits of word W-1 at or below start + horizon
   uint64_t* R;         // [2^n][n][W]
+  uint8_t node[kTdpMaxN];  // local customer c (bit c) -> compact node
+  int mapped;          // 0: node[c] = c + 1 for every c (the staging loop then needs no lookups)
 };
 
 VRPMS_DEV int tdp_slice(const TdpArgs& a, int w) { return a.H == 1 ? 0 : (a.h0m + w) % 24; }
@@ -77,7 +85,7 @@ __global__ __launch_bounds__(256) void tsp_tdp_init_kernel(TdpArgs a) {
   const int n = a.n, W = a.W;
   for (int e = threadIdx.x; e < n * W; e += 256) {
     const int c = e / W, w = e - c * W;
-    const int64_t rel = (int64_t)a.off + a.D[(int64_t)a.h0m * a.N * a.N + c + 1];
+    const int64_t rel = (int64_t)a.off + a.D[(int64_t)a.h0m * a.N * a.N + a.node[c]];
     uint64_t v = 0;
     if (rel <= (int64_t)a.off + a.horizon && rel / 60 == w) v = 1ull << (rel % 60);
     a.R[(((uint64_t)1 << c) * n + c) * W + w] = v;
@@ -96,9 +104,17 @@ __global__ __launch_bounds__(64 * kTdpMaxWaves) void tsp_tdp_layer_kernel(TdpArg
   const int waves = blockDim.x >> 6;
   int32_t* Dl = reinterpret_cast<int32_t*>(tdp_smem + waves * W);       // [H][n+1][n+1]
   uint8_t* members = reinterpret_cast<uint8_t*>(Dl + a.H * NN * NN);    // [waves][32]
-  for (int e = threadIdx.x; e < a.H * NN * NN; e += blockDim.x) {
-    const int h = e / (NN * NN), r = e - h * NN * NN, i = r / NN, j = r - i * NN;
-    Dl[e] = a.D[((int64_t)h * a.N + i) * a.N + j];
+  if (!a.mapped) {  // wave-uniform: the identity map costs the staging loop nothing
+    for (int e = threadIdx.x; e < a.H * NN * NN; e += blockDim.x) {
+      const int h = e / (NN * NN), r = e - h * NN * NN, i = r / NN, j = r - i * NN;
+      Dl[e] = a.D[((int64_t)h * a.N + i) * a.N + j];
+    }
+  } else {
+    for (int e = threadIdx.x; e < a.H * NN * NN; e += blockDim.x) {
+      const int h = e / (NN * NN), r = e - h * NN * NN, i = r / NN, j = r - i * NN;
+      const int gi = i ? a.node[i - 1] : 0, gj = j ? a.node[j - 1] : 0;
+      Dl[e] = a.D[((int64_t)h * a.N + gi) * a.N + gj];
+    }
   }
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -189,7 +205,7 @@ __global__ __launch_bounds__(64) void tsp_tdp_walk_kernel(TdpArgs a, int16_t* to
     const uint64_t x = a.R[((uint64_t)S * n + c) * W + w];
     if (!x) continue;
     const int brel = 60 * w + __builtin_ctzll(x);
-    const int64_t val = (int64_t)brel - a.off + a.D[tdp_slice(a, w) * NN2 + (int64_t)(c + 1) * a.N];
+    const int64_t val = (int64_t)brel - a.off + a.D[tdp_slice(a, w) * NN2 + (int64_t)a.node[c] * a.N];
     if (val > a.horizon) continue;
     const uint64_t cand = ((uint64_t)val << 24) | ((uint64_t)c << 16) | (uint64_t)brel;
     best = cand < best ? cand : best;
@@ -202,7 +218,7 @@ __global__ __launch_bounds__(64) void tsp_tdp_walk_kernel(TdpArgs a, int16_t* to
   }
   int c = (int)(best >> 16 & 0xff), brel = (int)(best & 0xffff);
   for (int pos = n - 1; pos >= 1; --pos) {
-    if (lane == 0) tour[pos] = (int16_t)(c + 1);
+    if (lane == 0) tour[pos] = (int16_t)a.node[c];
     S ^= 1u << c;
     const int nw = brel / 60 + 1;   // source words that can reach the clock
     uint64_t step = ~0ull;
@@ -210,7 +226,7 @@ __global__ __launch_bounds__(64) void tsp_tdp_walk_kernel(TdpArgs a, int16_t* to
       const int i = e / nw, w = e - i * nw;
       if (!(S >> i & 1u)) continue;
       const uint64_t x = a.R[((uint64_t)S * n + i) * W + w];
-      const int64_t m = (int64_t)brel - 60 * w - a.D[tdp_slice(a, w) * NN2 + (int64_t)(i + 1) * a.N + c + 1];
+      const int64_t m = (int64_t)brel - 60 * w - a.D[tdp_slice(a, w) * NN2 + (int64_t)a.node[i] * a.N + a.node[c]];
       if (m < 0 || m >= 60 || !(x >> m & 1ull)) continue;
       const uint64_t cand = ((uint64_t)i << 16) | (uint64_t)(60 * w + m);
       step = cand < step ? cand : step;
@@ -225,16 +241,62 @@ __global__ __launch_bounds__(64) void tsp_tdp_walk_kernel(TdpArgs a, int16_t* to
     brel = (int)(step & 0xffff);
   }
   if (lane == 0) {
-    tour[0] = (int16_t)(c + 1);
+    tour[0] = (int16_t)a.node[c];
     *key = pack_key(0, (uint32_t)(best >> 24), 0);
   }
 }
 
-// words per row, or 0 when start + horizon leaves int32 or the row the kernel's limit
-static int tdp_words(int64_t start, int64_t horizon) {
-  if (start + horizon >= 2147483648LL) return 0;
-  const int64_t W = (start % 60 + horizon) / 60 + 1;
-  return W > kTdpMaxWords ? 0 : (int)W;
+static TdpArgs tdp_args(const Instance& in, const TdpProblem& p, uint64_t* R) {
+  TdpArgs a{};
+  a.D = in.mat32;
+  a.N = in.N;
+  a.H = in.H;
+  a.n = p.n;
+  a.W = p.W;
+  a.h0m = (p.start / 60) % in.H;
+  a.off = p.start % 60;
+  a.horizon = p.horizon;
+  a.last_mask = (2ull << ((a.off + (int64_t)p.horizon) % 60)) - 1ull;
+  a.R = R;
+  for (int c = 0; c < p.n; ++c) {
+    a.node[c] = p.node[c];
+    a.mapped |= p.node[c] != c + 1;
+  }
+  return a;
+}
+
+int tsp_tdp_fill(vrpms_ctx* ctx, const TdpProblem& p, uint64_t* R, hipStream_t s) {
+  const Instance& in = ctx->inst;
+  const int n = p.n, W = p.W;
+  TdpArgs a = tdp_args(in, p, R);
+  tsp_tdp_init_kernel<<<1, 256, 0, s>>>(a);
+  VRPMS_HIP(hipGetLastError());
+  // the largest workgroup whose LDS stays within 64 KiB (the matrix is staged
+  // once per workgroup, and two or three workgroups fit a CU); two rounds of a
+  // full chip of wavefronts per layer
+  int wg_waves = kTdpMaxWaves;
+  while (wg_waves > 4 && tdp_lds_bytes(wg_waves, W, in.H, n) > kTdpLdsLimit) wg_waves /= 2;
+  const size_t lds = tdp_lds_bytes(wg_waves, W, in.H, n);
+  const uint64_t waves_target = (uint64_t)ctx->num_cus * 32 * 2;
+  for (int k = 2; k <= n; ++k) {
+    a.k = k;
+    a.count = kDpBinomHost.v[n][k];
+    a.chunk = (uint32_t)std::max<uint64_t>(1, (a.count + waves_target - 1) / waves_target);
+    const uint64_t waves = ((uint64_t)a.count + a.chunk - 1) / a.chunk;
+    const unsigned blocks = (unsigned)((waves + wg_waves - 1) / wg_waves);
+    tsp_tdp_layer_kernel<<<blocks, 64 * wg_waves, lds, s>>>(a);
+    VRPMS_HIP(hipGetLastError());
+  }
+  return VRPMS_OK;
+}
+
+int tsp_tdp_walk(vrpms_ctx* ctx, const TdpProblem& p, uint64_t* R, int16_t* tour, uint64_t* key,
+                 hipStream_t s) {
+  TdpArgs a = tdp_args(ctx->inst, p, R);
+  a.k = p.n;
+  tsp_tdp_walk_kernel<<<1, 64, 0, s>>>(a, tour, key);
+  VRPMS_HIP(hipGetLastError());
+  return VRPMS_OK;
 }
 
 }  // namespace vrpms
@@ -289,37 +351,8 @@ extern "C" int vrpms_tsp_tdp_run(vrpms_ctx* ctx, int32_t n, int32_t horizon, voi
   VRPMS_HIP(hipSetDevice(ctx->device));
   hipStream_t s = (hipStream_t)stream;
 
-  TdpArgs a{};
-  a.D = in.mat32;
-  a.N = in.N;
-  a.H = in.H;
-  a.n = n;
-  a.W = W;
-  a.h0m = (start / 60) % in.H;
-  a.off = start % 60;
-  a.horizon = horizon;
-  a.last_mask = (2ull << ((a.off + (int64_t)horizon) % 60)) - 1ull;
-  a.R = static_cast<uint64_t*>(d_work);
-  tsp_tdp_init_kernel<<<1, 256, 0, s>>>(a);
-  VRPMS_HIP(hipGetLastError());
-  // the largest workgroup whose LDS stays within 64 KiB (the matrix is staged
-  // once per workgroup, and two or three workgroups fit a CU); two rounds of a
-  // full chip of wavefronts per layer
-  int wg_waves = kTdpMaxWaves;
-  while (wg_waves > 4 && tdp_lds_bytes(wg_waves, W, in.H, n) > kTdpLdsLimit) wg_waves /= 2;
-  const size_t lds = tdp_lds_bytes(wg_waves, W, in.H, n);
-  const uint64_t waves_target = (uint64_t)ctx->num_cus * 32 * 2;
-  for (int k = 2; k <= n; ++k) {
-    a.k = k;
-    a.count = kDpBinomHost.v[n][k];
-    a.chunk = (uint32_t)std::max<uint64_t>(1, (a.count + waves_target - 1) / waves_target);
-    const uint64_t waves = ((uint64_t)a.count + a.chunk - 1) / a.chunk;
-    const unsigned blocks = (unsigned)((waves + wg_waves - 1) / wg_waves);
-    tsp_tdp_layer_kernel<<<blocks, 64 * wg_waves, lds, s>>>(a);
-    VRPMS_HIP(hipGetLastError());
-  }
-  a.k = n;
-  tsp_tdp_walk_kernel<<<1, 64, 0, s>>>(a, d_tour, d_key);
-  VRPMS_HIP(hipGetLastError());
-  return VRPMS_OK;
+  const TdpProblem p = tdp_identity(n, start, horizon, W);
+  const int rc = tsp_tdp_fill(ctx, p, static_cast<uint64_t*>(d_work), s);
+  if (rc != VRPMS_OK) return rc;
+  return tsp_tdp_walk(ctx, p, static_cast<uint64_t*>(d_work), d_tour, d_key, s);
 }

@@ -39,6 +39,10 @@
 //                        f_{k+1}[S] (1024 ranks at a time, in increasing
 //                        order), then one wavefront walks every route as
 //                        tsp_dp_walk_kernel does and writes tour and key.
+//
+// vrp_sp_cap / vrp_sp_layer_items / vrp_sp_layer (vrp_sp.hpp) enqueue the
+// capacity filter and one partition layer; vrp_tdsp.hip runs the same two
+// kernels on route tables that come from the time-expanded DP.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -47,24 +51,15 @@
 #include "common.hpp"
 #include "ctx.hpp"
 #include "tsp_dp.hpp"
+#include "vrp_sp.hpp"
 
 namespace vrpms {
 
-constexpr int kSpMaxN = 20;
-constexpr int kSpMaxK = 64;
 constexpr int kSpItemLog = 14;  // submasks per work item: 2^14 = 256 steps per lane
 constexpr int kSpMaxSets = 64;  // small sets per work item at most
 constexpr int kSpBatch = 8;     // steps whose gathers a lane keeps in flight together
-constexpr uint32_t kSpInf = 0xffffffffu;
 
 __constant__ DpBinom kSpBinom = dp_make_binom();
-
-// the bits of r deposited, lowest first, into the set bits of S
-VRPMS_DEV uint32_t sp_deposit(uint32_t r, uint32_t S) {
-  uint32_t T = 0;
-  for (uint32_t m = S; m; m &= m - 1u, r >>= 1) T |= (r & 1u) ? (m & (0u - m)) : 0u;
-  return T;
-}
 
 template <int NPAD>
 __global__ __launch_bounds__(256) void vrp_sp_route_kernel(const int32_t* D, int n, const int32_t* demand,
@@ -99,18 +94,6 @@ __global__ __launch_bounds__(256) void vrp_sp_cap_kernel(const uint32_t* __restr
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i < count) out[i] = dem[i] <= (uint32_t)cap[k] ? route[i] : kSpInf;
 }
-
-struct SpLayerArgs {
-  const uint32_t* routecap;  // [2^n], vehicle k's
-  const uint32_t* fk;        // [2^n] f_k
-  uint32_t* fn;              // [2^n] f_{k+1}, preset to unreachable
-  const uint32_t* dem;       // [2^n]
-  const int32_t* cap;        // [K]
-  int n, k;
-  // first[j] = first work item of cardinality n - j (heaviest sets first);
-  // first[n + 1] = the number of items
-  uint32_t first[kSpMaxN + 2];
-};
 
 template <int OBJ>
 __global__ __launch_bounds__(256) void vrp_sp_layer_kernel(SpLayerArgs a) {
@@ -312,6 +295,40 @@ __global__ __launch_bounds__(1024) void vrp_sp_back_kernel(SpBackArgs a) {
   if (lane == 0) *a.key = cvrp_key((uint32_t)(n - __popc(served)), dsum, dmax, a.objective);
 }
 
+int vrp_sp_cap(const uint32_t* route, const uint32_t* dem, const int32_t* cap, int k, uint32_t count,
+               uint32_t* out, hipStream_t s) {
+  vrp_sp_cap_kernel<<<(count + 255u) / 256u, 256, 0, s>>>(route, dem, cap, k, count, out);
+  VRPMS_HIP(hipGetLastError());
+  return VRPMS_OK;
+}
+
+void vrp_sp_layer_items(int n, SpLayerArgs& a) {
+  a.n = n;
+  uint32_t items = 0;
+  for (int j = 0; j <= n; ++j) {
+    const int c = n - j;
+    const uint32_t sets = kDpBinomHost.v[n][c];
+    a.first[j] = items;
+    if (c > kSpItemLog) {
+      items += sets << (c - kSpItemLog);
+    } else {
+      const uint32_t per_item = std::min<uint32_t>(1u << (kSpItemLog - c), kSpMaxSets);
+      items += (sets + per_item - 1) / per_item;
+    }
+  }
+  a.first[n + 1] = items;
+}
+
+int vrp_sp_layer(const SpLayerArgs& a, int objective, hipStream_t s) {
+  const unsigned blocks = (a.first[a.n + 1] + 3) / 4;
+  if (objective == VRPMS_OBJ_MAX)
+    vrp_sp_layer_kernel<1><<<blocks, 256, 0, s>>>(a);
+  else
+    vrp_sp_layer_kernel<0><<<blocks, 256, 0, s>>>(a);
+  VRPMS_HIP(hipGetLastError());
+  return VRPMS_OK;
+}
+
 static uint64_t sp_words(int n, int K) { return (uint64_t)dp_npad(n) + 3u + (uint64_t)K; }
 
 }  // namespace vrpms
@@ -373,29 +390,14 @@ extern "C" int vrpms_vrp_sp_run(vrpms_ctx* ctx, int32_t n, void* d_work, uint64_
       vrp_sp_route_kernel<32><<<blocks, 256, 0, s>>>(in.mat32, n, in.dem, g, route, dem);
     VRPMS_HIP(hipGetLastError());
   }
-  const unsigned cap_blocks = (unsigned)((full + 255) / 256);
-  vrp_sp_cap_kernel<<<cap_blocks, 256, 0, s>>>(route, dem, in.cap, 0, (uint32_t)full, f);
-  VRPMS_HIP(hipGetLastError());
+  int rc2 = vrp_sp_cap(route, dem, in.cap, 0, (uint32_t)full, f, s);
+  if (rc2 != VRPMS_OK) return rc2;
   if (K > 1) {
     VRPMS_HIP(hipMemsetAsync(f + full, 0xff, (size_t)(K - 1) * full * 4, s));
     SpLayerArgs a{};
     a.dem = dem;
     a.cap = in.cap;
-    a.n = n;
-    uint32_t items = 0;
-    for (int j = 0; j <= n; ++j) {
-      const int c = n - j;
-      const uint32_t sets = kDpBinomHost.v[n][c];
-      a.first[j] = items;
-      if (c > kSpItemLog) {
-        items += sets << (c - kSpItemLog);
-      } else {
-        const uint32_t per_item = std::min<uint32_t>(1u << (kSpItemLog - c), kSpMaxSets);
-        items += (sets + per_item - 1) / per_item;
-      }
-    }
-    a.first[n + 1] = items;
-    const unsigned blocks = (items + 3) / 4;
+    vrp_sp_layer_items(n, a);
     for (int k = 1; k < K; ++k) {
       a.k = k;
       a.fk = f + (size_t)(k - 1) * full;
@@ -403,15 +405,12 @@ extern "C" int vrpms_vrp_sp_run(vrpms_ctx* ctx, int32_t n, void* d_work, uint64_
       if (in.uniform_cap) {
         a.routecap = f;  // equal capacities: routecap is f_1 for every vehicle
       } else {
-        vrp_sp_cap_kernel<<<cap_blocks, 256, 0, s>>>(route, dem, in.cap, k, (uint32_t)full, routecap);
-        VRPMS_HIP(hipGetLastError());
+        rc2 = vrp_sp_cap(route, dem, in.cap, k, (uint32_t)full, routecap, s);
+        if (rc2 != VRPMS_OK) return rc2;
         a.routecap = routecap;
       }
-      if (in.objective == VRPMS_OBJ_MAX)
-        vrp_sp_layer_kernel<1><<<blocks, 256, 0, s>>>(a);
-      else
-        vrp_sp_layer_kernel<0><<<blocks, 256, 0, s>>>(a);
-      VRPMS_HIP(hipGetLastError());
+      rc2 = vrp_sp_layer(a, in.objective, s);
+      if (rc2 != VRPMS_OK) return rc2;
     }
   }
   const SpBackArgs b{in.mat32, in.N, n, K, in.objective == VRPMS_OBJ_MAX ? 1 : 0, npad, g, route, dem, f,

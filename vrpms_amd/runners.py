@@ -298,6 +298,88 @@ def time_expanded(ctx: Context, n: int, durations, start_time: int, upper_bound:
     return key, tour
 
 
+def tdsp_safe_bound(durations, demand, capacities, n: int) -> int:
+    """A17's always-valid bound on the duration of one route: a route serves at
+    most m customers (the most whose demands, smallest first, fit the largest
+    capacity) and leaves each of its at most m + 1 nodes once, so it takes at
+    most the sum of the m + 1 largest maxout[v], maxout[v] the largest entry of
+    row v over all slices and compact nodes 0..n."""
+    D = np.asarray(durations, dtype=np.int64)
+    if D.ndim == 2:
+        D = D[None]
+    room, m = int(max(capacities)), 0
+    for d in sorted(int(x) for x in np.asarray(demand)[1:n + 1]):
+        if d > room:
+            break
+        room -= d
+        m += 1
+    maxout = sorted((int(x) for x in D[:, :n + 1, :n + 1].max(axis=(0, 2))), reverse=True)
+    return sum(maxout[:m + 1])
+
+
+def tdsp_constructive(durations, demand, capacities, start_times, n: int):
+    """A host-side constructive solution: the nearest-neighbour giant tour
+    (static slice of the earliest start's hour, ties to the lowest index) under
+    the A6 greedy split (vehicles in order, a customer goes to the current
+    vehicle while it fits, else to the next; what fits no remaining vehicle is
+    unvisited), each route priced under the A3 clock from its vehicle's start
+    -> (unvisited count, [route duration per vehicle])."""
+    D = np.asarray(durations, dtype=np.int64)
+    if D.ndim == 2:
+        D = D[None]
+    H = D.shape[0]
+    row0 = D[(int(min(start_times)) // 60) % H]
+    cur, left, tour = 0, list(range(1, n + 1)), []
+    while left:
+        nxt = min(left, key=lambda c: (int(row0[cur, c]), c))
+        tour.append(nxt)
+        left.remove(nxt)
+        cur = nxt
+    K = len(capacities)
+    routes = [[] for _ in range(K)]
+    k, load, unvisited = 0, 0, 0
+    for c in tour:
+        d = int(demand[c])
+        while k < K and load + d > int(capacities[k]):
+            k, load = k + 1, 0
+        if k == K:
+            unvisited += 1
+            continue
+        routes[k].append(c)
+        load += d
+    durs = []
+    for k, r in enumerate(routes):
+        t, cur = int(start_times[k]), 0
+        for c in r + [0] if r else []:
+            t += int(D[(t // 60) % H, cur, c])
+            cur = c
+        durs.append(t - int(start_times[k]))
+    return unvisited, durs
+
+
+def tdsp_default_bound(durations, demand, capacities, start_times, n: int, objective_max: bool) -> int:
+    """The upper bound "tdsp" runs with when none is given: tdsp_safe_bound,
+    lowered to the primary of tdsp_constructive's solution when that leaves
+    nobody unvisited (zero unvisited cannot be beaten, so every route of an
+    optimum is at most its primary, which is at most that solution's)."""
+    bound = tdsp_safe_bound(durations, demand, capacities, n)
+    unvisited, durs = tdsp_constructive(durations, demand, capacities, start_times, n)
+    if unvisited == 0:
+        bound = min(bound, max(durs) if objective_max else sum(durs))
+    return bound
+
+
+def td_set_partition(ctx: Context, n: int, upper_bound: int):
+    """Exact optimum of (unvisited, primary) over all separator tours of the
+    loaded CVRP instance (H = 1 or 24, n <= 20, K <= 64, per-vehicle
+    capacities and start times; spec A17) -> (key, tour of n + K tokens).
+    `upper_bound` (minutes) bounds every single route: key and tour do not
+    depend on it as long as it is at least the optimum's primary
+    (tdsp_default_bound always is); below that the answer is the optimum among
+    solutions whose every route fits, which may leave customers unvisited."""
+    return ctx.vrp_tdsp(n, int(upper_bound))
+
+
 def unrank(rank: int, n: int):
     """Lexicographic rank -> permutation of 1..n (host-side index arithmetic)."""
     avail = list(range(1, n + 1))

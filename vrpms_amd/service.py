@@ -36,9 +36,10 @@ TITLES = {"bf": "Brute Force", "ga": "Genetic Algorithm", "sa": "Simulated Annea
 # algorithms of the inline route POST /solve/<problem>/<algo>: the endpoints'
 # and the exact solvers, "dp" (Held-Karp) for the TSP and "sp" (set
 # partitioning) for the VRP, and "tdp" (time-expanded subset DP, hour-indexed
-# matrices) for the TSP (they have no /api endpoint: the eight endpoints are
+# matrices) for the TSP and "tdsp" (its fleet counterpart, per-vehicle start
+# times) for the VRP (they have no /api endpoint: the eight endpoints are
 # the reference's wire contract)
-INLINE_ALGORITHMS = {"tsp": tuple(TITLES) + ("dp", "tdp"), "vrp": tuple(TITLES) + ("sp",)}
+INLINE_ALGORITHMS = {"tsp": tuple(TITLES) + ("dp", "tdp"), "vrp": tuple(TITLES) + ("tdsp", "sp")}
 
 # (body key, params key) in the order the reference checks them
 # (api/parameters.py:4-15 and 34-44); 'auth' is the only optional one
@@ -373,7 +374,7 @@ class App:
         knobs = dict(knobs)
         mt = multi_threaded(knobs.get("multi_threaded"))
         islands = n > self.island_min_n if mt is None else mt
-        if len(self.devices) > 1 and algorithm not in ("bf", "dp", "sp", "tdp") and islands:
+        if len(self.devices) > 1 and algorithm not in ("bf", "dp", "sp", "tdp", "tdsp") and islands:
             held = sorted(set(self.devices))   # each lock once, in one global order
             for d in held:
                 self.locks[d].acquire()
@@ -483,7 +484,10 @@ class App:
         customers on a static matrix) or "tdp" (exact time-expanded DP, up to
         solver.TDP_MAX_CUSTOMERS customers, hour-indexed matrices too; knob
         "upper_bound"), or, for vrp only, "sp" (exact set partitioning, up to solver.SP_MAX_CUSTOMERS customers and 64 vehicles
-        on a static matrix: INLINE_ALGORITHMS).  Body: the
+        on a static matrix) or "tdsp" (exact time-expanded partition DP, up
+        to solver.TDSP_MAX_CUSTOMERS customers and 64 vehicles, hour-indexed
+        matrices and per-vehicle start times; knob "upper_bound":
+        INLINE_ALGORITHMS).  Body: the
         solve_tsp / solve_vrp arguments in the request's camelCase names
         ("durations" is the DB's `matrix` payload); response as the
         handlers': {"success": true, "message": result} or a 400 error list."""

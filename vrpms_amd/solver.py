@@ -14,7 +14,9 @@ and adds the two calls the eight handler TODO slots make:
 `algorithm` is the endpoint name: 'bf', 'ga', 'sa' or 'aco', or 'dp' (TSP
 only: the exact Held-Karp subset DP, spec A14), or 'sp' (VRP only: the exact
 subset partition DP over all separator tours, spec A15), or 'tdp' (TSP only:
-the exact time-expanded subset DP for hour-indexed matrices, spec A16).  All search
+the exact time-expanded subset DP for hour-indexed matrices, spec A16), or
+'tdsp' (VRP only: the exact time-expanded partition DP for hour-indexed
+matrices with per-vehicle capacities and start times, spec A17).  All search
 and scoring runs in the gfx950 kernels (vrpms_amd.core); this module only
 builds the compact instance and maps results
 back to matrix indices.  Node ids in results are matrix row indices
@@ -33,7 +35,7 @@ import numpy as np
 from . import runners
 from .core import CVRP, OBJ_MAX, OBJ_SUM, TSP, Context
 
-ALGORITHMS = ("bf", "ga", "sa", "aco", "dp", "sp", "tdp")
+ALGORITHMS = ("bf", "ga", "sa", "aco", "dp", "sp", "tdp", "tdsp")
 # exhaustive search over n! giant tours: 13! = 6.2 G tours is ~0.1 s at the
 # measured ~64 G evals/s of bf_kernel on one MI355X (bench "search.bf") on a
 # static matrix; an hour-indexed one prices every edge at its departure
@@ -63,6 +65,19 @@ SP_MAX_VEHICLES = 64
 TDP_MAX_CUSTOMERS = 20
 TDP_MAX_WORKSPACE = 16 << 30
 TDP_MAX_WORDS = 512
+# time-expanded partition DP (A17, VRP, static or hour-indexed, per-vehicle
+# start times): G A16 tables, one per distinct start time, each followed by the
+# route kernel, then A15's K - 1 partition layers.  The kernel accepts 20
+# customers and 64 vehicles; TDSP_MAX_CUSTOMERS follows SP_MAX_CUSTOMERS' rule,
+# the largest n <= 20 whose median Context.vrp_tdsp time at K = 8 on
+# synth.td_cvrp_het(n, 8, seed=n) with the default upper bound is at most 1 s on
+# one MI355X and whose workspace is within TDSP_MAX_WORKSPACE: measured 0.194 s
+# at n = 19 with a 12.7 GiB workspace (tools/tdsp_rate.py --sizes 19, DESIGN.md
+# §4.3h); n = 20 needs 32.4 GiB there, so the workspace cap decides, not time.
+# TDSP_MAX_WORKSPACE is the same policy cap as TDP_MAX_WORKSPACE
+TDSP_MAX_CUSTOMERS = 19
+TDSP_MAX_VEHICLES = 64
+TDSP_MAX_WORKSPACE = 16 << 30
 # SA on tours of more than SA_WINDOW_MIN_N customers samples A11 windowed
 # moves (second position within SA_WINDOW of the first)
 SA_WINDOW, SA_WINDOW_MIN_N = 32, 150
@@ -281,6 +296,46 @@ def _check_tdp(ci: CompactInstance, upper_bound=None):
     return upper_bound
 
 
+def tdsp_workspace_bytes(n: int, K: int, G: int, max_start: int, upper_bound: int) -> int:
+    """vrpms_vrp_tdsp_workspace's formula: one A16 table of 2^n n rows of W
+    uint64 words, G + K + 2 arrays of 2^n uint32, and 8 K + 16 bytes."""
+    W = (min(59, int(max_start)) + int(upper_bound)) // 60 + 1
+    return (1 << n) * n * W * 8 + (4 << n) * (G + K + 2) + 8 * K + 16
+
+
+def _check_tdsp(ci: CompactInstance, objective: int, upper_bound=None):
+    """A17's domain and the workspace policy, checked on the host before any
+    device is touched -> the upper bound the run uses (None for n = 0)."""
+    if ci.problem != CVRP:
+        raise ValueError('tdsp solves the VRP only; use "tdp" for the exact time-dependent TSP')
+    if ci.n > TDSP_MAX_CUSTOMERS:
+        raise ValueError(f"tdsp (time-expanded partition DP) supports at most "
+                         f"{TDSP_MAX_CUSTOMERS} customers ({ci.n} given)")
+    K = len(ci.capacities)
+    if K > TDSP_MAX_VEHICLES:
+        raise ValueError(f"tdsp (time-expanded partition DP) supports at most "
+                         f"{TDSP_MAX_VEHICLES} vehicles ({K} given)")
+    if upper_bound is not None and int(upper_bound) < 0:
+        raise ValueError("tdsp: upper_bound must be non-negative (minutes)")
+    if ci.n == 0:
+        return None
+    if upper_bound is None:
+        upper_bound = runners.tdsp_default_bound(ci.durations, ci.demand, ci.capacities,
+                                                 ci.start_times, ci.n, objective == OBJ_MAX)
+    upper_bound = int(upper_bound)
+    starts = [int(s) for s in ci.start_times]
+    need = tdsp_workspace_bytes(ci.n, K, len(set(starts)), max(starts), upper_bound)
+    if need > TDSP_MAX_WORKSPACE:
+        raise ValueError(f"tdsp (time-expanded partition DP) would need a workspace of {need} "
+                         f"bytes for {ci.n} customers, {K} vehicles and an upper bound of "
+                         f"{upper_bound} minutes; the cap is {TDSP_MAX_WORKSPACE} bytes")
+    if (min(59, max(starts)) + upper_bound) // 60 + 1 > TDP_MAX_WORDS or \
+            max(starts) + upper_bound >= 2**31:
+        raise ValueError(f"tdsp (time-expanded partition DP) supports an upper bound of at most "
+                         f"{TDP_MAX_WORDS} hours from the start ({upper_bound} minutes given)")
+    return upper_bound
+
+
 def search_islands(ci: CompactInstance, algorithm: str, devices, seed: int = 0,
                    time_limit: float | None = None, objective: int = OBJ_SUM, **knobs):
     """The island model inside one process: one SA / GA / ACO
@@ -290,7 +345,7 @@ def search_islands(ci: CompactInstance, algorithm: str, devices, seed: int = 0,
     island."""
     import torch
     from . import islands
-    if ci.n <= 1 or algorithm in ("bf", "dp", "sp", "tdp"):
+    if ci.n <= 1 or algorithm in ("bf", "dp", "sp", "tdp", "tdsp"):
         raise ValueError("search_islands: SA / GA / ACO on two or more customers")
     rs, epochs = [], 1
     for d, dev in enumerate(devices):
@@ -308,8 +363,9 @@ def search_islands(ci: CompactInstance, algorithm: str, devices, seed: int = 0,
 
 
 def search(ctx: Context, ci: CompactInstance, algorithm: str, seed: int = 0,
-           time_limit: float | None = None, **knobs):
-    """Run one algorithm on the loaded instance -> (key, compact giant tour)."""
+           time_limit: float | None = None, objective: int = OBJ_SUM, **knobs):
+    """Run one algorithm on the loaded instance -> (key, compact giant tour).
+    `objective` is the loaded one ("tdsp"'s default upper bound depends on it)."""
     n = ci.n
     if algorithm == "dp":
         _check_dp(ci)
@@ -317,10 +373,14 @@ def search(ctx: Context, ci: CompactInstance, algorithm: str, seed: int = 0,
         _check_sp(ci)
     if algorithm == "tdp":
         bound = _check_tdp(ci, knobs.get("upper_bound"))
+    if algorithm == "tdsp":
+        bound = _check_tdsp(ci, objective, knobs.get("upper_bound"))
     if n == 0:
         return None, []
     if algorithm == "sp":
         return runners.set_partition(ctx, n)
+    if algorithm == "tdsp":
+        return runners.td_set_partition(ctx, n, bound)
     if n == 1:
         return None, [1]
     if algorithm == "dp":
@@ -366,15 +426,16 @@ def _remote():
 def _searched(ci, algorithm, seed, time_limit, device, devices, objective, knobs):
     """(context holding the instance, compact tour): one device, or the
     island model across `devices` (two or more) for SA / GA / ACO."""
-    if devices is not None and len(devices) > 1 and algorithm not in ("bf", "dp", "sp", "tdp") and ci.n > 1:
+    if devices is not None and len(devices) > 1 and algorithm not in ("bf", "dp", "sp", "tdp", "tdsp") and ci.n > 1:
         _, tour = search_islands(ci, algorithm, list(devices), seed=seed, time_limit=time_limit,
                                  objective=objective, **knobs)
         return context(devices[0]), tour
-    if algorithm in ("dp", "sp", "tdp") and devices:
+    if algorithm in ("dp", "sp", "tdp", "tdsp") and devices:
         device = devices[0]
     ctx = context(device)
     load(ctx, ci, objective)
-    _, tour = search(ctx, ci, algorithm, seed=seed, time_limit=time_limit, **knobs)
+    _, tour = search(ctx, ci, algorithm, seed=seed, time_limit=time_limit, objective=objective,
+                     **knobs)
     return ctx, tour
 
 
@@ -393,6 +454,9 @@ def solve_tsp(algorithm: str, durations, customers, start_node, start_time=0, *,
     if algorithm == "sp":
         raise ValueError('sp solves the VRP only (set partitioning over a fleet); use "dp" for '
                          'the exact TSP')
+    if algorithm == "tdsp":
+        raise ValueError('tdsp solves the VRP only (a fleet with per-vehicle start times); use '
+                         '"tdp" for the exact time-dependent TSP')
     if algorithm == "dp":
         ci = compact_tsp(durations, customers, start_node, start_time)
         _check_dp(ci)
@@ -421,19 +485,31 @@ def solve_vrp(algorithm: str, durations, locations, capacities, start_times,
     and SP_MAX_VEHICLES vehicles, static matrix) minimises (unvisited,
     primary) only; it runs on the first of `devices`, ignores `seed` and
     `time_limit`, and its domain is checked before any device or remote is
-    touched."""
+    touched.  "tdsp" (exact over all separator tours: at most
+    TDSP_MAX_CUSTOMERS customers and TDSP_MAX_VEHICLES vehicles, static or
+    hour-indexed matrix, per-vehicle capacities and start times) does the
+    same; its knob `upper_bound` (minutes) bounds every single route and
+    defaults to an always-valid bound (runners.tdsp_default_bound); the
+    workspace it implies must fit TDSP_MAX_WORKSPACE.  With an `upper_bound`
+    below the optimum's primary the answer is the optimum among solutions
+    whose every route fits it, which may leave customers unvisited: the
+    caller owns that promise."""
     if algorithm == "dp":
         raise ValueError("dp solves the TSP only (the greedy split of a giant tour does not "
                          "decompose over subsets); use bf, sa, ga or aco for the VRP")
     if algorithm == "tdp":
         raise ValueError("tdp solves the TSP only: per-vehicle start times (one table per "
                          "vehicle) and the capacity split are out of spec A16's scope; use bf, "
-                         "sa, ga or aco for a time-dependent VRP")
+                         "sa, ga or aco for a time-dependent VRP, or tdsp for the exact one")
     ci = None
     if algorithm == "sp":
         ci = compact_vrp(durations, locations, capacities, start_times, ignored_customers,
                          completed_customers)
         _check_sp(ci)
+    if algorithm == "tdsp":
+        ci = compact_vrp(durations, locations, capacities, start_times, ignored_customers,
+                         completed_customers)
+        _check_tdsp(ci, OBJ_MAX if objective == "max" else OBJ_SUM, knobs.get("upper_bound"))
     rem = _remote()
     if rem is not None:
         out = rem.solve_vrp(algorithm, durations, locations, capacities, start_times,
