@@ -167,6 +167,11 @@ int vrpms_eval_path(vrpms_ctx* ctx, int32_t perm_bytes, int64_t ld, const void* 
  *   workgroup of up to 16 ants of one colony, whenever N * N * 8 bytes fit;
  *   else from L2), 2 = force the L2 path; A/B -- the tours are the same. */
 #define VRPMS_OPT_ACO_CONSTRUCT 12
+/*   VRPMS_OPT_BATCH_DP_TEAM: threads per request of vrpms_tsp_batch_dp (0 =
+ *   auto: the measured n -> T table of DESIGN.md §4.3i; 16, 32, 64, 128 or
+ *   256 force, A/B -- the results do not depend on it; a forced T whose
+ *   256 / T tables do not fit the LDS makes the call fail). */
+#define VRPMS_OPT_BATCH_DP_TEAM 13
 int vrpms_set_option(vrpms_ctx* ctx, int32_t option, int32_t value);
 
 /* Decode ONE giant tour into the result dict of api/vrp/ga/index.py:49-53
@@ -381,6 +386,21 @@ int vrpms_vrp_tdsp_run(vrpms_ctx* ctx, int32_t n, int32_t horizon, void* d_work,
 int vrpms_tsp_batch_sa(vrpms_ctx* ctx, const int32_t* d_mats, int32_t R, int32_t N,
                        const vrpms_sa_params* p, uint16_t* d_best_tours, uint64_t* d_best_keys,
                        void* stream);
+
+/* Throughput mode of the exact TSP: R independent static
+ * TSP requests of one node count N, 2 <= N <= 13 (1..12 customers), each with
+ * its own int32 [N][N] matrix (d_mats [R][N][N], node 0 = start node,
+ * asymmetric and non-metric allowed; N * max(D) < 2^31 is the caller's
+ * promise, A9).  Each request's Held-Karp table lives in LDS: a team of T
+ * threads per request, 256 / T requests per workgroup, one launch for all R.
+ * Out: d_tours [R][N-1] (int16 customers) and d_keys [R], per request exactly
+ * what vrpms_tsp_dp_run writes for that matrix: the A8 key of the optimum and
+ * the lexicographically smallest optimal tour.  No instance and no workspace
+ * needed; asynchronous on `stream`.  R = 0 launches nothing.  VRPMS_EINVAL,
+ * with nothing launched, for a NULL ctx, R < 0, N outside 2..13, or a NULL
+ * buffer with R > 0. */
+int vrpms_tsp_batch_dp(vrpms_ctx* ctx, const int32_t* d_mats, int32_t R, int32_t N,
+                       uint16_t* d_tours, uint64_t* d_keys, void* stream);
 
 /* ------------------------------------------------------------------------
  * Populations and the island model.  A pool is a set of

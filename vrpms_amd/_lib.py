@@ -37,6 +37,7 @@ OPT_ROUTE_WG_PER_CU = 9
 OPT_ISLAND_TIMEOUT_S = 10
 OPT_SEG_WAVES = 11
 OPT_ACO_CONSTRUCT = 12
+OPT_BATCH_DP_TEAM = 13
 OBJ_SUM = 0
 OBJ_MAX = 1
 INJECT_WORST = 0
@@ -103,6 +104,7 @@ SIGNATURES = {
     "vrpms_probe_l2_gather": (_c.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "vrpms_tsp_batch_sa": (_c.c_int, [_vp, _vp, _i32, _i32, _c.POINTER(SaParams), _vp, _vp,
                                       _vp]),
+    "vrpms_tsp_batch_dp": (_c.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "vrpms_random_tours": (_c.c_int, [_vp, _i64, _i32, _i32, _i64, _i32, _u64, _c.c_uint32, _vp,
                                       _vp]),
     "vrpms_insert_separators": (_c.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),

@@ -398,6 +398,29 @@ class Context:
                                           tours.data_ptr(), keys.data_ptr(), self.stream()))
         return tours, keys
 
+    def tsp_batch_dp(self, mats):
+        """Exact optimum of every request in one launch (spec A18, at most 12
+        customers): mats int32 [R][N][N] on the device -> (tours int16
+        [R][N-1], keys int64 [R]), per request what tsp_dp returns for that
+        matrix.  N * max(mats) < 2^31 (A9) is the caller's promise: whoever
+        builds `mats` from host data checks it before uploading.
+        Asynchronous on the current stream."""
+        torch = _torch()
+        if mats.device != self.dev or mats.dim() != 3 or mats.shape[1] != mats.shape[2] or \
+                mats.dtype != torch.int32 or not mats.is_contiguous():
+            raise ValueError(f"mats must be a contiguous int32 [R][N][N] tensor on {self.dev}")
+        R, N, _ = mats.shape
+        tours = torch.empty((R, max(N - 1, 1)), dtype=torch.int16, device=self.dev)
+        keys = torch.empty(R, dtype=torch.int64, device=self.dev)
+        check(self.lib.vrpms_tsp_batch_dp(self._ctx, mats.data_ptr(), R, N, tours.data_ptr(),
+                                          keys.data_ptr(), self.stream()))
+        return tours, keys
+
+    def set_batch_dp_team(self, T: int):
+        """Threads per request of tsp_batch_dp: 0 = auto (the n -> T table),
+        16, 32, 64, 128 or 256 force (A/B; the results do not depend on it)."""
+        check(self.lib.vrpms_set_option(self._ctx, _lib.OPT_BATCH_DP_TEAM, int(T)))
+
     # -- populations and the island model (pool.hip) ---------------------------
     def random_tours(self, count: int, n: int, seed: int, stream_id: int = 0, ld: int | None = None,
                      dtype=None, n_sep: int = 0):

@@ -302,6 +302,13 @@ int vrpms_set_option(vrpms_ctx* ctx, int32_t option, int32_t value) {
     ctx->opt_aco_construct = value;
     return VRPMS_OK;
   }
+  if (option == VRPMS_OPT_BATCH_DP_TEAM) {
+    if (value != 0 && value != 16 && value != 32 && value != 64 && value != 128 && value != 256)
+      return fail(VRPMS_EINVAL,
+                  "vrpms_set_option: batch DP team must be 0 (auto), 16, 32, 64, 128 or 256");
+    ctx->opt_batch_dp_team = value;
+    return VRPMS_OK;
+  }
   if (option == VRPMS_OPT_ISLAND_TIMEOUT_S) {
     if (value <= 0)
       return fail(VRPMS_EINVAL, "vrpms_set_option: island timeout must be > 0 seconds");

@@ -72,6 +72,7 @@ struct vrpms_ctx {
   int opt_island_timeout_s = 120;  // VRPMS_OPT_ISLAND_TIMEOUT_S
   int opt_seg_waves = 0;           // VRPMS_OPT_SEG_WAVES (0 auto, 1..4 force)
   int opt_aco_construct = 0;       // VRPMS_OPT_ACO_CONSTRUCT (0 auto, 2 = the L2 path)
+  int opt_batch_dp_team = 0;       // VRPMS_OPT_BATCH_DP_TEAM (0 auto, 16..256 force)
 };
 
 namespace vrpms {

@@ -1,0 +1,216 @@
+// Batched exact TSP: Held-Karp for many small requests, each request's table
+// in LDS.
+//
+// The recurrence, the tie rule and the result are tsp_dp.hip's (A14), per
+// request: g[0][j] = D[j][0], g[S][j] = min over i in S of D[j][i] +
+// g[S \ {i}][i], and the forward walk from node 0 that takes the smallest
+// customer attaining the cost-to-go.  What differs is where the table lives
+// and who fills it:
+//
+//   - A request has at most kBatchDpMaxN customers, so its whole table fits
+//     one CU's LDS next to its matrix; nothing but the matrix is read from
+//     memory and nothing but the tour and the key is written to it.
+//   - The table is compact: g[S][j] exists only for j outside S, so customer
+//     j's states are indexed by c = S with bit j squeezed out, 2^(n-1) words
+//     per customer, n 2^(n-1) words in all.  The order is [j][c] (customer
+//     major): a layer's reads are g[S \ {i}][i] for one i at a time over many
+//     S, which are then the words base_i + c, consecutive subsets on
+//     different banks (§4.3i).
+//   - A team of T threads owns one request; a 256-thread workgroup holds
+//     256 / T requests of the same N, so all of its teams run the same number
+//     of layers and the workgroup-wide barrier between layers stays uniform.
+//     A team past the end of the batch still reaches every barrier; it reads
+//     and writes nothing (its layers are empty).
+//   - A thread takes a run of consecutive ranks of the layer's k-subsets:
+//     dp_unrank for the first mask, dp_next_mask from there (tsp_dp.hpp).
+//     For its subset S it loads h[i] = g[S \ {i}][i] once (0x80000000 for i
+//     outside S: above every real cost, and D + h cannot wrap since D < 2^31),
+//     then for every j outside S reads row j of the matrix from LDS and
+//     stores min over i of D[j][i] + h[i].
+//   - The walk runs in-kernel after the last layer, on the first 16 lanes of
+//     the team: lane i prices D[cur][i] + g[S \ {i}][i], a 16-lane shuffle
+//     minimum over (value, lane) picks the smallest customer attaining it.
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "common.hpp"
+#include "ctx.hpp"
+#include "tsp_dp.hpp"
+
+namespace vrpms {
+
+// Why 12: the compact table has n 2^(n-1) 32-bit words, 98,304 B at n = 12;
+// with the 13 x 16-word matrix image (832 B) and the binomial table (704 B)
+// that is 99,840 B, within ctx->max_lds (160 KiB per CU).  At n = 13 the table
+// alone is 13 * 4096 * 4 = 212,992 B, which does not fit.
+constexpr int kBatchDpMaxN = 12;
+constexpr int kBatchDpNodes = kBatchDpMaxN + 1;
+constexpr int kBatchDpRow = 16;     // words per matrix row in LDS: three 16-byte reads per row
+constexpr int kBatchDpBinomWords = (kBatchDpNodes * kBatchDpNodes + 3) & ~3;
+constexpr int kBatchDpMatWords = kBatchDpNodes * kBatchDpRow;
+constexpr uint32_t kBatchDpOut = 0x80000000u;   // h of a customer outside S
+
+// threads per request by n (index n): the fastest T of tools/batch_dp_rate.py
+// --teams 16,32,64,128,256 at each n (DESIGN.md §4.3i has the measurements)
+constexpr int kBatchDpTeam[kBatchDpMaxN + 1] = {16, 16, 16, 16, 16, 16, 16, 32, 32, 128, 256, 256,
+                                                256};
+
+__constant__ DpBinom kBatchDpBinom = dp_make_binom();
+
+struct BatchDpArgs {
+  const int32_t* mats;  // [R][N][N]
+  int R, N;
+  uint16_t* tours;      // [R][N-1]
+  uint64_t* keys;       // [R]
+};
+
+// words of one team: the matrix image, then the table padded to 16 bytes
+inline size_t batch_dp_team_words(int n) {
+  return kBatchDpMatWords + ((((size_t)n << (n - 1)) + 3) & ~(size_t)3);
+}
+
+inline size_t batch_dp_lds_bytes(int n, int T) {
+  return (kBatchDpBinomWords + (size_t)(256 / T) * batch_dp_team_words(n)) * 4;
+}
+
+// S with bit b squeezed out
+VRPMS_DEV uint32_t batch_dp_squeeze(uint32_t S, int b) {
+  return (S & ((1u << b) - 1u)) | ((S >> (b + 1)) << b);
+}
+
+template <int T>
+__global__ __launch_bounds__(256) void tsp_batch_dp_kernel(BatchDpArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t batch_dp_lds[];
+  const int N = a.N, n = N - 1;
+  const uint32_t half = 1u << (n - 1), full = (1u << n) - 1u;
+  const int team = threadIdx.x / T, tl = threadIdx.x % T;
+  const int64_t req = (int64_t)blockIdx.x * (256 / T) + team;
+  const bool active = req < a.R;
+  const uint32_t team_words = kBatchDpMatWords + ((((uint32_t)n << (n - 1)) + 3u) & ~3u);
+
+  uint32_t* B = batch_dp_lds;                                     // B[c][t] = C(c, t)
+  uint32_t* Dr = batch_dp_lds + kBatchDpBinomWords + team * team_words;  // Dr[node][i] = D[node][i + 1]
+  uint32_t* g = Dr + kBatchDpMatWords;                            // g[j][c], customer j + 1
+
+  for (int e = threadIdx.x; e < kBatchDpNodes * kBatchDpNodes; e += 256)
+    B[e] = kBatchDpBinom.v[e / kBatchDpNodes][e % kBatchDpNodes];
+  const int32_t* D = a.mats + (active ? req : 0) * N * N;
+  if (active) {
+    for (int e = tl; e < kBatchDpMatWords; e += T) {
+      const int node = e / kBatchDpRow, i = e % kBatchDpRow;
+      Dr[e] = (node <= n && i < n) ? (uint32_t)D[node * N + i + 1] : 0u;
+    }
+    for (int j = tl; j < n; j += T) g[j * half] = (uint32_t)D[(j + 1) * N];   // the empty set
+  }
+  __syncthreads();
+
+  for (int k = 1; k < n; ++k) {
+    // an inactive team has no subsets: it only keeps the barrier's count
+    const uint32_t count = active ? B[n * kBatchDpNodes + k] : 0u;
+    const uint32_t chunk = (count + T - 1) / T;
+    const uint32_t lo = tl * chunk;
+    const uint32_t hi = lo + chunk < count ? lo + chunk : count;
+    if (lo < hi) {
+      uint32_t S = dp_unrank(B, kBatchDpNodes, n, k, lo);
+      for (uint32_t r = lo; r < hi; ++r) {
+        uint32_t h[kBatchDpMaxN];
+#pragma unroll
+        for (int i = 0; i < kBatchDpMaxN; ++i)
+          h[i] = ((S >> i) & 1u) ? g[i * half + batch_dp_squeeze(S, i)] : kBatchDpOut;
+        for (uint32_t m = full & ~S; m; m &= m - 1u) {
+          const int j = __builtin_ctz(m);
+          const v4u* row = reinterpret_cast<const v4u*>(Dr + (j + 1) * kBatchDpRow);
+          const v4u r0 = row[0];
+          uint32_t best = min(min(r0.x + h[0], r0.y + h[1]), min(r0.z + h[2], r0.w + h[3]));
+          if (n > 4) {
+            const v4u r1 = row[1];
+            best = min(best, min(min(r1.x + h[4], r1.y + h[5]), min(r1.z + h[6], r1.w + h[7])));
+          }
+          if (n > 8) {
+            const v4u r2 = row[2];
+            best = min(best, min(min(r2.x + h[8], r2.y + h[9]), min(r2.z + h[10], r2.w + h[11])));
+          }
+          g[j * half + batch_dp_squeeze(S, j)] = best;
+        }
+        S = dp_next_mask(S);
+      }
+    }
+    __syncthreads();
+  }
+
+  // the forward walk, on one 16-lane group (T is a multiple of 16, so the
+  // group lies inside one wavefront and is active as a whole)
+  if (active && tl < 16) {
+    const int l = tl;
+    uint32_t S = full, total = 0;
+    int cur = 0;
+    for (int s = 0; s < n; ++s) {
+      uint32_t val = 0xffffffffu;
+      if (l < n && ((S >> l) & 1u))
+        val = Dr[cur * kBatchDpRow + l] + g[l * half + batch_dp_squeeze(S, l)];
+      uint64_t v = ((uint64_t)val << 8) | (uint32_t)l;
+#pragma unroll
+      for (int off = 8; off > 0; off >>= 1) {
+        const uint64_t o = __shfl_xor(v, off, 16);
+        v = o < v ? o : v;
+      }
+      const int i = (int)(v & 0xffu);
+      if (s == 0) total = (uint32_t)(v >> 8);
+      if (l == 0) a.tours[req * n + s] = (uint16_t)(i + 1);
+      cur = i + 1;
+      S &= ~(1u << i);
+    }
+    if (l == 0) a.keys[req] = pack_key(0, total, 0);
+  }
+}
+
+template <int T>
+static hipError_t batch_dp_launch(const BatchDpArgs& a, size_t lds, hipStream_t s) {
+  if (lds > 65536) {
+    const hipError_t e =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(tsp_batch_dp_kernel<T>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  const int per_wg = 256 / T;
+  const unsigned blocks = (unsigned)(((int64_t)a.R + per_wg - 1) / per_wg);
+  tsp_batch_dp_kernel<T><<<blocks, 256, lds, s>>>(a);
+  return hipGetLastError();
+}
+
+}  // namespace vrpms
+
+using namespace vrpms;
+
+extern "C" int vrpms_tsp_batch_dp(vrpms_ctx* ctx, const int32_t* d_mats, int32_t R, int32_t N,
+                                  uint16_t* d_tours, uint64_t* d_keys, void* stream) {
+  if (!ctx) return fail(VRPMS_EINVAL, "vrpms_tsp_batch_dp: ctx is NULL");
+  if (R < 0) return fail(VRPMS_EINVAL, "vrpms_tsp_batch_dp: R must not be negative");
+  if (N < 2 || N > kBatchDpNodes)
+    return fail(VRPMS_EINVAL, "vrpms_tsp_batch_dp: the LDS-resident table needs 2 <= N <= 13 (" +
+                                  std::to_string(N) + " given)");
+  if (R == 0) return VRPMS_OK;
+  if (!d_mats || !d_tours || !d_keys)
+    return fail(VRPMS_EINVAL, "vrpms_tsp_batch_dp: NULL matrix/tour/key buffer");
+  const int n = N - 1;
+  const int T = ctx->opt_batch_dp_team ? ctx->opt_batch_dp_team : kBatchDpTeam[n];
+  const size_t lds = batch_dp_lds_bytes(n, T);
+  if (lds > ctx->max_lds)
+    return fail(VRPMS_EINVAL, "vrpms_tsp_batch_dp: " + std::to_string(256 / T) + " tables of n = " +
+                                  std::to_string(n) + " need " + std::to_string(lds) +
+                                  " bytes of LDS (" + std::to_string(ctx->max_lds) + " available)");
+  VRPMS_HIP(hipSetDevice(ctx->device));
+  const BatchDpArgs a{d_mats, R, N, d_tours, d_keys};
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e = hipSuccess;
+  switch (T) {
+    case 16: e = batch_dp_launch<16>(a, lds, s); break;
+    case 32: e = batch_dp_launch<32>(a, lds, s); break;
+    case 64: e = batch_dp_launch<64>(a, lds, s); break;
+    case 128: e = batch_dp_launch<128>(a, lds, s); break;
+    default: e = batch_dp_launch<256>(a, lds, s); break;
+  }
+  VRPMS_HIP(e);
+  return VRPMS_OK;
+}

@@ -80,19 +80,7 @@ __global__ __launch_bounds__(256) void tsp_dp_layer_kernel(DpArgs a) {
   if (lo >= a.count) return;  // the whole lane group leaves together
   const uint32_t hi = lo + a.chunk < a.count ? (uint32_t)(lo + a.chunk) : a.count;
 
-  // rank -> mask: the k-subsets in increasing mask order are the combinations
-  // c_k > ... > c_1 with rank = sum C(c_t, t)
-  uint32_t S = 0;
-  {
-    uint32_t r = (uint32_t)lo;
-    int c = n - 1;
-    for (int t = k; t >= 1; --t) {
-      while (B[c * kDpNodes + t] > r) --c;
-      S |= 1u << c;
-      r -= B[c * kDpNodes + t];
-      --c;
-    }
-  }
+  uint32_t S = dp_unrank(B, kDpNodes, n, k, (uint32_t)lo);
 
   const bool mine = l < n;
   const uint32_t bit = 1u << l;

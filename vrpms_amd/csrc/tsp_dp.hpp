@@ -34,6 +34,22 @@ VRPMS_DEV uint32_t dp_next_mask(uint32_t m) {
   return (((r ^ m) >> 2) >> __builtin_ctz(c)) | r;
 }
 
+// rank -> mask: the k-subsets of n customers in increasing mask order are the
+// combinations c_k > ... > c_1 with rank = sum C(c_t, t) (combinatorial number
+// system).  B is a copy of the binomial table with rows of `ld` words,
+// B[c * ld + t] = C(c, t), that covers c < n and t <= k.
+VRPMS_DEV uint32_t dp_unrank(const uint32_t* B, int ld, int n, int k, uint32_t r) {
+  uint32_t S = 0;
+  int c = n - 1;
+  for (int t = k; t >= 1; --t) {
+    while (B[c * ld + t] > r) --c;
+    S |= 1u << c;
+    r -= B[c * ld + t];
+    --c;
+  }
+  return S;
+}
+
 // words per table row: one 64- or 128-byte line
 inline int dp_npad(int n) { return n > 16 ? 32 : 16; }
 

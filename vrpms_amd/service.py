@@ -329,6 +329,39 @@ class TspBatcher:
         return tours, durs
 
 
+class ExactTspBatcher(TspBatcher):
+    """Coalesces concurrent exact small-TSP requests -- ("tsp", "dp") on the
+    inline route and ("tsp", "bf") on the endpoint -- into one `tsp_batch_dp`
+    launch per node count (spec A18: each request's Held-Karp table in LDS).
+    The queue, the window, the grouping, the device round-robin and the error
+    fan-out are TspBatcher's; only the admission rule and the launch differ.
+    Unlike the SA batcher's, a batched answer does not depend on the batch: it
+    is the unbatched answer of the same request, key and tour."""
+
+    MIN_N, MAX_N = 2, 13         # 1..12 customers (solver.BATCH_DP_MAX_CUSTOMERS)
+
+    def __init__(self, app, window_s: float = 0.005, max_batch: int = 16384, launch=None):
+        super().__init__(app, window_s, steps=0, max_batch=max_batch, launch=launch)
+
+    @classmethod
+    def accepts(cls, ci) -> bool:
+        """Static matrices of 1..12 customers that pass the A9 int32 guard
+        vrpms_set_instance applies on the unbatched path (with the request's
+        start time, as there); anything else takes the unbatched path, so
+        both paths share one error contract."""
+        from . import solver
+        if ci.durations.shape[0] != 1 or not cls.MIN_N <= ci.N <= cls.MAX_N:
+            return False
+        return solver.batch_dp_guard(ci)
+
+    def _gpu_launch(self, N, cis, device=None):
+        """-> (tours, durations) on `device` (default: the app's first)."""
+        from . import solver
+        dev = self.devices[0] if device is None else device
+        with self.app.locks[dev]:
+            return solver.batch_dp_launch(solver.context(dev), cis)
+
+
 # ---------------------------------------------------------------------------
 # the endpoint logic
 # ---------------------------------------------------------------------------
@@ -349,7 +382,7 @@ class App:
     def __init__(self, store, device: int = 0, seed: int = 0, max_seconds: float | None = None,
                  solve=None, batch_tsp: bool = False, batch_window_s: float = 0.005,
                  batch_steps: int = 2000, batch_launch=None, devices=None,
-                 island_min_n: int = 150):
+                 island_min_n: int = 150, batch_exact: bool = False, batch_exact_launch=None):
         self.store = store
         self.devices = list(devices) if devices else [device]
         self.device = self.devices[0]
@@ -363,6 +396,9 @@ class App:
         self._solve = solve or self._gpu_solve
         self.batcher = TspBatcher(self, batch_window_s, batch_steps, launch=batch_launch) \
             if batch_tsp else None
+        # exact small-TSP requests share tsp_batch_dp launches (off by default)
+        self.exact_batcher = ExactTspBatcher(self, batch_window_s, launch=batch_exact_launch) \
+            if batch_exact else None
 
     def _scheduled(self, problem, algorithm, params, knobs, locations, durations):
         """Run the solve on a device: all of them (in order, as an island
@@ -398,14 +434,16 @@ class App:
         finally:
             self.locks[dev].release()
 
-    def _batched_tsp(self, params, durations):
-        """The compact instance when this request rides the batcher, else None."""
-        if self.batcher is None:
+    def _batched_tsp(self, params, durations, batcher=None):
+        """The compact instance when this request rides `batcher` (default:
+        the SA batcher), else None."""
+        batcher = self.batcher if batcher is None else batcher
+        if batcher is None:
             return None
         from . import solver
         ci = solver.compact_tsp(durations, params["customers"], params["start_node"],
                                 params["start_time"] or 0)
-        return ci if TspBatcher.accepts(ci) else None
+        return ci if batcher.accepts(ci) else None
 
     def _gpu_solve(self, problem, algorithm, params, knobs, locations, durations):
         """knobs may carry "seed", "time_limit" and "objective" (the /solve
@@ -451,10 +489,11 @@ class App:
         if errors:
             return 400, {"success": False, "errors": errors}
         try:
-            ci = self._batched_tsp(params, durations) if (problem, algorithm) == ("tsp", "sa") \
-                else None
+            batcher = {("tsp", "sa"): self.batcher,
+                       ("tsp", "bf"): self.exact_batcher}.get((problem, algorithm))
+            ci = self._batched_tsp(params, durations, batcher) if batcher is not None else None
             if ci is not None:
-                result = self.batcher.solve(ci)
+                result = batcher.solve(ci)
             else:
                 result = self._scheduled(problem, algorithm, params, knobs, locations, durations)
         except Exception as e:   # bad instance shape, GPU unavailable, ...
@@ -542,8 +581,13 @@ class App:
             return 400, {"success": False,
                          "errors": [{"what": "Invalid request", "reason": str(e)}]}
         try:
-            result = self._scheduled(problem, algorithm, params, knobs, locations,
-                                     vals["durations"])
+            ci = self._batched_tsp(params, vals["durations"], self.exact_batcher) \
+                if (problem, algorithm) == ("tsp", "dp") and self.exact_batcher is not None else None
+            if ci is not None:
+                result = self.exact_batcher.solve(ci)
+            else:
+                result = self._scheduled(problem, algorithm, params, knobs, locations,
+                                         vals["durations"])
         except Exception as e:
             return 400, {"success": False,
                          "errors": [{"what": "Solver error", "reason": str(e)}]}
@@ -649,6 +693,10 @@ def main(argv=None):
                     help="wall-time cap per solve (default: the algorithm's own budget)")
     ap.add_argument("--batch-tsp", action="store_true",
                     help="coalesce concurrent /api/tsp/sa requests into one launch")
+    ap.add_argument("--batch-exact", action="store_true",
+                    help="coalesce concurrent exact small-TSP requests (/solve/tsp/dp and "
+                         "/api/tsp/bf, static matrix, 1..12 customers) into tsp_batch_dp "
+                         "launches; the answers equal the unbatched ones")
     ap.add_argument("--batch-window-ms", type=float, default=5.0)
     ap.add_argument("--batch-steps", type=int, default=2000)
     ap.add_argument("--workers", type=int, default=0,
@@ -686,7 +734,7 @@ def main(argv=None):
         return
     app = App(store, device=args.device, seed=args.seed, max_seconds=args.max_seconds,
               batch_tsp=args.batch_tsp, batch_window_s=args.batch_window_ms * 1e-3,
-              batch_steps=args.batch_steps, devices=devices)
+              batch_steps=args.batch_steps, devices=devices, batch_exact=args.batch_exact)
     srv = serve(app, args.host, args.port)
     print(f"vrpms_amd service on http://{args.host}:{args.port}/api", flush=True)
     try:

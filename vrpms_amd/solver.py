@@ -16,7 +16,9 @@ only: the exact Held-Karp subset DP, spec A14), or 'sp' (VRP only: the exact
 subset partition DP over all separator tours, spec A15), or 'tdp' (TSP only:
 the exact time-expanded subset DP for hour-indexed matrices, spec A16), or
 'tdsp' (VRP only: the exact time-expanded partition DP for hour-indexed
-matrices with per-vehicle capacities and start times, spec A17).  All search
+matrices with per-vehicle capacities and start times, spec A17).
+solve_tsp_batch("dp", requests) answers many small exact TSP requests with
+shared launches (spec A18), each answer solve_tsp("dp")'s.  All search
 and scoring runs in the gfx950 kernels (vrpms_amd.core); this module only
 builds the compact instance and maps results
 back to matrix indices.  Node ids in results are matrix row indices
@@ -46,6 +48,10 @@ BF_MAX_CUSTOMERS_TD = 11
 # Held-Karp (A14, static TSP only): O(2^n n^2) steps over a table of 2^n rows,
 # 2 GiB at 24 customers (vrpms_tsp_dp_workspace)
 DP_MAX_CUSTOMERS = 24
+# batched Held-Karp (A18): one request's compact table, n 2^(n-1) words, has to
+# fit one CU's LDS next to its matrix: 98,304 B at n = 12, 212,992 B at n = 13
+# (vrpms_tsp_batch_dp); larger requests of a batch take the single-request path
+BATCH_DP_MAX_CUSTOMERS = 12
 # set partitioning (A15, static VRP only): 3^n steps per vehicle.  The kernel
 # accepts 20 customers; the cap here is a time budget, the largest n <= 20
 # whose median Context.vrp_sp time at K = 8 on one MI355X is at most 1 s:
@@ -473,6 +479,86 @@ def solve_tsp(algorithm: str, durations, customers, start_node, start_time=0, *,
     _, dur = _decode(ctx, tour)
     vehicle = [ci.nodes[0]] + [ci.nodes[c] for c in tour] + [ci.nodes[0]]
     return {"duration": int(dur[0]), "vehicle": vehicle}
+
+
+def batch_dp_guard(ci: CompactInstance) -> bool:
+    """The A9 int32 guard vrpms_set_instance applies to this request on the
+    single-request path (start + (N + K + 1) * max_duration < 2^31, K = 1);
+    it implies A18's N * max(D) < 2^31."""
+    mx = int(ci.durations.max()) if ci.durations.size else 0
+    return int(ci.start_times[0]) + (ci.N + 2) * mx < 2**31
+
+
+def batch_dp_launch(ctx: Context, cis):
+    """One upload and one tsp_batch_dp launch for compact instances of one
+    node count (each passed batch_dp_guard) -> (tours, durations), one row per
+    instance.  A duration is the key's primary field (A8: a TSP key is
+    duration << 28), exact below the 2^28 - 1 clamp; a clamped one is summed
+    on the host."""
+    import torch
+    N = cis[0].N
+    host = np.empty((len(cis), N, N), dtype=np.int32)
+    for x, ci in enumerate(cis):
+        host[x] = ci.durations[0]
+    tours, keys = ctx.tsp_batch_dp(torch.from_numpy(host).to(ctx.dev))
+    tours, keys = tours.cpu().tolist(), keys.cpu().tolist()
+    clamp = (1 << 28) - 1
+    durs = []
+    for ci, tour, k in zip(cis, tours, keys):
+        d = (k >> 28) & clamp
+        if d == clamp:
+            path = [0] + tour + [0]
+            d = int(sum(int(ci.durations[0][a][b]) for a, b in zip(path, path[1:])))
+        durs.append(int(d))
+    return tours, durs
+
+
+def solve_tsp_batch(algorithm: str, requests, *, device: int = 0) -> list:
+    """[solve_tsp(algorithm, *r) for r in requests], element for element, with
+    the small requests sharing launches.  `requests`: (durations, customers,
+    start_node, start_time) tuples, or dicts with those keys.  Only "dp" has a
+    batched kernel (spec A18).  Every request is compacted and checked on the
+    host before anything is launched; a bad one (hour-indexed, more than
+    DP_MAX_CUSTOMERS customers, A9 guard) raises solve_tsp("dp")'s message
+    prefixed with its index.  Requests of 2..BATCH_DP_MAX_CUSTOMERS customers
+    are grouped by node count, one upload and one tsp_batch_dp launch per
+    group; none or one customer take solve_tsp's trivial path, and 13..24
+    customers its single-request Held-Karp, one by one."""
+    if algorithm != "dp":
+        raise ValueError(f'solve_tsp_batch: no batched kernel for algorithm {algorithm!r}; only '
+                         '"dp" (exact Held-Karp) is batched')
+    reqs, cis = [], []
+    for x, r in enumerate(requests):
+        if isinstance(r, dict):
+            r = (r["durations"], r["customers"], r["start_node"], r.get("start_time", 0))
+        r = tuple(r) + (0,) * (4 - len(r))
+        try:
+            ci = compact_tsp(*r[:4])
+            _check_dp(ci)
+            if not batch_dp_guard(ci):
+                raise ValueError("start + (N+K+1)*max_duration overflows int32 (A9 guard)")
+        except ValueError as e:
+            raise ValueError(f"request {x}: {e}") from None
+        reqs.append(r[:4])
+        cis.append(ci)
+    if _remote() is not None:      # no local GPU: the GPU box answers each request
+        return [solve_tsp("dp", *r) for r in reqs]
+    out = [None] * len(cis)
+    groups: dict = {}
+    for x, ci in enumerate(cis):
+        if 2 <= ci.n <= BATCH_DP_MAX_CUSTOMERS:
+            groups.setdefault(ci.N, []).append(x)
+        else:
+            out[x] = solve_tsp("dp", *reqs[x], device=device)
+    if groups:
+        ctx = context(device)
+        for N, xs in groups.items():
+            tours, durs = batch_dp_launch(ctx, [cis[x] for x in xs])
+            for x, tour, dur in zip(xs, tours, durs):
+                nodes = cis[x].nodes
+                out[x] = {"duration": dur,
+                          "vehicle": [nodes[0]] + [nodes[c] for c in tour] + [nodes[0]]}
+    return out
 
 
 def solve_vrp(algorithm: str, durations, locations, capacities, start_times,
