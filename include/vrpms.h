@@ -63,7 +63,12 @@ int vrpms_ctx_destroy(vrpms_ctx* ctx);
 /* Load an instance (replaces the DB fetch result consumed at
  * api/vrp/ga/index.py:41-42 / api/tsp/ga/index.py:33-34).
  *   problem  VRPMS_TSP or VRPMS_CVRP
- *   d_dur    int32 [H][N][N] durations in minutes (A2/A3), H = 1 or 24
+ *   d_dur    int32 [H][N][N] durations in minutes (A2/A3), any H in
+ *            [1, 1024] with H * N * N < 2^31: an edge leaving at minute t
+ *            reads slice (t / 60) % H.  Scoring and the SA / GA / ACO / BF
+ *            kernels take every such H (H = 1 and 24 have kernels of their
+ *            own); the exact solvers still need H = 1 (tsp_dp, vrp_sp) or
+ *            H = 1 or 24 (tsp_tdp, vrp_tdsp) and refuse any other
  *   d_demand int32 [N] (demand[0] ignored); NULL for TSP
  *   d_cap    int32 [K] vehicle capacities (api/parameters.py:11); NULL for TSP
  *   d_start  int32 [K] start minutes (api/parameters.py:12; TSP: K = 1 and
@@ -117,7 +122,11 @@ int vrpms_eval_path(vrpms_ctx* ctx, int32_t perm_bytes, int64_t ld, const void* 
  *   add's carry (the two give identical keys; tests check both). */
 #define VRPMS_OPT_SPLIT_MODE 1
 /*   VRPMS_OPT_STAGED_M: candidates interleaved per lane in eval_staged
- *   (0 = auto: 2 for hour-indexed matrices, 1 for static; 1 or 2 force). */
+ *   (0 = auto: 1; 1 forces 1; 2 asks for two, which the launcher grants
+ *   only on an hour-indexed matrix (H > 1) whose fleet needs no vehicle
+ *   skipping (every demand fits the smallest vehicle) and whose two-candidate
+ *   tile fits the LDS -- otherwise it runs one; A/B, the results are the
+ *   same). */
 #define VRPMS_OPT_STAGED_M 2
 /*   VRPMS_OPT_WORDS_KERNEL: LDS-packed kernel for path 0 of vrpms_eval
  *   (0 = auto: eval_cvrp_rows2; 1 = eval_cvrp_packed, the LDS-tile kernel

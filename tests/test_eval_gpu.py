@@ -352,3 +352,61 @@ def test_rows2_mixed_exhaustion(words_gen, coracle, n, ld, slack):
     for cfg in range(6):
         ctx.set_rows_config(cfg)
         check_batch(ctx, coracle, inst, P, n=inst.n, expect_path=0)
+
+
+# VRPMS_OPT_STAGED_M = 2: eval_staged<..., M = 2, ...>, two interleaved
+# candidates per lane (lane l of a tile walks rows l and 512 + l), which auto
+# never picks.  launch_staged grants it on an hour-indexed matrix (H > 1)
+# without the FLEX split when the 1,024-row tile fits the LDS; the variant
+# each case reaches, <MatT, HM, CVRP, FLEX, PermT, M, ALIGNED, MLDS>:
+def _m2_case(name):
+    if name == "td20_lds":            # <u16, 24, CVRP, -, u8, 2, aligned, MLDS>
+        return synth.td_cvrp(20, 3, seed=3), np.uint8, None
+    if name == "td200_l2":            # <u16, 24, CVRP, -, u8, 2, aligned, !MLDS>
+        return synth.td_cvrp(200, 16, seed=0), np.uint8, None
+    if name == "td60_u16":            # <u16, 24, CVRP, -, u16, 2, aligned, !MLDS>
+        return synth.td_cvrp(60, 5, seed=5), np.uint16, None
+    if name == "td60_ld61":           # <u16, 24, CVRP, -, u8, 2, !aligned, !MLDS>
+        return synth.td_cvrp(60, 5, seed=5), np.uint8, 61
+    if name == "tdtsp30":             # <u16, 24, TSP, -, u8, 2, aligned, MLDS>
+        base = synth.td_cvrp(30, 2, seed=1)
+        return synth.Instance("tdtsp", base.durations, None, None, np.array([415]), "tsp"), \
+            np.uint8, None
+    if name == "td40_i32":            # <i32, 24, CVRP, -, u8, 2, aligned, !MLDS> (161 KB matrix)
+        import dataclasses
+        base = synth.td_cvrp(40, 4, seed=2)
+        return dataclasses.replace(base, durations=base.durations * 60), np.uint8, None
+    if name == "cvrp20_h7":           # <u16, 0, CVRP, -, u8, 2, aligned, MLDS>: M = 2 x HM = 0
+        from test_hours_gpu import with_hours
+        return with_hours(synth.td_cvrp(20, 3, seed=3), 7, first=7), np.uint8, None
+    if name == "td60_flex":           # min_cap < max_dem: the launcher falls back to M = 1,
+        inst = synth.td_cvrp(60, 6, seed=4)     # <u16, 24, CVRP, FLEX, u8, 1, aligned, !MLDS>
+        inst.capacities = np.array([40, 5, 90, 30, 7, 60])
+        inst.demand[5] = 80
+        return inst, np.uint8, None
+    raise KeyError(name)
+
+
+# a tile is 1,024 rows at M = 2: C = 1 leaves the lane's second candidate
+# absent, 513 puts one row in the tile's second half, 1,539 = 1,024 + 512 + 3
+# leaves the last tile ragged in its second half
+@pytest.mark.parametrize("C", [1, 513, 1024 + 512 + 3])
+@pytest.mark.parametrize("name", ["td20_lds", "td200_l2", "td60_u16", "td60_ld61", "tdtsp30",
+                                  "td40_i32", "cvrp20_h7", "td60_flex"])
+def test_staged_two_candidates_per_lane(ctx, coracle, name, C):
+    inst, dtype, ld = _m2_case(name)
+    P = synth.random_perms(C, inst.n, seed=C, ld=ld, dtype=dtype)
+    objective = C % 2
+
+    def parts():
+        return [t.cpu().numpy() for t in ctx.eval(upload(ctx, P), n=inst.n, with_parts=True)]
+
+    ctx.set_staged_m(2)
+    try:
+        check_batch(ctx, coracle, inst, P, n=inst.n, objective=objective, expect_path=2)
+        forced = parts()
+    finally:
+        ctx.set_staged_m(0)
+    check_batch(ctx, coracle, inst, P, n=inst.n, objective=objective, expect_path=2)
+    for a, b in zip(forced, parts()):
+        np.testing.assert_array_equal(a, b)

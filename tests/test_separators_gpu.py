@@ -443,6 +443,22 @@ SEG_CASES = [
     # it, so the launcher hands the chains to the full re-evaluation kernels
     ("cvrp150_huge_demand", lambda: _huge_demand(synth.cvrp(150, 12, seed=19)), "pack", 4, 40,
      1 / 300.0, 0, 0, 64),
+    # wavefronts per chain W and moves per lane M = moves / 64 / W that no case
+    # above reaches: launch_sa_seg starts from W = min(moves / 64, 4) and steps
+    # W down until it divides moves / 64 -- 192: (W, M) = (3, 1), 320: (1, 5),
+    # 384: (3, 2), 448: (1, 7) -- on one capacity and on per-vehicle capacities
+    ("cvrp150_m192", lambda: synth.cvrp(150, 12, seed=25), "pack", 8, 100, 1 / 100.0, 0, 0, 192),
+    ("cvrp150_m320", lambda: synth.cvrp(150, 12, seed=26), "random", 8, 60, 1e-7, 0, 0, 320),
+    ("cvrp150_m384", lambda: synth.cvrp(150, 12, seed=27), "pack", 8, 100, 1 / 100.0, 12, 2, 384),
+    ("cvrp150_m448", lambda: synth.cvrp(150, 12, seed=28), "pack", 8, 100, 1 / 100.0, 0, 0, 448),
+    ("cvrp150_het_m192", lambda: _classes(synth.cvrp(150, 12, seed=29, slack=1.3), (1.3, 1.0, 0.8)),
+     "pack", 8, 100, 1 / 100.0, 12, 2, 192),
+    ("cvrp150_het_m320", lambda: _classes(synth.cvrp(150, 12, seed=30, slack=1.3), (1.2, 0.9),
+                                          shuffle=True), "pack", 8, 100, 1 / 100.0, 0, 0, 320),
+    ("cvrp150_het_m384", lambda: _classes(synth.cvrp(150, 12, seed=31, slack=1.2), (1.5, 1.0, 0.7)),
+     "random", 8, 60, 1e-7, 0, 0, 384),
+    ("cvrp150_het_m448", lambda: _classes(synth.cvrp(150, 12, seed=32, slack=1.3), (1.3, 1.0, 0.8)),
+     "pack", 8, 100, 1 / 100.0, 12, 2, 448),
 ]
 
 
@@ -515,21 +531,25 @@ def test_segment_sa_matches_c_restatement(ctx, coracle, name, maker, start, chai
         assert (best.cpu().numpy().view(np.uint16) == cbest).all()
 
 
-@pytest.mark.parametrize("het,moves", [(False, 128), (True, 64)])
-def test_segment_sa_two_wavefronts_per_simd_same_trajectories(ctx, het, moves):
+@pytest.mark.parametrize("het,moves,big", [
+    pytest.param(False, 128, 1280, id="False-128"), pytest.param(True, 64, 1280, id="True-64"),
+    pytest.param(False, 128, 600, id="False-128-600chains")])
+def test_segment_sa_two_wavefronts_per_simd_same_trajectories(ctx, het, moves, big):
     """A launch with more wavefronts than the chip has SIMDs runs
     sa_seg_kernel's OCC = 2 variant (registers capped for two wavefronts per
     SIMD).  Chain c draws the same Philox streams in any launch, so the first
     chains of a 1,280-chain launch must follow exactly the trajectories of
     an 8-chain launch (the OCC = 1 variant, checked against the C
-    restatement above)."""
+    restatement above).  1,280 chains halve W to 1 (2,560 wavefronts would
+    pass 8 per CU); 600 chains at moves = 128 keep W = 2: 1,200 wavefronts,
+    more than 4 x 256 CUs and at most 8 x 256, so OCC = 2 with two
+    wavefronts per chain."""
     torch = torch_()
     inst = synth.x_style(1000, seed=3)
     if het:
         inst = _classes(inst, (1.4, 1.1, 0.9))
     load(ctx, inst)
     S = inst.K - 1
-    big = 1280
     P0 = synth.random_perms(big, inst.n, seed=9, dtype=np.uint16)
     P = np.array([spec.pack_separators(p, S, inst.demand, inst.capacities) for p in P0])
     P = P.astype(np.int16)
@@ -544,3 +564,91 @@ def test_segment_sa_two_wavefronts_per_simd_same_trajectories(ctx, het, moves):
         out.append((cur.cpu().numpy()[:8], u64(ck)[:8], best.cpu().numpy()[:8], u64(bk)[:8]))
     a, b = out
     assert (a[0] == b[0]).all() and a[1] == b[1] and (a[2] == b[2]).all() and a[3] == b[3]
+
+
+def _start_tours(inst, start, chains):
+    S = {"pack_few": inst.K - 4, "nosep": 0}.get(start, inst.K - 1)
+    if start == "nosep":
+        P = synth.random_perms(chains, inst.n, seed=9, dtype=np.uint16)
+    elif start != "random":
+        P0 = synth.random_perms(chains, inst.n, seed=9, dtype=np.uint16)
+        f = spec.insert_separators if start == "greedy" else spec.pack_separators
+        P = np.array([f(p, S, inst.demand, inst.capacities) for p in P0])
+    else:
+        P = sep_tours(chains, inst.n, S, seed=9, dtype=np.uint16)
+    return P.astype(np.int16)
+
+
+def _run_sa_moves(ctx, P, steps, inv_t0, seed, step0, window, types, moves):
+    torch = torch_()
+    cur = torch.from_numpy(P.copy()).to(ctx.dev)
+    best = cur.clone()
+    ck = torch.empty(P.shape[0], dtype=torch.int64, device=ctx.dev)
+    bk = torch.full((P.shape[0],), -1, dtype=torch.int64, device=ctx.dev)
+    ctx.sa_run(cur, ck, best, bk, steps=steps, inv_t0=inv_t0, inv_alpha=1 / 0.99, seed=seed,
+               step0=step0, window=window, window_types=types, moves=moves)
+    return cur.cpu().numpy(), u64(ck), best.cpu().numpy(), u64(bk)
+
+
+def _same_run(a, b):
+    return (a[0] == b[0]).all() and a[1] == b[1] and (a[2] == b[2]).all() and a[3] == b[3]
+
+
+@pytest.mark.parametrize("moves", [256, 512])
+@pytest.mark.parametrize("het", [False, True], ids=["uniform", "het"])
+def test_segment_sa_forced_waves_same_trajectories(ctx, coracle, het, moves):
+    """VRPMS_OPT_SEG_WAVES forces W wavefronts per chain (launch_sa_seg steps
+    a W that does not divide moves / 64 down to one that does, so 3 runs as
+    2 here); a lane then prices M = moves / 64 / W moves per step:
+      moves = 256: W = 1 -> M = 4, 2 -> 2, 3 -> (W = 2) 2, 4 -> 1 (auto: W = 4)
+      moves = 512: W = 1 -> M = 8 = kSegMaxMoves, 2 -> 4, 3 -> (W = 2) 4, 4 -> 2 (auto)
+    Every forced run equals the C restatement and the auto run."""
+    inst = synth.cvrp(150, 12, seed=40 + moves // 256, slack=1.3 if het else 1.1)
+    if het:
+        inst = _classes(inst, (1.3, 1.0, 0.8))
+    load(ctx, inst)
+    chains, steps, inv_t0, window, types = 8, 100, 1 / 100.0, 12, 2
+    P = _start_tours(inst, "pack", chains)
+    auto = _run_sa_moves(ctx, P, steps, inv_t0, 33, 5, window, types, moves)
+    ccur, cbest = P.view(np.uint16).copy(), P.view(np.uint16).copy()
+    cbk = np.full(chains, 2**64 - 1, dtype=np.uint64)
+    cck = coracle.sa_run(inst.durations, ccur, cbest, cbk, steps, inv_t0, 1 / 0.99, 33, 5,
+                         inst.demand, inst.capacities, inst.start_times, window=window,
+                         window_types=types, moves=moves)
+    want = (ccur.view(np.int16), [int(x) for x in cck], cbest.view(np.int16),
+            [int(x) for x in cbk])
+    assert _same_run(auto, want)
+    assert (auto[0] != P).any()
+    for W in (1, 2, 3, 4):
+        ctx.set_seg_waves(W)
+        try:
+            forced = _run_sa_moves(ctx, P, steps, inv_t0, 33, 5, window, types, moves)
+        finally:
+            ctx.set_seg_waves(0)
+        assert _same_run(forced, want), W
+        assert _same_run(forced, auto), W
+
+
+# sa_route_kernel's LDS request: one workgroup per CU pads it past half the
+# CU's LDS (auto for multi-wavefront chains), two leave it as it is (auto for
+# four one-wavefront chains per workgroup).  Both rows are static asymmetric
+# instances, which launch_sa_seg declines (!symmetric) and launch_sa_td
+# declines (H != 24), so auto reaches the route kernel: the first
+# sa_route_kernel<i32, 1> with four chains per workgroup, the second
+# sa_route_kernel<u16, 1, HV> with two wavefronts per chain.
+@pytest.mark.parametrize("name,moves", [("cvrp300_asym_i32", 64), ("x1000_asym_het_starts", 128)])
+def test_route_local_sa_workgroups_per_cu_same_trajectories(ctx, name, moves):
+    case = {c[0]: c for c in ROUTE_CASES}[name]
+    _, maker, start, chains, steps, inv_t0, window, types = case
+    inst = maker()
+    load(ctx, inst)
+    P = _start_tours(inst, start, chains)
+    auto = _run_sa_moves(ctx, P, steps, inv_t0, 21, 7, window, types, moves)
+    assert (auto[0] != P).any()
+    for wg in (1, 2):
+        ctx.set_route_wg_per_cu(wg)
+        try:
+            forced = _run_sa_moves(ctx, P, steps, inv_t0, 21, 7, window, types, moves)
+        finally:
+            ctx.set_route_wg_per_cu(0)
+        assert _same_run(forced, auto), wg

@@ -509,3 +509,68 @@ def test_service_batch_exact_equals_the_unbatched_answers():
         want = off.solve_inline("tsp", algo, body) if kind == "inline" else \
             off.post("tsp", algo, body)
         assert want[0] == 200 and got == want
+
+
+# ---------------------------------------------------------------------------
+# VRPMS_OPT_BATCH_DP_TEAM: every tsp_batch_dp_kernel<T> at every n, not only
+# the n -> T pairs of the launcher's table (which never picks T = 64)
+# ---------------------------------------------------------------------------
+TEAMS = (16, 32, 64, 128, 256)
+TEAM_NS = (1, 2, 5, 8, 9, 10, 11, 12)
+LDS_BYTES = 160 * 1024
+# 256 / T tables of n 2^(n-1) words do not fit next to each other
+TEAM_REFUSED = {(10, 16), (10, 32), (11, 16), (11, 32), (11, 64),
+                (12, 16), (12, 32), (12, 64), (12, 128)}
+
+
+def batch_dp_lds_bytes(n, T):
+    """tsp_batch_dp.hip batch_dp_lds_bytes: the binomial table (172 words),
+    then per team the 13 x 16-word matrix image and the table padded to four
+    words."""
+    pad4 = ((n << (n - 1)) + 3) & ~3
+    return (172 + (256 // T) * (208 + pad4)) * 4
+
+
+def test_forced_team_refused_set_is_what_the_lds_formula_gives():
+    over = {(n, T) for n in range(1, 13) for T in TEAMS if batch_dp_lds_bytes(n, T) > LDS_BYTES}
+    assert over == TEAM_REFUSED
+    assert batch_dp_lds_bytes(9, 16) == 161456 <= LDS_BYTES       # the tightest fit
+    assert batch_dp_lds_bytes(12, 256) == 99824                   # the auto choice at n = 12
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,R", [(n, 5) for n in TEAM_NS] + [(8, 67)])
+@pytest.mark.parametrize("T", TEAMS)
+def test_gpu_forced_team_equals_reference_and_auto_or_is_refused(ctx, T, n, R):
+    """T = 256 at n = 1 and 2 leaves most of a team idle through every
+    barrier; (n = 9, T = 16) fills the LDS to 161,456 of 163,840 B; R = 67 at
+    T = 16 is five workgroups, the last with three of its sixteen teams."""
+    import torch
+    lib, N = ctx.lib, n + 1
+    cases = mixed(N, R, seed=R)
+    mats = [matrix(*c) for c in cases]
+    auto = gpu_batch(ctx, mats)
+    wkeys, wtours = expected(cases)
+    assert auto == (wkeys, wtours)
+    ctx.set_batch_dp_team(T)
+    try:
+        if (n, T) in TEAM_REFUSED:
+            M = torch.tensor(np.stack(mats), dtype=torch.int32, device=ctx.dev)
+            tours = torch.full((R, n), -7, dtype=torch.int16, device=ctx.dev)
+            keys = torch.full((R,), -7, dtype=torch.int64, device=ctx.dev)
+            rc = lib.vrpms_tsp_batch_dp(ctx.handle, M.data_ptr(), R, N, tours.data_ptr(),
+                                        keys.data_ptr(), ctx.stream())
+            assert rc == _lib.VRPMS_EINVAL
+            msg = lib.vrpms_last_error()
+            assert b"vrpms_tsp_batch_dp" in msg and b"bytes of LDS" in msg
+            assert str(batch_dp_lds_bytes(n, T)).encode() in msg
+            torch.cuda.synchronize(ctx.dev)
+            assert (tours == -7).all().item() and (keys == -7).all().item()
+        else:
+            assert batch_dp_lds_bytes(n, T) <= LDS_BYTES
+            forced = gpu_batch(ctx, mats)
+            assert forced[1] == wtours and forced[0] == wkeys
+            assert forced == auto
+    finally:
+        ctx.set_batch_dp_team(0)
+    assert gpu_batch(ctx, mats[:1]) == (wkeys[:1], wtours[:1])      # auto again
