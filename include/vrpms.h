@@ -411,6 +411,34 @@ int vrpms_tsp_batch_sa(vrpms_ctx* ctx, const int32_t* d_mats, int32_t R, int32_t
 int vrpms_tsp_batch_dp(vrpms_ctx* ctx, const int32_t* d_mats, int32_t R, int32_t N,
                        uint16_t* d_tours, uint64_t* d_keys, void* stream);
 
+/* Throughput mode of the exact VRP: R independent static
+ * CVRP requests of one node count N, 2 <= N <= 13 (n = N - 1 customers, node 0
+ * the depot), one fleet size K, 1 <= K <= 64, and one objective, each with its
+ * own int32 [N][N] matrix (d_mats [R][N][N], asymmetric and non-metric
+ * allowed), demands (d_demand [R][N], entry 0 ignored) and capacities (d_cap
+ * [R][K], in vehicle order; they may differ or be 0).  (N + K + 1) * max(D) <
+ * 2^31 (A9) and non-negative demands and capacities are the caller's promise.
+ * A request's whole state -- the compact Held-Karp table, the route table and
+ * the K partition layers -- lives in LDS: a team of `team` threads per request
+ * (0 = the measured n -> T table, raised where fewer requests fit the LDS; or
+ * 16, 32, 64, 128, 256: the answers do not depend on it), 256 / team requests
+ * per workgroup, one launch for all R.  vrpms_vrp_batch_sp_lds gives the
+ * launch's dynamic-LDS bytes for (n, K, team) (host only, no context); a
+ * launch that needs more than the device has is refused with that byte count
+ * in the message.  Out: d_tours [R][N-1+K] and d_keys [R], per request exactly
+ * what vrpms_vrp_sp_run writes for that instance (route 0, a separator 0, ...,
+ * route K-1, 0, then the unserved customers ascending; its A8 key), and d_durs
+ * [R][K], the K route durations, unclamped.  No instance and no workspace
+ * needed; asynchronous on `stream`.  R = 0 launches nothing.  VRPMS_EINVAL,
+ * with nothing launched and nothing written, for a NULL ctx, R < 0, N outside
+ * 2..13, K outside 1..64, an unknown objective or team, a NULL buffer with
+ * R > 0, or an LDS need above the device's. */
+int vrpms_vrp_batch_sp_lds(int32_t n, int32_t K, int32_t team, uint64_t* bytes);
+int vrpms_vrp_batch_sp(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_demand,
+                       const int32_t* d_cap, int32_t R, int32_t N, int32_t K, int32_t objective,
+                       int32_t team, int16_t* d_tours, uint64_t* d_keys, int32_t* d_durs,
+                       void* stream);
+
 /* ------------------------------------------------------------------------
  * Populations and the island model.  A pool is a set of
  * tours with their A8 keys: SA chains, a GA population ([islands][pop],

@@ -41,6 +41,15 @@ def tour_dtype(N: int):
     return torch.uint8 if N <= 256 else torch.int16
 
 
+def vrp_batch_sp_lds(n: int, K: int, team: int = 0) -> int:
+    """vrpms_vrp_batch_sp_lds: the dynamic-LDS bytes of a vrp_batch_sp launch
+    for n customers, K vehicles and `team` threads per request (0 = the auto
+    team).  Host only: needs the library, no GPU."""
+    nbytes = ctypes.c_uint64()
+    check(_lib.load().vrpms_vrp_batch_sp_lds(int(n), int(K), int(team), ctypes.byref(nbytes)))
+    return int(nbytes.value)
+
+
 class Context:
     """One solver context on one GPU (``vrpms_ctx_create``)."""
 
@@ -415,6 +424,38 @@ class Context:
         check(self.lib.vrpms_tsp_batch_dp(self._ctx, mats.data_ptr(), R, N, tours.data_ptr(),
                                           keys.data_ptr(), self.stream()))
         return tours, keys
+
+    def vrp_batch_sp(self, mats, demand, caps, objective: int = OBJ_SUM, team: int = 0):
+        """Exact VRP optimum of every request in one launch (spec A19, at most
+        12 customers, all requests of one N, K and objective): mats int32
+        [R][N][N], demand int32 [R][N] (entry 0 ignored) and caps int32 [R][K]
+        on the device -> (tours int16 [R][N-1+K], keys int64 [R], durs int32
+        [R][K]), per request the tour and key vrp_sp returns for that instance
+        and its K route durations, unclamped.  `team`: threads per request, 0 =
+        auto, or 16, 32, 64, 128, 256 (the answers do not depend on it).
+        (N + K + 1) * max(mats) < 2^31 (A9) and non-negative demands and
+        capacities are the caller's promise: whoever builds the buffers from
+        host data checks them before uploading.  Asynchronous on the current
+        stream."""
+        torch = _torch()
+        if mats.device != self.dev or mats.dim() != 3 or mats.shape[1] != mats.shape[2] or \
+                mats.dtype != torch.int32 or not mats.is_contiguous():
+            raise ValueError(f"mats must be a contiguous int32 [R][N][N] tensor on {self.dev}")
+        R, N, _ = mats.shape
+        for name, t, cols in (("demand", demand, N), ("caps", caps, None)):
+            if t.device != self.dev or t.dim() != 2 or t.shape[0] != R or t.dtype != torch.int32 or \
+                    not t.is_contiguous() or (cols is not None and t.shape[1] != cols):
+                raise ValueError(f"{name} must be a contiguous int32 [R][{'N' if cols else 'K'}] "
+                                 f"tensor on {self.dev}")
+        K = caps.shape[1]
+        tours = torch.empty((R, max(N - 1 + K, 1)), dtype=torch.int16, device=self.dev)
+        keys = torch.empty(R, dtype=torch.int64, device=self.dev)
+        durs = torch.empty((R, max(K, 1)), dtype=torch.int32, device=self.dev)
+        check(self.lib.vrpms_vrp_batch_sp(self._ctx, mats.data_ptr(), demand.data_ptr(),
+                                          caps.data_ptr(), R, N, K, int(objective), int(team),
+                                          tours.data_ptr(), keys.data_ptr(), durs.data_ptr(),
+                                          self.stream()))
+        return tours, keys, durs
 
     def set_batch_dp_team(self, T: int):
         """Threads per request of tsp_batch_dp: 0 = auto (the n -> T table),

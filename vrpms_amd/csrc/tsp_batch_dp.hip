@@ -36,20 +36,10 @@
 
 #include "common.hpp"
 #include "ctx.hpp"
+#include "tsp_batch_dp.hpp"
 #include "tsp_dp.hpp"
 
 namespace vrpms {
-
-// Why 12: the compact table has n 2^(n-1) 32-bit words, 98,304 B at n = 12;
-// with the 13 x 16-word matrix image (832 B) and the binomial table (704 B)
-// that is 99,840 B, within ctx->max_lds (160 KiB per CU).  At n = 13 the table
-// alone is 13 * 4096 * 4 = 212,992 B, which does not fit.
-constexpr int kBatchDpMaxN = 12;
-constexpr int kBatchDpNodes = kBatchDpMaxN + 1;
-constexpr int kBatchDpRow = 16;     // words per matrix row in LDS: three 16-byte reads per row
-constexpr int kBatchDpBinomWords = (kBatchDpNodes * kBatchDpNodes + 3) & ~3;
-constexpr int kBatchDpMatWords = kBatchDpNodes * kBatchDpRow;
-constexpr uint32_t kBatchDpOut = 0x80000000u;   // h of a customer outside S
 
 // threads per request by n (index n): the fastest T of tools/batch_dp_rate.py
 // --teams 16,32,64,128,256 at each n (DESIGN.md §4.3i has the measurements)
@@ -66,17 +56,10 @@ struct BatchDpArgs {
 };
 
 // words of one team: the matrix image, then the table padded to 16 bytes
-inline size_t batch_dp_team_words(int n) {
-  return kBatchDpMatWords + ((((size_t)n << (n - 1)) + 3) & ~(size_t)3);
-}
+inline size_t batch_dp_team_words(int n) { return kBatchDpMatWords + batch_dp_table_words(n); }
 
 inline size_t batch_dp_lds_bytes(int n, int T) {
   return (kBatchDpBinomWords + (size_t)(256 / T) * batch_dp_team_words(n)) * 4;
-}
-
-// S with bit b squeezed out
-VRPMS_DEV uint32_t batch_dp_squeeze(uint32_t S, int b) {
-  return (S & ((1u << b) - 1u)) | ((S >> (b + 1)) << b);
 }
 
 template <int T>
@@ -93,51 +76,11 @@ __global__ __launch_bounds__(256) void tsp_batch_dp_kernel(BatchDpArgs a) {
   uint32_t* Dr = batch_dp_lds + kBatchDpBinomWords + team * team_words;  // Dr[node][i] = D[node][i + 1]
   uint32_t* g = Dr + kBatchDpMatWords;                            // g[j][c], customer j + 1
 
-  for (int e = threadIdx.x; e < kBatchDpNodes * kBatchDpNodes; e += 256)
-    B[e] = kBatchDpBinom.v[e / kBatchDpNodes][e % kBatchDpNodes];
-  const int32_t* D = a.mats + (active ? req : 0) * N * N;
-  if (active) {
-    for (int e = tl; e < kBatchDpMatWords; e += T) {
-      const int node = e / kBatchDpRow, i = e % kBatchDpRow;
-      Dr[e] = (node <= n && i < n) ? (uint32_t)D[node * N + i + 1] : 0u;
-    }
-    for (int j = tl; j < n; j += T) g[j * half] = (uint32_t)D[(j + 1) * N];   // the empty set
-  }
+  batch_dp_stage_binom(kBatchDpBinom, B);
+  if (active) batch_dp_stage<T>(a.mats + req * N * N, N, tl, Dr, g);
   __syncthreads();
 
-  for (int k = 1; k < n; ++k) {
-    // an inactive team has no subsets: it only keeps the barrier's count
-    const uint32_t count = active ? B[n * kBatchDpNodes + k] : 0u;
-    const uint32_t chunk = (count + T - 1) / T;
-    const uint32_t lo = tl * chunk;
-    const uint32_t hi = lo + chunk < count ? lo + chunk : count;
-    if (lo < hi) {
-      uint32_t S = dp_unrank(B, kBatchDpNodes, n, k, lo);
-      for (uint32_t r = lo; r < hi; ++r) {
-        uint32_t h[kBatchDpMaxN];
-#pragma unroll
-        for (int i = 0; i < kBatchDpMaxN; ++i)
-          h[i] = ((S >> i) & 1u) ? g[i * half + batch_dp_squeeze(S, i)] : kBatchDpOut;
-        for (uint32_t m = full & ~S; m; m &= m - 1u) {
-          const int j = __builtin_ctz(m);
-          const v4u* row = reinterpret_cast<const v4u*>(Dr + (j + 1) * kBatchDpRow);
-          const v4u r0 = row[0];
-          uint32_t best = min(min(r0.x + h[0], r0.y + h[1]), min(r0.z + h[2], r0.w + h[3]));
-          if (n > 4) {
-            const v4u r1 = row[1];
-            best = min(best, min(min(r1.x + h[4], r1.y + h[5]), min(r1.z + h[6], r1.w + h[7])));
-          }
-          if (n > 8) {
-            const v4u r2 = row[2];
-            best = min(best, min(min(r2.x + h[8], r2.y + h[9]), min(r2.z + h[10], r2.w + h[11])));
-          }
-          g[j * half + batch_dp_squeeze(S, j)] = best;
-        }
-        S = dp_next_mask(S);
-      }
-    }
-    __syncthreads();
-  }
+  batch_dp_fill<T>(B, Dr, g, n, tl, active);
 
   // the forward walk, on one 16-lane group (T is a multiple of 16, so the
   // group lies inside one wavefront and is active as a whole)

@@ -245,15 +245,24 @@ class TspBatcher:
         mx = int(ci.durations.max()) if ci.durations.size else 0
         return (ci.N + 2) * mx < 2**31
 
-    def solve(self, ci) -> dict:
-        """Blocks until the request's launch finished -> the TSP slot dict."""
-        job = {"ci": ci, "done": threading.Event()}
+    @staticmethod
+    def group_key(job):
+        """What the jobs of one launch share: the node count."""
+        return job["ci"].N
+
+    def _wait(self, job):
+        """Queue the job and block until its launch finished."""
         with self._cv:
             self._q.append(job)
             self._cv.notify()
         job["done"].wait()
         if "error" in job:
             raise job["error"]
+
+    def solve(self, ci) -> dict:
+        """Blocks until the request's launch finished -> the TSP slot dict."""
+        job = {"ci": ci, "done": threading.Event()}
+        self._wait(job)
         path = [0] + list(job["tour"]) + [0]
         duration = job.get("duration")
         if duration is None:  # a launch that returns tours only (tests' stand-in launches)
@@ -271,7 +280,7 @@ class TspBatcher:
                 batch, self._q = self._q[:self.max_batch], self._q[self.max_batch:]
             groups = {}
             for job in batch:
-                groups.setdefault(job["ci"].N, []).append(job)
+                groups.setdefault(self.group_key(job), []).append(job)
             for N, jobs in groups.items():
                 dev = self.devices[self._rr % len(self.devices)]
                 self._rr += 1
@@ -362,6 +371,47 @@ class ExactTspBatcher(TspBatcher):
             return solver.batch_dp_launch(solver.context(dev), cis)
 
 
+class ExactVrpBatcher(TspBatcher):
+    """Coalesces concurrent exact small-fleet requests -- ("vrp", "sp") on the
+    inline route -- into one `vrp_batch_sp` launch per (node count, fleet size,
+    objective) (spec A19: each request's partition DP in LDS).  The queue, the
+    window, the device round-robin and the error fan-out are TspBatcher's.  A
+    batched answer does not depend on the batch: it is the unbatched answer of
+    the same request.  ("vrp", "bf") does not ride it: bf is the optimum over
+    greedy-split giant tours, a different and sometimes worse answer."""
+
+    def __init__(self, app, window_s: float = 0.005, max_batch: int = 16384, launch=None):
+        super().__init__(app, window_s, steps=0, max_batch=max_batch, launch=launch)
+
+    @classmethod
+    def accepts(cls, ci) -> bool:
+        """Static matrices of at least one customer whose (n, K) is inside
+        A19's LDS domain (solver.batch_sp_fits) and that pass the int32 guards
+        vrpms_set_instance applies on the unbatched path; anything else takes
+        the unbatched path, so both paths share one error contract."""
+        from . import solver
+        return solver.batch_sp_fits(ci) and solver.batch_sp_guard(ci)
+
+    @staticmethod
+    def group_key(job):
+        return job["ci"].N, len(job["ci"].capacities), job["objective"]
+
+    def solve(self, ci, objective: str = "sum") -> dict:
+        """Blocks until the request's launch finished -> the VRP slot dict."""
+        from . import solver
+        job = {"ci": ci, "objective": "max" if objective == "max" else "sum",
+               "done": threading.Event()}
+        self._wait(job)
+        return solver.sp_result(ci, list(job["tour"]), job["duration"])
+
+    def _gpu_launch(self, key, cis, device=None):
+        """-> (tours, route durations) on `device` (default: the app's first)."""
+        from . import solver
+        dev = self.devices[0] if device is None else device
+        with self.app.locks[dev]:
+            return solver.batch_sp_launch(solver.context(dev), cis, key[2])
+
+
 # ---------------------------------------------------------------------------
 # the endpoint logic
 # ---------------------------------------------------------------------------
@@ -382,7 +432,8 @@ class App:
     def __init__(self, store, device: int = 0, seed: int = 0, max_seconds: float | None = None,
                  solve=None, batch_tsp: bool = False, batch_window_s: float = 0.005,
                  batch_steps: int = 2000, batch_launch=None, devices=None,
-                 island_min_n: int = 150, batch_exact: bool = False, batch_exact_launch=None):
+                 island_min_n: int = 150, batch_exact: bool = False, batch_exact_launch=None,
+                 batch_exact_vrp_launch=None):
         self.store = store
         self.devices = list(devices) if devices else [device]
         self.device = self.devices[0]
@@ -398,6 +449,10 @@ class App:
             if batch_tsp else None
         # exact small-TSP requests share tsp_batch_dp launches (off by default)
         self.exact_batcher = ExactTspBatcher(self, batch_window_s, launch=batch_exact_launch) \
+            if batch_exact else None
+        # and exact small-fleet VRP requests vrp_batch_sp launches
+        self.exact_vrp_batcher = ExactVrpBatcher(self, batch_window_s,
+                                                 launch=batch_exact_vrp_launch) \
             if batch_exact else None
 
     def _scheduled(self, problem, algorithm, params, knobs, locations, durations):
@@ -444,6 +499,16 @@ class App:
         ci = solver.compact_tsp(durations, params["customers"], params["start_node"],
                                 params["start_time"] or 0)
         return ci if batcher.accepts(ci) else None
+
+    def _batched_vrp(self, params, durations, locations):
+        """The compact instance when this ("vrp", "sp") request rides the
+        exact VRP batcher, else None."""
+        if self.exact_vrp_batcher is None:
+            return None
+        from . import solver
+        ci = solver.compact_vrp(durations, locations, params["capacities"], params["start_times"],
+                                params["ignored_customers"], params["completed_customers"])
+        return ci if self.exact_vrp_batcher.accepts(ci) else None
 
     def _gpu_solve(self, problem, algorithm, params, knobs, locations, durations):
         """knobs may carry "seed", "time_limit" and "objective" (the /solve
@@ -583,8 +648,12 @@ class App:
         try:
             ci = self._batched_tsp(params, vals["durations"], self.exact_batcher) \
                 if (problem, algorithm) == ("tsp", "dp") and self.exact_batcher is not None else None
+            vrp_ci = self._batched_vrp(params, vals["durations"], locations) \
+                if (problem, algorithm) == ("vrp", "sp") else None
             if ci is not None:
                 result = self.exact_batcher.solve(ci)
+            elif vrp_ci is not None:
+                result = self.exact_vrp_batcher.solve(vrp_ci, knobs.get("objective", "sum"))
             else:
                 result = self._scheduled(problem, algorithm, params, knobs, locations,
                                          vals["durations"])
@@ -696,6 +765,8 @@ def main(argv=None):
     ap.add_argument("--batch-exact", action="store_true",
                     help="coalesce concurrent exact small-TSP requests (/solve/tsp/dp and "
                          "/api/tsp/bf, static matrix, 1..12 customers) into tsp_batch_dp "
+                         "launches, and exact small-fleet VRP requests (/solve/vrp/sp, static "
+                         "matrix, 1..12 customers, a fleet that fits the LDS) into vrp_batch_sp "
                          "launches; the answers equal the unbatched ones")
     ap.add_argument("--batch-window-ms", type=float, default=5.0)
     ap.add_argument("--batch-steps", type=int, default=2000)

@@ -18,7 +18,9 @@ the exact time-expanded subset DP for hour-indexed matrices, spec A16), or
 'tdsp' (VRP only: the exact time-expanded partition DP for hour-indexed
 matrices with per-vehicle capacities and start times, spec A17).
 solve_tsp_batch("dp", requests) answers many small exact TSP requests with
-shared launches (spec A18), each answer solve_tsp("dp")'s.  All search
+shared launches (spec A18), each answer solve_tsp("dp")'s, and
+solve_vrp_batch("sp", requests) many small exact VRP requests (spec A19), each
+answer solve_vrp("sp")'s.  All search
 and scoring runs in the gfx950 kernels (vrpms_amd.core); this module only
 builds the compact instance and maps results
 back to matrix indices.  Node ids in results are matrix row indices
@@ -59,6 +61,12 @@ BATCH_DP_MAX_CUSTOMERS = 12
 # kernel's own limit.  vrpms_vrp_sp_run accepts K <= 64
 SP_MAX_CUSTOMERS = 20
 SP_MAX_VEHICLES = 64
+# batched set partitioning (A19): one request's Held-Karp table, route table and
+# K partition layers have to fit one CU's LDS (vrpms_vrp_batch_sp_lds gives the
+# bytes for (n, K)): K <= 64 up to 9 customers, 32 at 10, 12 at 11, 1 at 12;
+# other requests of a batch take the single-request path
+BATCH_SP_MAX_CUSTOMERS = 12
+BATCH_SP_LDS_BYTES = 160 * 1024
 # time-expanded subset DP (A16, TSP, static or hour-indexed): 2^n n^2 / 4 W
 # word steps over a table of 2^n n W words, W the hours from the start to the
 # upper bound.  The kernel accepts 20 customers; the cap here follows
@@ -629,6 +637,125 @@ def solve_vrp(algorithm: str, durations, locations, capacities, start_times,
            "vehicles": vehicles}
     if with_unvisited:
         out["unvisited"] = unvisited
+    return out
+
+
+def batch_sp_guard(ci: CompactInstance) -> bool:
+    """The two int32 range checks vrpms_set_instance applies to this request
+    on the single-request path: max(start) + (N + K + 1) * max_duration < 2^31
+    (A9; it implies A19's (N + K + 1) * max(D) < 2^31) and max(capacity) +
+    max(demand) < 2^31."""
+    mx = int(ci.durations.max()) if ci.durations.size else 0
+    K = len(ci.capacities)
+    if int(ci.start_times.max()) + (ci.N + K + 1) * mx >= 2**31:
+        return False
+    return int(ci.capacities.max()) + int(ci.demand.max()) < 2**31
+
+
+def batch_sp_fits(ci: CompactInstance) -> bool:
+    """A19's LDS domain: 1..BATCH_SP_MAX_CUSTOMERS customers on a static matrix
+    whose (n, K) state fits BATCH_SP_LDS_BYTES with the auto team."""
+    from .core import vrp_batch_sp_lds
+    K = len(ci.capacities)
+    if ci.durations.shape[0] != 1 or not 1 <= ci.n <= BATCH_SP_MAX_CUSTOMERS or \
+            not 1 <= K <= SP_MAX_VEHICLES:
+        return False
+    return vrp_batch_sp_lds(ci.n, K) <= BATCH_SP_LDS_BYTES
+
+
+def batch_sp_launch(ctx: Context, cis, objective: str = "sum"):
+    """One upload and one vrp_batch_sp launch for compact instances of one
+    (N, K) (each passed batch_sp_guard and batch_sp_fits) -> (tours,
+    durations): per instance the n + K tour tokens and the K route
+    durations."""
+    import torch
+    N, K = cis[0].N, len(cis[0].capacities)
+    mats = np.empty((len(cis), N, N), dtype=np.int32)
+    dem = np.empty((len(cis), N), dtype=np.int32)
+    caps = np.empty((len(cis), K), dtype=np.int32)
+    for x, ci in enumerate(cis):
+        mats[x], dem[x], caps[x] = ci.durations[0], ci.demand, ci.capacities
+    tours, _, durs = ctx.vrp_batch_sp(torch.from_numpy(mats).to(ctx.dev),
+                                      torch.from_numpy(dem).to(ctx.dev),
+                                      torch.from_numpy(caps).to(ctx.dev),
+                                      OBJ_MAX if objective == "max" else OBJ_SUM)
+    return tours.cpu().tolist(), durs.cpu().tolist()
+
+
+def sp_result(ci: CompactInstance, tour, durs, with_unvisited: bool = False) -> dict:
+    """The VRP slot dict from A15's tour tokens (route 0, a separator 0, ...,
+    route K-1, 0, then the unserved customers) and the K route durations,
+    compact indices mapped back through ci.nodes."""
+    K = len(ci.capacities)
+    routes, at = [], 0
+    for _ in range(K):
+        end = tour.index(0, at)
+        routes.append([ci.nodes[c] for c in tour[at:end]])
+        at = end + 1
+    vehicles = [{"tour": [ci.nodes[0]] + r + [ci.nodes[0]], "duration": int(d)}
+                for r, d in zip(routes, durs)]
+    out = {"durationMax": int(max(durs)), "durationSum": int(sum(durs)), "vehicles": vehicles}
+    if with_unvisited:
+        out["unvisited"] = [ci.nodes[c] for c in tour[at:]]
+    return out
+
+
+_VRP_REQUEST_KEYS = ("durations", "locations", "capacities", "start_times", "ignored_customers",
+                     "completed_customers")
+
+
+def solve_vrp_batch(algorithm: str, requests, *, objective: str = "sum",
+                    with_unvisited: bool = False, device: int = 0) -> list:
+    """[solve_vrp(algorithm, *r, objective=objective, with_unvisited=...) for r
+    in requests], element for element, with the small requests sharing
+    launches.  `requests`: (durations, locations, capacities, start_times[,
+    ignored_customers, completed_customers]) tuples, or dicts with those keys.
+    Only "sp" has a batched kernel (spec A19).  Every request is compacted and
+    checked on the host before anything is launched; a bad one (hour-indexed,
+    more than SP_MAX_CUSTOMERS customers or SP_MAX_VEHICLES vehicles, the int32
+    guards) raises solve_vrp("sp")'s message prefixed with its index.  Requests
+    of 1..BATCH_SP_MAX_CUSTOMERS customers whose (n, K) fits the LDS
+    (batch_sp_fits) are grouped by (N, K), one upload and one vrp_batch_sp
+    launch per group, and their result dicts are built on the host from the
+    tour tokens and the route durations; no customer, 13..20 customers and
+    fleets beyond the LDS take solve_vrp("sp"), one by one."""
+    if algorithm != "sp":
+        raise ValueError(f'solve_vrp_batch: no batched kernel for algorithm {algorithm!r}; only '
+                         '"sp" (exact set partitioning) is batched')
+    reqs, cis = [], []
+    for x, r in enumerate(requests):
+        if isinstance(r, dict):
+            r = (r["durations"], r["locations"], r["capacities"], r["start_times"],
+                 r.get("ignored_customers", ()), r.get("completed_customers", ()))
+        r = tuple(r) + ((),) * (6 - len(r))
+        try:
+            ci = compact_vrp(*r[:6])
+            _check_sp(ci)
+            if not batch_sp_guard(ci):
+                mx = int(ci.durations.max()) if ci.durations.size else 0
+                if int(ci.start_times.max()) + (ci.N + len(ci.capacities) + 1) * mx >= 2**31:
+                    raise ValueError("start + (N+K+1)*max_duration overflows int32 (A9 guard)")
+                raise ValueError("capacity + demand overflows int32")
+        except ValueError as e:
+            raise ValueError(f"request {x}: {e}") from None
+        reqs.append(r[:6])
+        cis.append(ci)
+    single = dict(objective=objective, with_unvisited=with_unvisited)
+    if _remote() is not None:      # no local GPU: the GPU box answers each request
+        return [solve_vrp("sp", *r, **single) for r in reqs]
+    out = [None] * len(cis)
+    groups: dict = {}
+    for x, ci in enumerate(cis):
+        if batch_sp_fits(ci):
+            groups.setdefault((ci.N, len(ci.capacities)), []).append(x)
+        else:
+            out[x] = solve_vrp("sp", *reqs[x], device=device, **single)
+    if groups:
+        ctx = context(device)
+        for xs in groups.values():
+            tours, durs = batch_sp_launch(ctx, [cis[x] for x in xs], objective)
+            for x, tour, d in zip(xs, tours, durs):
+                out[x] = sp_result(cis[x], tour, d, with_unvisited)
     return out
 
 
