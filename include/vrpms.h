@@ -115,6 +115,28 @@ int vrpms_rows_to_words(vrpms_ctx* ctx, const uint8_t* d_rows, int64_t C, int32_
  * fit the LDS); -1 = no instance. */
 int vrpms_eval_path(vrpms_ctx* ctx, int32_t perm_bytes, int64_t ld, const void* d_perms);
 
+/* The data layouts vrpms_set_instance chose for the loaded instance, and
+ * whether the branch-free split (eval_cvrp_rows2 / eval_cvrp_words2, the
+ * packed SA / GA / ACO scorers) takes tours of n customers.  Host only:
+ * launches and copies nothing.  Fills out[0 .. VRPMS_LAYOUT_FIELDS), count >=
+ * VRPMS_LAYOUT_FIELDS:
+ *    0 use16        the matrix is also held as uint16 (max duration <= 65535)
+ *    1 tier         0 packed u64 matrix in LDS, 1 plain matrix in LDS, 2 L2
+ *    2 pack_w       width of the packed ret / out fields; 0 = no packed matrix
+ *    3 pref_S       width of the prefix-ret duration field; 0 = no such layout
+ *    4 pref_lim     (cap + 1) << pref_S, the uint32 bit pattern
+ *    5 uniform_cap  every vehicle has the same capacity
+ *    6 symmetric    hour slice 0 is symmetric
+ *    7 sym_all      every hour slice is symmetric
+ *    8 flex         some demand exceeds the smallest capacity (vehicle skipping)
+ *    9 fast         the branch-free split takes tours of n customers
+ *   10 ks           fast: bit position of its vehicle counter, else 0
+ *   11 B            fast: width of that counter (31 - ks), else 0
+ *   12 carry        fast: the fit test is the add's carry (every demand >= 1)
+ *   13 hour_minor   the hour-minor uint16 copy exists (H = 24, use16) */
+#define VRPMS_LAYOUT_FIELDS 14
+int vrpms_instance_layout(vrpms_ctx* ctx, int32_t n, int32_t* out, int32_t count);
+
 /* Context options (kernel-variant overrides for A/B tests and profiling).
  *   VRPMS_OPT_SPLIT_MODE: 0 = auto (branch-free prefix-ret split whenever its
  *   packed layout fits), 2 = force the branchy split in eval_cvrp_packed,

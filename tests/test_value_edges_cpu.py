@@ -1,0 +1,142 @@
+"""The premises of tests/value_edges.py, proved without a GPU: Python ints and
+oracle/spec.py only.  Each edge instance sits exactly on its threshold (and
+its partner one step past it), the Python model of the host's layout choice
+lands where the edge says, and enough tours of each batch -- a wavefront's
+worth -- reach the state the edge is about: a route closed at load == cap, a
+customer refused at cap + 1, the fleet exhausted, a route that fills the
+duration field, both key fields clamped."""
+import numpy as np
+import pytest
+
+import value_edges as ve
+from oracle import spec
+
+
+@pytest.mark.parametrize("name", list(ve.BUILDERS))
+def test_pair_sits_on_its_threshold(name):
+    inside, outside = ve.pair(name)
+    assert inside.quantity == inside.limit
+    if name == "e7":       # not a threshold: the same edge with and without zero demands
+        assert outside.quantity == outside.limit == inside.limit
+    else:
+        assert outside.quantity > outside.limit == inside.limit
+    assert ve.accepted(inside.inst) and not inside.refused
+    assert ve.accepted(outside.inst) == (not outside.refused)
+    for e in (inside, outside):
+        if e.refused:
+            continue
+        m = ve.model_layout(e.inst, e.n)
+        for k, v in e.expect.items():
+            assert m[k] == v, (e.name, k, m[k], v)
+        assert (e.P is not None) or (e.Psep is not None)
+        for P, n in ((e.P, e.n), (e.Psep, e.n + e.n_sep)):
+            if P is None:
+                continue
+            rows = P[:, :n].astype(np.int64)
+            # every tour is a permutation of the customers it uses plus its separators
+            if n >= e.inst.n:
+                want = np.concatenate([np.zeros(n - e.inst.n, dtype=np.int64),
+                                       np.arange(1, e.inst.N)])
+                assert (np.sort(rows, axis=1) == want).all(), e.name
+                assert (P[:, n:] == 0).all()
+
+
+def test_governing_quantities_from_the_instances():
+    """The same equalities recomputed from the instance data alone."""
+    s = ve.stats
+    for name in ("e1_tsp", "e1_cvrp", "e1_td"):
+        i, o = ve.pair(name)
+        assert (s(i.inst)["max_dur"], s(o.inst)["max_dur"]) == (65535, 65536)
+    for w, md in ve.E2_SPLITS:
+        i, o = ve.pair(f"e2_w{w}")
+        for e, total in ((i, 32), (o, 33)):
+            st = s(e.inst)
+            assert 2 * ve.bits_for(st["max_dur"]) + ve.bits_for(st["max_dem"]) == total
+        st, D, dem = s(i.inst), i.inst.durations[0], i.inst.demand
+        assert st["max_dur"] == 2**w - 1 and st["max_dem"] == md
+        # one customer carries all three packed fields full at once
+        assert D[1, 0] == D[0, 1] == 2**w - 1 and dem[1] == 2**ve.bits_for(md) - 1
+    i, o = ve.pair("e3")
+    for e, v in ((i, 2**32 - 2**19), (o, 2**32)):
+        st = s(e.inst)
+        assert ve.field_bits((e.inst.N + 1) * st["max_dur"]) == 19
+        assert (st["cap0"] + st["max_dem"] + 1) << 19 == v
+    assert i.expect["pref_lim"] >= 2**31            # bit 31 of lim (and of acc) in use
+    for name in ("e4", "e4_max", "e7"):
+        i, o = ve.pair(name)
+        for e, v in ((i, 2**31), (o, 2**31 + 2**19 if name != "e7" else 2**31)):
+            st = s(e.inst)
+            assert ve.field_bits((e.inst.N + 1) * st["max_dur"]) == 19
+            assert (st["cap0"] + st["max_dem"] + 3) << 19 == v
+    i, o = ve.pair("e7")
+    assert s(i.inst)["min_dem"] == 1 and s(o.inst)["min_dem"] == 0
+    for name in ("e5", "e5_asym"):
+        i, o = ve.pair(name)
+        assert ve.field_bits((i.inst.N + 1) * s(i.inst)["max_dur"]) == 19
+        assert (i.inst.N + 1) * (s(i.inst)["max_dur"] + 1) >= 2**19
+        assert ve.field_bits((o.inst.N + 1) * s(o.inst)["max_dur"]) == 20
+    D = ve.pair("e5_asym")[0].inst.durations[0]
+    md = int(D.max())
+    assert min(int(D[a, b] + D[b, 0] - D[a, 0]) for a in range(1, 64) for b in range(1, 64)
+               if a != b) == -md
+    for name in ("e6_fleet", "e6_tokens"):
+        i, o = ve.pair(name)
+        for e in (i, o):
+            ks = ve.field_bits((e.n + e.inst.K + 1) * s(e.inst)["max_dur"])
+            assert 31 - ks == 8
+        assert 2**8 == max(i.inst.K, i.n) + 1 and 2**8 == max(o.inst.K, o.n)
+    i, o = ve.pair("e8_time")
+    for e, v in ((i, 2**31 - 1), (o, 2**31)):
+        assert s(e.inst)["max_start"] + (e.inst.N + e.inst.K + 1) * s(e.inst)["max_dur"] == v
+    i, o = ve.pair("e8_hour")
+    for e, v in ((i, 2**31 - 1), (o, 2**31)):
+        assert e.inst.H == 24
+        assert s(e.inst)["max_start"] + (e.inst.N + e.inst.K + 1) * s(e.inst)["max_dur"] == v
+    for name in ("e8_cap", "e8_het"):
+        i, o = ve.pair(name)
+        for e, v in ((i, 2**31 - 1), (o, 2**31)):
+            assert s(e.inst)["max_cap"] + s(e.inst)["max_dem"] == v
+    i, _ = ve.pair("e8_het")
+    assert s(i.inst)["min_cap"] == 1 and len(set(i.inst.capacities.tolist())) > 1
+    i, o = ve.pair("e9")
+    assert i.inst.N >= 258 and i.P.dtype == np.uint16 and i.inst.K == 1
+    assert int(i.inst.capacities[0]) == 1 and (i.inst.demand[1:] == 1).all()
+
+
+@pytest.mark.parametrize("name,side", ve.SIDES, ids=ve.SIDE_IDS)
+def test_tours_reach_the_edge(name, side):
+    e = ve.pair(name)[side]
+    if e.refused or not e.needs:
+        return
+    P, n = (e.P, e.n) if e.P is not None else (e.Psep, e.n + e.n_sep)
+    facts = [ve.tour_facts(e.inst, [int(x) for x in row[:n]]) for row in P]
+    count = {k: sum(bool(f[k]) for f in facts) for k in ("close", "refuse", "exhaust")}
+    S = ve.field_bits((e.inst.N + 1) * ve.stats(e.inst)["max_dur"])
+    count["saturate"] = sum(10 * f["longest"] >= 9 * 2**S for f in facts)
+    count["clamp"] = sum(f["sum"] > spec.KEY_CLAMP and f["max"] > spec.KEY_CLAMP for f in facts)
+    count["unv"] = sum(f["unv"] == e.quantity for f in facts)
+    for need in e.needs:
+        assert count[need] >= ve.WAVE, (e.name, need, count)
+    st = ve.stats(e.inst)
+    if "exhaust" in e.needs and st["max_dem"] <= st["cap0"]:    # (an oversized customer exhausts it)
+        # ... and a wavefront's worth does not, so both outcomes share wavefronts
+        assert len(facts) - count["exhaust"] >= ve.WAVE, (e.name, count)
+    if e.Psep is not None and e.P is not None:
+        assert e.n_sep > 0 and (np.sort(e.Psep[:, :e.n + e.n_sep], axis=1)[:, e.n_sep - 1] == 0).all()
+
+
+def test_small_search_cases_sit_on_the_same_thresholds():
+    md = 2**22 - 2
+    for kind, plus, v in (("e4_in", 3, 2**31), ("e4_out", 3, 2**31 + 2**8),
+                          ("e3_in", 1, 2**32 - 2**8)):
+        inst = ve.small(kind)
+        st = ve.stats(inst)
+        assert inst.N == 13 and st["max_dur"] == 15 and st["max_dem"] == md <= st["cap0"]
+        assert ve.field_bits((inst.N + 1) * st["max_dur"]) == 8
+        assert (st["cap0"] + md + plus) << 8 == v
+        m = ve.model_layout(inst)
+        assert m["pack_w"] == 4 and m["pref_S"] == 8 and m["fast"] == (kind == "e4_in")
+        assert int(inst.demand.sum()) > 2 * st["cap0"]       # capacity closes routes
+    inst = ve.small("e4_in")
+    f = ve.tour_facts(inst, [1, 5, 6, 2, 3, 4, 7, 8, 9, 10, 11, 12])
+    assert f["close"] and f["refuse"]

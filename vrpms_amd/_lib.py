@@ -81,6 +81,7 @@ SIGNATURES = {
     "vrpms_set_instance": (_c.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp]),
     "vrpms_eval": (_c.c_int, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
     "vrpms_eval_path": (_c.c_int, [_vp, _i32, _i64, _vp]),
+    "vrpms_instance_layout": (_c.c_int, [_vp, _i32, _vp, _i32]),
     "vrpms_eval_words": (_c.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
     "vrpms_rows_to_words": (_c.c_int, [_vp, _vp, _i64, _i32, _i64, _vp, _vp]),
     "vrpms_set_option": (_c.c_int, [_vp, _i32, _i32]),

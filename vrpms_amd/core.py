@@ -228,6 +228,23 @@ class Context:
         return self.lib.vrpms_eval_path(self._ctx, perm_dtype_bytes(perms), perms.shape[-1],
                                         perms.data_ptr())
 
+    LAYOUT_FIELDS = ("use16", "tier", "pack_w", "pref_S", "pref_lim", "uniform_cap", "symmetric",
+                     "sym_all", "flex", "fast", "ks", "B", "carry", "hour_minor")
+
+    def instance_layout(self, n: int | None = None) -> dict:
+        """The layouts vrpms_set_instance chose and whether the branch-free
+        split takes tours of n customers (default N - 1): the fields of
+        vrpms_instance_layout by name, flags as bool, pref_lim as uint32."""
+        out = (ctypes.c_int32 * len(self.LAYOUT_FIELDS))()
+        check(self.lib.vrpms_instance_layout(self._ctx, self.N - 1 if n is None else int(n), out,
+                                             len(out)))
+        d = dict(zip(self.LAYOUT_FIELDS, (int(x) for x in out)))
+        d["pref_lim"] &= 0xFFFFFFFF
+        for k in ("use16", "uniform_cap", "symmetric", "sym_all", "flex", "fast", "carry",
+                  "hour_minor"):
+            d[k] = bool(d[k])
+        return d
+
     def decode(self, perm, n: int | None = None):
         """Vehicle of each tour position and per-vehicle durations (host lists)."""
         torch = _torch()

@@ -10,6 +10,7 @@
 
 #include "common.hpp"
 #include "ctx.hpp"
+#include "split.hpp"
 
 namespace vrpms {
 
@@ -445,6 +446,26 @@ int vrpms_set_instance(vrpms_ctx* ctx, int32_t problem, const int32_t* d_dur, in
   }
   VRPMS_HIP(hipStreamSynchronize(s));
   ctx->has_instance = true;
+  return VRPMS_OK;
+}
+
+// The layout decisions above and fast_split_params' verdict for tours of n
+// customers, read back for tests (order: include/vrpms.h).  Host only.
+int vrpms_instance_layout(vrpms_ctx* ctx, int32_t n, int32_t* out, int32_t count) {
+  if (!ctx) return fail(VRPMS_EINVAL, "vrpms_instance_layout: ctx is NULL");
+  if (!ctx->has_instance) return fail(VRPMS_ESTATE, "vrpms_instance_layout: no instance loaded");
+  if (!out || count < VRPMS_LAYOUT_FIELDS || n < 0)
+    return fail(VRPMS_EINVAL, "vrpms_instance_layout: need n >= 0 and room for " +
+                                  std::to_string(VRPMS_LAYOUT_FIELDS) + " fields");
+  const Instance& in = ctx->inst;
+  FastSplit f{};
+  const bool fast = fast_split_params(ctx, n, &f);
+  const int32_t v[VRPMS_LAYOUT_FIELDS] = {
+      in.use16, in.tier, in.pack64 ? in.pack_w : 0, in.pack64p ? in.pref_S : 0,
+      (int32_t)(in.pack64p ? in.pref_lim : 0u), in.uniform_cap, in.symmetric, in.sym_all,
+      in.problem == VRPMS_CVRP && in.min_cap < in.max_dem, fast, fast ? (int32_t)f.ks : 0,
+      fast ? 31 - (int32_t)f.ks : 0, fast && f.carry, in.mat16h != nullptr};
+  std::copy(v, v + VRPMS_LAYOUT_FIELDS, out);
   return VRPMS_OK;
 }
 
