@@ -461,6 +461,37 @@ int vrpms_vrp_batch_sp(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_d
                        int32_t team, int16_t* d_tours, uint64_t* d_keys, int32_t* d_durs,
                        void* stream);
 
+/* Throughput mode of the exact time-dependent TSP: R
+ * independent TSP requests of one node count N, 2 <= N <= 12 (n = N - 1
+ * customers, node 0 the start node), and one hour count H (1 or 24), each with
+ * its own int32 [H][N][N] matrix (d_mats [R][H][N][N], non-negative entries),
+ * start time (d_start [R], minutes, >= 0) and horizon (d_horizon [R], minutes,
+ * >= 0).  A request's whole time-expanded table -- n 2^(n-1) rows of W hour
+ * words -- lives in LDS next to the matrix slices its words can use: a team of
+ * `team` threads per request (0 = the measured n -> T table, raised until the
+ * workgroup's 256 / T requests fit a fifth of a CU's LDS; or 16, 32, 64, 128,
+ * 256: the answers do not depend on it), 256 / team requests per workgroup,
+ * one launch for all R.  W,
+ * 1 <= W <= 512, is the launch's row width in hour words; W at least every
+ * request's (start % 60 + horizon) / 60 + 1 is the caller's promise.  A
+ * request's effective horizon is min(horizon, 60 W - 1 - start % 60): a
+ * smaller W can prune an answer but never leaves the request's rows.
+ * vrpms_tsp_batch_tdp_lds gives the launch's dynamic-LDS bytes for (n, H, W,
+ * team) (host only, no context); a launch that needs more than the device has
+ * is refused with that byte count in the message.  Out: d_tours [R][N-1] and
+ * d_keys [R], per request exactly what vrpms_tsp_tdp_run writes for that
+ * matrix, start and (effective) horizon: the A8 key of the optimum among tours
+ * of at most that many minutes and A16's tie-ruled tour, or UINT64_MAX and an
+ * all-zero tour when no tour fits.  No instance and no workspace needed;
+ * asynchronous on `stream`.  R = 0 launches nothing.  VRPMS_EINVAL, with
+ * nothing launched and nothing written, for a NULL ctx, R < 0, N outside
+ * 2..12, H other than 1 or 24, W outside 1..512, an unknown team, a NULL
+ * buffer with R > 0, or an LDS need above the device's. */
+int vrpms_tsp_batch_tdp_lds(int32_t n, int32_t H, int32_t W, int32_t team, uint64_t* bytes);
+int vrpms_tsp_batch_tdp(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_start,
+                        const int32_t* d_horizon, int32_t R, int32_t N, int32_t H, int32_t W,
+                        int32_t team, int16_t* d_tours, uint64_t* d_keys, void* stream);
+
 /* ------------------------------------------------------------------------
  * Populations and the island model.  A pool is a set of
  * tours with their A8 keys: SA chains, a GA population ([islands][pop],

@@ -50,6 +50,23 @@ def vrp_batch_sp_lds(n: int, K: int, team: int = 0) -> int:
     return int(nbytes.value)
 
 
+def tsp_batch_tdp_lds(n: int, H: int, W: int, team: int = 0) -> int:
+    """vrpms_tsp_batch_tdp_lds: the dynamic-LDS bytes of a tsp_batch_tdp
+    launch for n customers, H hour slices (1 or 24), rows of W hour words and
+    `team` threads per request (0 = the auto team).  Host only: needs the
+    library, no GPU."""
+    nbytes = ctypes.c_uint64()
+    check(_lib.load().vrpms_tsp_batch_tdp_lds(int(n), int(H), int(W), int(team),
+                                              ctypes.byref(nbytes)))
+    return int(nbytes.value)
+
+
+def tdp_words(start: int, horizon: int) -> int:
+    """Hour words of one A16 row: the words from the start's hour to the one
+    of start + horizon."""
+    return (int(start) % 60 + int(horizon)) // 60 + 1
+
+
 class Context:
     """One solver context on one GPU (``vrpms_ctx_create``)."""
 
@@ -473,6 +490,57 @@ class Context:
                                           tours.data_ptr(), keys.data_ptr(), durs.data_ptr(),
                                           self.stream()))
         return tours, keys, durs
+
+    def tsp_batch_tdp(self, mats, starts, horizons, W: int | None = None, team: int = 0):
+        """Exact time-dependent optimum of every request in one launch (spec
+        A20, at most 11 customers, all requests of one N and H): mats int32
+        [R][H][N][N] (H = 1 or 24; [R][N][N] is taken as H = 1), starts and
+        horizons [R] (host sequences, numpy arrays or tensors; minutes, >= 0;
+        int32 tensors on the device together with an explicit `W` are passed
+        through as they are) -> (tours int16 [R][N-1], keys int64 [R]), per request what tsp_tdp
+        returns for that matrix, start and horizon: all-ones key and a zero
+        tour where no tour fits the horizon.  `W`: the launch's row width in
+        hour words, default the largest tdp_words(start, horizon) of the
+        batch, computed on the host; a smaller one can prune an answer (the
+        effective horizon is min(horizon, 60 W - 1 - start % 60)).  `team`:
+        threads per request, 0 = auto, or 16, 32, 64, 128, 256 (the answers do
+        not depend on it).  Non-negative durations are the caller's promise.
+        Asynchronous on the current stream."""
+        torch = _torch()
+        if mats.dim() == 3:
+            mats = mats.unsqueeze(1)
+        if mats.device != self.dev or mats.dim() != 4 or mats.shape[2] != mats.shape[3] or \
+                mats.dtype != torch.int32 or not mats.is_contiguous():
+            raise ValueError(f"mats must be a contiguous int32 [R][H][N][N] tensor on {self.dev}")
+        R, H, N, _ = mats.shape
+        on_device = [isinstance(t, torch.Tensor) and t.device == self.dev and
+                     t.dtype == torch.int32 and t.shape == (R,) and t.is_contiguous()
+                     for t in (starts, horizons)]
+        if all(on_device) and W is not None:
+            d_st, d_hz = starts, horizons      # uploaded and checked by the caller
+        else:
+            host = []
+            for name, t in (("starts", starts), ("horizons", horizons)):
+                a = t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+                a = a.astype(np.int64).reshape(-1)
+                if a.shape[0] != R:
+                    raise ValueError(f"{name} must have one entry per request ({R})")
+                if R and (a.min() < 0 or a.max() >= 2**31):
+                    raise ValueError(f"{name} must be non-negative int32 minutes")
+                host.append(a)
+            st, hz = host
+            if R and int((st + hz).max()) >= 2**31:
+                raise ValueError("start + horizon must stay below 2^31")
+            if W is None:
+                W = int(((st % 60 + hz) // 60 + 1).max()) if R else 1
+            d_st = torch.from_numpy(st.astype(np.int32)).to(self.dev)
+            d_hz = torch.from_numpy(hz.astype(np.int32)).to(self.dev)
+        tours = torch.empty((R, max(N - 1, 1)), dtype=torch.int16, device=self.dev)
+        keys = torch.empty(R, dtype=torch.int64, device=self.dev)
+        check(self.lib.vrpms_tsp_batch_tdp(self._ctx, mats.data_ptr(), d_st.data_ptr(),
+                                           d_hz.data_ptr(), R, N, H, int(W), int(team),
+                                           tours.data_ptr(), keys.data_ptr(), self.stream()))
+        return tours, keys
 
     def set_batch_dp_team(self, T: int):
         """Threads per request of tsp_batch_dp: 0 = auto (the n -> T table),

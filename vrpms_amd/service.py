@@ -412,6 +412,72 @@ class ExactVrpBatcher(TspBatcher):
             return solver.batch_sp_launch(solver.context(dev), cis, key[2])
 
 
+class ExactTdpBatcher(TspBatcher):
+    """Coalesces concurrent exact time-dependent small-TSP requests -- ("tsp",
+    "tdp") on the inline route -- into one `tsp_batch_tdp` launch per (node
+    count, hour count) (spec A20: each request's time-expanded table in LDS).
+    The queue, the window, the device round-robin and the error fan-out are
+    TspBatcher's; a job carries its own upper bound, and the launch takes the
+    group's bounds next to its instances.  A batched answer does not depend on
+    the batch: it is the unbatched answer of the same request."""
+
+    def __init__(self, app, window_s: float = 0.005, max_batch: int = 16384, launch=None):
+        super().__init__(app, window_s, steps=0, max_batch=max_batch, launch=launch)
+
+    @classmethod
+    def accepts(cls, ci, bound=None) -> bool:
+        """Requests inside A20's LDS domain for their bound (solver.
+        batch_tdp_fits: 1..11 customers, static or 24 slices, the row width
+        the bound implies) that pass the A9 int32 guard vrpms_set_instance
+        applies on the unbatched path; anything else takes the unbatched path,
+        so both paths share one error contract."""
+        from . import solver
+        return solver.batch_tdp_fits(ci, bound) and solver.batch_dp_guard(ci)
+
+    @staticmethod
+    def group_key(job):
+        return job["ci"].N, job["ci"].durations.shape[0]
+
+    def solve(self, ci, bound) -> dict:
+        """Blocks until the request's launch finished -> the TSP slot dict."""
+        from . import solver
+        job = {"ci": ci, "bound": int(bound), "done": threading.Event()}
+        self._wait(job)
+        duration = job.get("duration")
+        if duration is None and not any(job["tour"]) and ci.n > 0:
+            raise ValueError(f"no tour within upper_bound = {int(bound)} minutes")
+        if duration is None:  # a launch that returns tours only (tests' stand-in launches)
+            duration = solver._td_duration(ci, job["tour"])
+        path = [0] + list(job["tour"]) + [0]
+        return {"duration": duration, "vehicle": [ci.nodes[c] for c in path]}
+
+    def _run(self, key, jobs, dev):
+        try:
+            args = (key, [j["ci"] for j in jobs], [j["bound"] for j in jobs])
+            res = self._launch(*args, dev) if len(self.devices) > 1 else self._launch(*args)
+            tours, durs = res if isinstance(res, tuple) else (res, None)
+            with self._cv:
+                self.launches += 1
+                self.requests += len(jobs)
+                self.per_device[dev] += len(jobs)
+            for x, (j, t) in enumerate(zip(jobs, tours)):
+                j["tour"] = t
+                if durs is not None and durs[x] is not None:
+                    j["duration"] = durs[x]
+        except Exception as e:         # every waiter of the group sees it
+            for j in jobs:
+                j["error"] = e
+        for j in jobs:
+            j["done"].set()
+
+    def _gpu_launch(self, key, cis, bounds, device=None):
+        """-> (tours, durations) on `device` (default: the app's first)."""
+        from . import solver
+        dev = self.devices[0] if device is None else device
+        with self.app.locks[dev]:
+            return solver.batch_tdp_launch(solver.context(dev), cis, bounds)
+
+
 # ---------------------------------------------------------------------------
 # the endpoint logic
 # ---------------------------------------------------------------------------
@@ -433,7 +499,7 @@ class App:
                  solve=None, batch_tsp: bool = False, batch_window_s: float = 0.005,
                  batch_steps: int = 2000, batch_launch=None, devices=None,
                  island_min_n: int = 150, batch_exact: bool = False, batch_exact_launch=None,
-                 batch_exact_vrp_launch=None):
+                 batch_exact_vrp_launch=None, batch_exact_tdp_launch=None):
         self.store = store
         self.devices = list(devices) if devices else [device]
         self.device = self.devices[0]
@@ -453,6 +519,10 @@ class App:
         # and exact small-fleet VRP requests vrp_batch_sp launches
         self.exact_vrp_batcher = ExactVrpBatcher(self, batch_window_s,
                                                  launch=batch_exact_vrp_launch) \
+            if batch_exact else None
+        # and exact time-dependent small-TSP requests tsp_batch_tdp launches
+        self.exact_tdp_batcher = ExactTdpBatcher(self, batch_window_s,
+                                                 launch=batch_exact_tdp_launch) \
             if batch_exact else None
 
     def _scheduled(self, problem, algorithm, params, knobs, locations, durations):
@@ -509,6 +579,18 @@ class App:
         ci = solver.compact_vrp(durations, locations, params["capacities"], params["start_times"],
                                 params["ignored_customers"], params["completed_customers"])
         return ci if self.exact_vrp_batcher.accepts(ci) else None
+
+    def _batched_tdp(self, params, durations, upper_bound=None):
+        """(compact instance, bound) when this ("tsp", "tdp") request rides the
+        exact time-dependent batcher, else None.  A request outside A16's
+        domain raises here what the unbatched path raises for it."""
+        if self.exact_tdp_batcher is None:
+            return None
+        from . import solver
+        ci = solver.compact_tsp(durations, params["customers"], params["start_node"],
+                                params["start_time"] or 0)
+        bound = solver.batch_tdp_bound(ci, upper_bound)
+        return (ci, bound) if self.exact_tdp_batcher.accepts(ci, bound) else None
 
     def _gpu_solve(self, problem, algorithm, params, knobs, locations, durations):
         """knobs may carry "seed", "time_limit" and "objective" (the /solve
@@ -650,8 +732,13 @@ class App:
                 if (problem, algorithm) == ("tsp", "dp") and self.exact_batcher is not None else None
             vrp_ci = self._batched_vrp(params, vals["durations"], locations) \
                 if (problem, algorithm) == ("vrp", "sp") else None
+            tdp = self._batched_tdp(params, vals["durations"],
+                                    knobs["inline"].get("upper_bound")) \
+                if (problem, algorithm) == ("tsp", "tdp") else None
             if ci is not None:
                 result = self.exact_batcher.solve(ci)
+            elif tdp is not None:
+                result = self.exact_tdp_batcher.solve(*tdp)
             elif vrp_ci is not None:
                 result = self.exact_vrp_batcher.solve(vrp_ci, knobs.get("objective", "sum"))
             else:
@@ -767,7 +854,10 @@ def main(argv=None):
                          "/api/tsp/bf, static matrix, 1..12 customers) into tsp_batch_dp "
                          "launches, and exact small-fleet VRP requests (/solve/vrp/sp, static "
                          "matrix, 1..12 customers, a fleet that fits the LDS) into vrp_batch_sp "
-                         "launches; the answers equal the unbatched ones")
+                         "launches, and exact time-dependent small-TSP requests (/solve/tsp/tdp, "
+                         "static or hour-indexed matrix, 1..11 customers, an upper bound whose "
+                         "hour words fit the LDS) into tsp_batch_tdp launches; the answers equal "
+                         "the unbatched ones")
     ap.add_argument("--batch-window-ms", type=float, default=5.0)
     ap.add_argument("--batch-steps", type=int, default=2000)
     ap.add_argument("--workers", type=int, default=0,

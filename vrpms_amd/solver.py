@@ -79,6 +79,13 @@ BATCH_SP_LDS_BYTES = 160 * 1024
 TDP_MAX_CUSTOMERS = 20
 TDP_MAX_WORKSPACE = 16 << 30
 TDP_MAX_WORDS = 512
+# batched time-expanded DP (A20): one request's compact table, n 2^(n-1) rows of
+# W hour words, has to fit one CU's LDS next to the matrix slices its words use
+# (vrpms_tsp_batch_tdp_lds gives the bytes for (n, H, W)): W = 1 at 11
+# customers, up to 3 at 10, 8 at 9, 19 at 8; 12 customers never fit (196,608 B
+# at W = 1).  Other requests of a batch take the single-request path
+BATCH_TDP_MAX_CUSTOMERS = 11
+BATCH_TDP_LDS_BYTES = 160 * 1024
 # time-expanded partition DP (A17, VRP, static or hour-indexed, per-vehicle
 # start times): G A16 tables, one per distinct start time, each followed by the
 # route kernel, then A15's K - 1 partition layers.  The kernel accepts 20
@@ -521,20 +528,141 @@ def batch_dp_launch(ctx: Context, cis):
     return tours, durs
 
 
+def batch_tdp_bound(ci: CompactInstance, upper_bound=None):
+    """_check_tdp for a request that may ride a tsp_batch_tdp launch -> the
+    bound its row width follows from.  One customer has the single path's
+    trivial answer whatever `upper_bound` says, so its bound is its one tour's
+    duration; no customer has none."""
+    bound = _check_tdp(ci, upper_bound)
+    if ci.n == 1:
+        bound = runners.nearest_neighbour_duration(ci.durations, 1, int(ci.start_times[0]))
+    return bound
+
+
+def batch_tdp_fits(ci: CompactInstance, bound) -> bool:
+    """A20's domain: 1..BATCH_TDP_MAX_CUSTOMERS customers and one request of
+    (n, H, W) -- W the hour words of `bound` from the request's start -- within
+    BATCH_TDP_LDS_BYTES.  Needs the library, no GPU."""
+    from .core import tdp_words, tsp_batch_tdp_lds
+    if ci.problem != TSP or not 1 <= ci.n <= BATCH_TDP_MAX_CUSTOMERS or bound is None:
+        return False
+    H = ci.durations.shape[0]
+    start = int(ci.start_times[0])
+    W = tdp_words(start, bound)
+    if H not in (1, 24) or W > TDP_MAX_WORDS or start + int(bound) >= 2**31:
+        return False
+    return tsp_batch_tdp_lds(ci.n, H, W) <= BATCH_TDP_LDS_BYTES
+
+
+def _td_duration(ci: CompactInstance, tour) -> int:
+    """The tour's duration under the A3 clock, on the host."""
+    D, H = ci.durations, ci.durations.shape[0]
+    t0 = t = int(ci.start_times[0])
+    path = [0] + list(tour) + [0]
+    for a, b in zip(path, path[1:]):
+        t += int(D[(t // 60) % H][a][b])
+    return t - t0
+
+
+def batch_tdp_launch(ctx: Context, cis, bounds):
+    """One upload and one tsp_batch_tdp launch for compact instances of one
+    (N, H) (each passed batch_dp_guard and batch_tdp_fits with its bound), W
+    the largest of their row widths -> (tours, durations), one row per
+    instance; the duration is None where no tour fits the request's bound.  A
+    duration is the key's primary field, exact below the 2^28 - 1 clamp; a
+    clamped one is summed on the host."""
+    import torch
+    N, H = cis[0].N, cis[0].durations.shape[0]
+    host = np.empty((len(cis), H, N, N), dtype=np.int32)
+    for x, ci in enumerate(cis):
+        host[x] = ci.durations
+    starts = np.array([int(ci.start_times[0]) for ci in cis], dtype=np.int64)
+    tours, keys = ctx.tsp_batch_tdp(torch.from_numpy(host).to(ctx.dev), starts,
+                                    np.array([int(b) for b in bounds], dtype=np.int64))
+    tours, keys = tours.cpu().tolist(), keys.cpu().tolist()
+    clamp = (1 << 28) - 1
+    durs = []
+    for ci, tour, k in zip(cis, tours, keys):
+        if k == -1:
+            durs.append(None)
+            continue
+        d = (k >> 28) & clamp
+        durs.append(_td_duration(ci, tour) if d == clamp else int(d))
+    return tours, durs
+
+
+def _solve_tdp_batch(requests, device: int) -> list:
+    """solve_tsp_batch("tdp")."""
+    reqs, cis, bounds, knobs = [], [], [], []
+    for x, r in enumerate(requests):
+        if isinstance(r, dict):
+            r = (r["durations"], r["customers"], r["start_node"], r.get("start_time", 0),
+                 r.get("upper_bound"))
+        r = tuple(r)
+        r = r + (0,) * (4 - len(r)) if len(r) < 4 else r
+        ub = r[4] if len(r) > 4 else None
+        try:
+            ci = compact_tsp(*r[:4])
+            bound = batch_tdp_bound(ci, ub)
+            if not batch_dp_guard(ci):
+                raise ValueError("start + (N+K+1)*max_duration overflows int32 (A9 guard)")
+        except ValueError as e:
+            raise ValueError(f"request {x}: {e}") from None
+        reqs.append(r[:4])
+        cis.append(ci)
+        bounds.append(bound)
+        knobs.append({} if ub is None else {"upper_bound": ub})
+    if _remote() is not None:      # no local GPU: the GPU box answers each request
+        return [solve_tsp("tdp", *r, **k) for r, k in zip(reqs, knobs)]
+    out = [None] * len(cis)
+    groups: dict = {}
+    for x, ci in enumerate(cis):
+        if batch_tdp_fits(ci, bounds[x]):
+            groups.setdefault((ci.N, ci.durations.shape[0]), []).append(x)
+        else:
+            out[x] = solve_tsp("tdp", *reqs[x], device=device, **knobs[x])
+    if groups:
+        ctx = context(device)
+        for xs in groups.values():
+            tours, durs = batch_tdp_launch(ctx, [cis[x] for x in xs], [bounds[x] for x in xs])
+            for x, tour, dur in zip(xs, tours, durs):
+                if dur is None:
+                    raise ValueError(f"request {x}: no tour within upper_bound = "
+                                     f"{int(bounds[x])} minutes")
+                nodes = cis[x].nodes
+                out[x] = {"duration": dur,
+                          "vehicle": [nodes[0]] + [nodes[c] for c in tour] + [nodes[0]]}
+    return out
+
+
 def solve_tsp_batch(algorithm: str, requests, *, device: int = 0) -> list:
     """[solve_tsp(algorithm, *r) for r in requests], element for element, with
     the small requests sharing launches.  `requests`: (durations, customers,
-    start_node, start_time) tuples, or dicts with those keys.  Only "dp" has a
-    batched kernel (spec A18).  Every request is compacted and checked on the
-    host before anything is launched; a bad one (hour-indexed, more than
-    DP_MAX_CUSTOMERS customers, A9 guard) raises solve_tsp("dp")'s message
-    prefixed with its index.  Requests of 2..BATCH_DP_MAX_CUSTOMERS customers
-    are grouped by node count, one upload and one tsp_batch_dp launch per
-    group; none or one customer take solve_tsp's trivial path, and 13..24
-    customers its single-request Held-Karp, one by one."""
+    start_node, start_time) tuples, or dicts with those keys.  "dp" (spec A18)
+    and "tdp" (spec A20) have batched kernels.  Every request is compacted and
+    checked on the host before anything is launched; a bad one raises
+    solve_tsp's message for that algorithm prefixed with its index.
+
+    "dp" (bad: hour-indexed, more than DP_MAX_CUSTOMERS customers, A9 guard):
+    requests of 2..BATCH_DP_MAX_CUSTOMERS customers are grouped by node count,
+    one upload and one tsp_batch_dp launch per group; none or one customer
+    take solve_tsp's trivial path, and 13..24 customers its single-request
+    Held-Karp, one by one.
+
+    "tdp" (static or hour-indexed; bad: more than TDP_MAX_CUSTOMERS customers,
+    a negative bound, a table or a row above the caps, A9 guard): a request may
+    carry a fifth tuple element or an "upper_bound" key, the knob of
+    solve_tsp("tdp") (default: the nearest-neighbour tour's duration).
+    Requests inside A20's LDS domain (batch_tdp_fits: 1..11 customers, the row
+    width the bound implies) are grouped by (node count, hour count), one
+    upload and one tsp_batch_tdp launch per group at the group's largest row
+    width; no customer, 12..20 customers and an (n, W) outside the LDS take
+    solve_tsp("tdp"), one by one."""
+    if algorithm == "tdp":
+        return _solve_tdp_batch(requests, device)
     if algorithm != "dp":
         raise ValueError(f'solve_tsp_batch: no batched kernel for algorithm {algorithm!r}; only '
-                         '"dp" (exact Held-Karp) is batched')
+                         '"dp" (exact Held-Karp) and "tdp" (exact time-expanded DP) are batched')
     reqs, cis = [], []
     for x, r in enumerate(requests):
         if isinstance(r, dict):
