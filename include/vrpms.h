@@ -492,6 +492,51 @@ int vrpms_tsp_batch_tdp(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_
                         const int32_t* d_horizon, int32_t R, int32_t N, int32_t H, int32_t W,
                         int32_t team, int16_t* d_tours, uint64_t* d_keys, void* stream);
 
+/* Throughput mode of the exact time-dependent VRP: R
+ * independent CVRP requests of one node count N, 2 <= N <= 12 (n = N - 1
+ * customers, node 0 the depot), one fleet size K, 1 <= K <= 64, one hour count
+ * H (1 or 24) and one objective, each with its own int32 [H][N][N] matrix
+ * (d_mats [R][H][N][N], non-negative entries), demands (d_demand [R][N], entry
+ * 0 ignored), capacities (d_cap [R][K], in vehicle order; they may differ or be
+ * 0), start times (d_start [R][K], minutes) and horizon (d_horizon [R],
+ * minutes: the bound on every single route).  G, 1 <= G <= K, is the launch's
+ * limit on the distinct start times of one request; W, 1 <= W <= 512, its row
+ * width in hour words, at least (start % 60 + horizon) / 60 + 1 for every
+ * vehicle's start by the caller's promise.  For a start s the effective
+ * horizon is min(horizon, 60 W - 1 - s % 60): a smaller W can prune an answer
+ * but never leaves the request's rows.  A request's whole state -- the
+ * time-expanded table (refilled per distinct start time and per route), the G
+ * route tables and the K partition layers -- lives in LDS: a team of `team`
+ * threads per request (0 = A20's n -> T table, raised until the workgroup's
+ * 256 / T requests fit a fifth of a CU's LDS; or 16, 32, 64, 128, 256: the
+ * answers do not depend on it, nor on G, W or the batch), 256 / team requests
+ * per workgroup, one launch for all R.  vrpms_vrp_batch_tdsp_lds gives the
+ * launch's dynamic-LDS bytes for (n, K, G, H, W, team) (host only, no
+ * context); a launch that needs more than the device has is refused with that
+ * byte count in the message.  The (N + K + 1) * max(D) + max(start) < 2^31
+ * guard (A9) and non-negative demands and capacities are the caller's
+ * promise.  Out: d_tours [R][N-1+K], d_keys [R] and d_durs [R][K], per request
+ * exactly what vrpms_vrp_tdsp_run writes for that instance and horizon -- A17's
+ * key, its tie-ruled tour (route 0, a separator 0, ..., route K-1, 0, then the
+ * unserved customers ascending) -- and the K route durations, unclamped, 0 for
+ * an empty route.  A request with more than G distinct start times, a negative
+ * start time or a negative horizon gets UINT64_MAX, an all-zero tour and
+ * durations of -1, and touches nothing else (A17 always has an answer, so all
+ * ones means "outside the launch's contract").  No instance and no workspace
+ * needed; asynchronous on `stream`.  R = 0 launches nothing.  VRPMS_EINVAL,
+ * with nothing launched and nothing written, checked in this order and also
+ * with R = 0: a NULL ctx, R < 0, N outside 2..12, K outside 1..64, G outside
+ * 1..K, H other than 1 or 24, W outside 1..512, an unknown objective, an
+ * unknown team; then, with R > 0, a NULL buffer or an LDS need above the
+ * device's. */
+int vrpms_vrp_batch_tdsp_lds(int32_t n, int32_t K, int32_t G, int32_t H, int32_t W, int32_t team,
+                             uint64_t* bytes);
+int vrpms_vrp_batch_tdsp(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_demand,
+                         const int32_t* d_cap, const int32_t* d_start, const int32_t* d_horizon,
+                         int32_t R, int32_t N, int32_t K, int32_t G, int32_t H, int32_t W,
+                         int32_t objective, int32_t team, int16_t* d_tours, uint64_t* d_keys,
+                         int32_t* d_durs, void* stream);
+
 /* ------------------------------------------------------------------------
  * Populations and the island model.  A pool is a set of
  * tours with their A8 keys: SA chains, a GA population ([islands][pop],

@@ -61,6 +61,17 @@ def tsp_batch_tdp_lds(n: int, H: int, W: int, team: int = 0) -> int:
     return int(nbytes.value)
 
 
+def vrp_batch_tdsp_lds(n: int, K: int, G: int, H: int, W: int, team: int = 0) -> int:
+    """vrpms_vrp_batch_tdsp_lds: the dynamic-LDS bytes of a vrp_batch_tdsp
+    launch for n customers, K vehicles, at most G distinct start times per
+    request, H hour slices (1 or 24), rows of W hour words and `team` threads
+    per request (0 = the auto team).  Host only: needs the library, no GPU."""
+    nbytes = ctypes.c_uint64()
+    check(_lib.load().vrpms_vrp_batch_tdsp_lds(int(n), int(K), int(G), int(H), int(W), int(team),
+                                               ctypes.byref(nbytes)))
+    return int(nbytes.value)
+
+
 def tdp_words(start: int, horizon: int) -> int:
     """Hour words of one A16 row: the words from the start's hour to the one
     of start + horizon."""
@@ -541,6 +552,74 @@ class Context:
                                            d_hz.data_ptr(), R, N, H, int(W), int(team),
                                            tours.data_ptr(), keys.data_ptr(), self.stream()))
         return tours, keys
+
+    def vrp_batch_tdsp(self, mats, demand, caps, starts, horizons, objective: int = OBJ_SUM,
+                       G: int | None = None, W: int | None = None, team: int = 0):
+        """Exact time-dependent VRP optimum of every request in one launch
+        (spec A21, at most 11 customers, all requests of one N, K, H and
+        objective): mats int32 [R][H][N][N] (H = 1 or 24; [R][N][N] is taken
+        as H = 1), demand int32 [R][N] (entry 0 ignored) and caps int32 [R][K]
+        on the device, starts [R][K] and horizons [R] (host sequences, numpy
+        arrays or tensors; minutes, >= 0; int32 tensors on the device
+        together with explicit `G` and `W` are passed through as they are)
+        -> (tours int16 [R][N-1+K], keys int64 [R], durs int32 [R][K]), per
+        request the tour and key vrp_tdsp returns for that instance and
+        horizon and its K route durations, unclamped.  `G`: the launch's
+        limit on one request's distinct start times, `W`: its row width in
+        hour words; both default to the batch's largest need, computed on
+        the host.  A request with more than G distinct starts gets an
+        all-ones key, a zero tour and durations of -1; a smaller W can prune
+        an answer (for a start s the effective horizon is min(horizon, 60 W -
+        1 - s % 60)).  `team`: threads per request, 0 = auto, or 16, 32, 64,
+        128, 256 (the answers do not depend on it).  The A9 guard and
+        non-negative durations, demands and capacities are the caller's
+        promise.  Asynchronous on the current stream."""
+        torch = _torch()
+        if mats.dim() == 3:
+            mats = mats.unsqueeze(1)
+        if mats.device != self.dev or mats.dim() != 4 or mats.shape[2] != mats.shape[3] or \
+                mats.dtype != torch.int32 or not mats.is_contiguous():
+            raise ValueError(f"mats must be a contiguous int32 [R][H][N][N] tensor on {self.dev}")
+        R, H, N, _ = mats.shape
+        for name, t, cols in (("demand", demand, N), ("caps", caps, None)):
+            if t.device != self.dev or t.dim() != 2 or t.shape[0] != R or t.dtype != torch.int32 or \
+                    not t.is_contiguous() or (cols is not None and t.shape[1] != cols):
+                raise ValueError(f"{name} must be a contiguous int32 [R][{'N' if cols else 'K'}] "
+                                 f"tensor on {self.dev}")
+        K = caps.shape[1]
+        on_device = [isinstance(t, torch.Tensor) and t.device == self.dev and
+                     t.dtype == torch.int32 and t.shape == shape and t.is_contiguous()
+                     for t, shape in ((starts, (R, K)), (horizons, (R,)))]
+        if all(on_device) and W is not None and G is not None:
+            d_st, d_hz = starts, horizons      # uploaded and checked by the caller
+        else:
+            st = starts.cpu().numpy() if isinstance(starts, torch.Tensor) else np.asarray(starts)
+            hz = horizons.cpu().numpy() if isinstance(horizons, torch.Tensor) else np.asarray(horizons)
+            st, hz = st.astype(np.int64), hz.astype(np.int64).reshape(-1)
+            if st.size != R * K:
+                raise ValueError(f"starts must have one row of {K} start times per request ({R})")
+            st = st.reshape(R, K)
+            if hz.shape[0] != R:
+                raise ValueError(f"horizons must have one entry per request ({R})")
+            if R and K and (min(st.min(), hz.min()) < 0 or max(st.max(), hz.max()) >= 2**31):
+                raise ValueError("starts and horizons must be non-negative int32 minutes")
+            if R and K and int((st.max(axis=1) + hz).max()) >= 2**31:
+                raise ValueError("start + horizon must stay below 2^31")
+            if W is None:
+                W = int(((st % 60 + hz[:, None]) // 60 + 1).max()) if R and K else 1
+            if G is None:
+                G = max((len(set(row)) for row in st.tolist()), default=1) if K else 1
+            d_st = torch.from_numpy(st.astype(np.int32)).to(self.dev)
+            d_hz = torch.from_numpy(hz.astype(np.int32)).to(self.dev)
+        tours = torch.empty((R, max(N - 1 + K, 1)), dtype=torch.int16, device=self.dev)
+        keys = torch.empty(R, dtype=torch.int64, device=self.dev)
+        durs = torch.empty((R, max(K, 1)), dtype=torch.int32, device=self.dev)
+        check(self.lib.vrpms_vrp_batch_tdsp(self._ctx, mats.data_ptr(), demand.data_ptr(),
+                                            caps.data_ptr(), d_st.data_ptr(), d_hz.data_ptr(), R, N,
+                                            K, int(G), H, int(W), int(objective), int(team),
+                                            tours.data_ptr(), keys.data_ptr(), durs.data_ptr(),
+                                            self.stream()))
+        return tours, keys, durs
 
     def set_batch_dp_team(self, T: int):
         """Threads per request of tsp_batch_dp: 0 = auto (the n -> T table),

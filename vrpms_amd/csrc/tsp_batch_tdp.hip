@@ -49,32 +49,16 @@
 #include "common.hpp"
 #include "ctx.hpp"
 #include "tsp_batch_dp.hpp"
+#include "tsp_batch_tdp.hpp"
 #include "tsp_dp.hpp"
 #include "tsp_tdp.hpp"
 
 namespace vrpms {
 
-// 0: owner thread per row at every W, 1: atomic OR at every W (the A/B builds
-// of tools/ab_build.py), 2: the launch picks by W -- owner rows below
-// kBatchTdpAtomicWords words, atomic OR from there (§4.3k: neither wins everywhere)
-#ifndef VRPMS_BATCH_TDP_FILL
-#define VRPMS_BATCH_TDP_FILL 2
-#endif
-constexpr int kBatchTdpFill = VRPMS_BATCH_TDP_FILL;
-static_assert(kBatchTdpFill >= 0 && kBatchTdpFill <= 2, "0: owner, 1: atomic OR, 2: by W");
-constexpr int kBatchTdpAtomicWords = 8;
-
-constexpr int kBatchTdpMaxN = 11;      // customers: n = 12 is 196,608 B of table at W = 1
-constexpr uint64_t kBatchTdpMask60 = (1ull << 60) - 1;
-
-// threads per request by n (index n), before the LDS has its say: the fastest
-// T of tools/batch_tdp_rate.py --teams 16,32,64,128,256 at each n and W = 1
-// (DESIGN.md §4.3k has the measurements; n = 1 is not measured and takes
-// n = 2's).  The work of a request grows with W, and so does its table: the
-// auto team is the next larger T whose 256 / T requests fit kBatchTdpTeamLds,
-// a fifth of the CU's LDS, so that five workgroups share a CU -- at every
-// measured (n, W) the fastest T or within 7 % of it -- and 256 if none does
-constexpr int kBatchTdpTeam[kBatchTdpMaxN + 1] = {16, 16, 16, 16, 16, 16, 32, 32, 128, 256, 256, 256};
+// the auto team: kBatchTdpTeam[n] (tsp_batch_tdp.hpp), or the next larger T
+// whose 256 / T requests fit kBatchTdpTeamLds, a fifth of the CU's LDS, so
+// that five workgroups share a CU -- at every measured (n, W) the fastest T or
+// within 7 % of it -- and 256 if none does
 constexpr size_t kBatchTdpTeamLds = 32 * 1024;
 
 __constant__ DpBinom kBatchTdpBinom = dp_make_binom();
@@ -87,9 +71,6 @@ struct BatchTdpArgs {
   int16_t* tours;          // [R][N-1]
   uint64_t* keys;          // [R]
 };
-
-// matrix slices one request stages
-inline int batch_tdp_slices(int H, int W) { return H == 1 ? 1 : (W < 24 ? W : 24); }
 
 // bytes of one team: the table, then the staged slices padded to 8 bytes
 inline size_t batch_tdp_team_bytes(int n, int H, int W) {
@@ -109,48 +90,11 @@ inline int batch_tdp_auto_team(int n, int H, int W) {
   return T;
 }
 
-inline bool batch_tdp_team_ok(int team) {
-  return team == 0 || team == 16 || team == 32 || team == 64 || team == 128 || team == 256;
-}
-
-template <int FILL>
-VRPMS_DEV void batch_tdp_or(uint64_t* p, uint64_t v) {
-  if (FILL)
-    atomicOr(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
-  else
-    *p |= v;
-}
-
-// What one request's lanes share after staging.
-struct BatchTdpReq {
-  int off;             // start % 60: the start's bit in word 0
-  int hz;              // the effective horizon
-  int lw;              // the last word a clock within the horizon can be in
-  uint64_t last_mask;  // bits of word lw at or below start + hz
-};
-
-// One source word x of row (P, i), at word w, moved along the edge i -> c into
-// the destination row: the clip and the last-word mask are applied here.
-template <int FILL>
-VRPMS_DEV void batch_tdp_move(uint64_t x, int d, int w, const BatchTdpReq& q, uint64_t* dest) {
-  const int dq = d / 60, s = d - dq * 60;
-  const int dst = w + dq;
-  if ((unsigned)dst > (unsigned)q.lw) return;
-  uint64_t lo60 = (x << s) & kBatchTdpMask60;
-  if (dst == q.lw) lo60 &= q.last_mask;
-  if (lo60) batch_tdp_or<FILL>(dest + dst, lo60);
-  if (dst < q.lw) {
-    uint64_t hi60 = x >> (60 - s);   // s = 0: x < 2^60, nothing carries
-    if (dst + 1 == q.lw) hi60 &= q.last_mask;
-    if (hi60) batch_tdp_or<FILL>(dest + dst + 1, hi60);
-  }
-}
-
 template <int T, int FILL>
 __global__ __launch_bounds__(256) void tsp_batch_tdp_kernel(BatchTdpArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint64_t batch_tdp_lds[];
   const int N = a.N, n = N - 1, W = a.W, NN2 = N * N;
-  const uint32_t half = 1u << (n - 1), full = (1u << n) - 1u;
+  const uint32_t full = (1u << n) - 1u;
   const int team = threadIdx.x / T, tl = threadIdx.x % T;
   const int64_t req = (int64_t)blockIdx.x * (256 / T) + team;
   const bool active = req < a.R;
@@ -168,163 +112,28 @@ __global__ __launch_bounds__(256) void tsp_batch_tdp_kernel(BatchTdpArgs a) {
   if (active) {
     const int start = a.start[req], horizon = a.horizon[req];
     live = start >= 0 && horizon >= 0;
-    const int st = live ? start : 0;
-    const int h0 = (st / 60) % 24;
-    q.off = st % 60;
-    if (live) {
-      const int cap = 60 * W - 1 - q.off;
-      q.hz = horizon < cap ? horizon : cap;
-      q.lw = (q.off + q.hz) / 60;
-      q.last_mask = (2ull << ((q.off + q.hz) % 60)) - 1ull;
-    }
-    const int32_t* D = a.mats + req * (int64_t)a.H * NN2;
-    for (int e = tl; e < ns * NN2; e += T) {
-      const int p = e / NN2, r = e - p * NN2;
-      const int slice = a.H == 1 ? 0 : (h0 + p) % 24;
-      Dl[e] = D[slice * NN2 + r];
-    }
-    for (uint32_t e = tl; e < table_words; e += T) tab[e] = 0;
+    if (live) q = batch_tdp_req(start, horizon, W);
+    batch_tdp_stage<T>(a.mats + req * (int64_t)a.H * NN2, N, a.H, W, ns, live ? start : 0, full, n, tl, Dl,
+                       tab);
   }
   __syncthreads();
-  // the n singleton rows: ({c}, c) squeezes to 0
-  if (live && tl < n) {
-    const int64_t rel = (int64_t)q.off + Dl[tl + 1];
-    if (rel >= 0 && rel <= (int64_t)q.off + q.hz)
-      tab[(size_t)tl * half * W + rel / 60] = 1ull << (rel % 60);
-  }
-  __syncthreads();
+  batch_tdp_fill<T, FILL>(B, tab, Dl, n, W, ns, q, tl, live, n);
 
-  const int nw = q.lw + 1;   // words of a row that can hold a clock
-  // lanes per destination row
-  int G = 1;
-  if (FILL) {
-    G = 4;
-    while (G < W && G < 64 && G < T) G *= 2;
-  }
-  // lane -> (predecessor index, word) of its first item of a row, and the step of G items
-  const int gl = tl % G, nwd = nw > 0 ? nw : 1;
-  const int p0 = gl / nwd, w0 = gl - p0 * nwd;
-  const int pstep = G / nwd, wstep = G - pstep * nwd;
-  for (int k = 2; k <= n; ++k) {
-    if (live) {
-      const uint32_t rows = B[n * kBatchDpNodes + k] * (uint32_t)k;
-      const uint32_t NG = (uint32_t)(T / G), grp = (uint32_t)(tl / G);
-      const uint32_t lo = grp * rows / NG, hi = (grp + 1u) * rows / NG;
-      if (lo < hi) {
-        uint32_t r = lo / k;
-        int t = (int)(lo - r * k);
-        uint32_t S = k == n ? full : dp_unrank(B, kBatchDpNodes, n, k, r);
-        for (uint32_t e = lo; e < hi; ++e) {
-          uint32_t m = S;   // c = the t-th customer of S
-          for (int u = 0; u < t; ++u) m &= m - 1u;
-          const int c = __builtin_ctz(m);
-          const uint32_t P = S ^ (1u << c);
-          uint64_t* dest = tab + (size_t)(c * half + batch_dp_squeeze(S, c)) * W;
-          const int32_t* col = Dl + c + 1;   // col[(p N + i + 1) N] = D[slice p][i + 1][c + 1]
-          if (!FILL) {
-            for (uint32_t pm = P; pm; pm &= pm - 1u) {
-              const int i = __builtin_ctz(pm);
-              const uint64_t* src = tab + (size_t)(i * half + batch_dp_squeeze(P, i)) * W;
-              for (int w = 0; w < nw; ++w) {
-                const uint64_t x = src[w];
-                if (x) batch_tdp_move<FILL>(x, col[((w % 24 % ns) * N + i + 1) * N], w, q, dest);
-              }
-            }
-          } else {
-            const int items = (k - 1) * nw;
-            int p = p0, w = w0;
-            for (int it = gl; it < items; it += G) {
-              uint32_t pm = P;   // i = the p-th customer of P
-              for (int u = 0; u < p; ++u) pm &= pm - 1u;
-              const int i = __builtin_ctz(pm);
-              const uint64_t x = tab[(size_t)(i * half + batch_dp_squeeze(P, i)) * W + w];
-              if (x) batch_tdp_move<FILL>(x, col[((w % 24 % ns) * N + i + 1) * N], w, q, dest);
-              p += pstep;
-              w += wstep;
-              if (w >= nw) {
-                w -= nw;
-                ++p;
-              }
-            }
-          }
-          if (++t == k) {
-            t = 0;
-            if (e + 1u < hi) S = dp_next_mask(S);
-          }
-        }
-      }
-    }
-    __syncthreads();
-  }
-
-  // the walk: the closing edge prices the lowest bit of every word of the n
-  // full-set rows (one slice per word, so the lowest bit is the word's best);
-  // then n - 1 steps back, each the smallest predecessor and for it the
-  // smallest clock that reaches the current (customer, clock)
   constexpr int WL = T < 64 ? T : 64;
   if (!active || tl >= WL) return;
   int16_t* tour = a.tours + req * n;
-  uint32_t S = full;
-  uint64_t best = ~0ull;
-  if (live) {
-    for (int e = tl; e < n * nw; e += WL) {
-      const int c = e / nw, w = e - c * nw;
-      const uint64_t x = tab[(size_t)(c * half + batch_dp_squeeze(S, c)) * W + w];
-      if (!x) continue;
-      const int brel = 60 * w + __builtin_ctzll(x);
-      const int64_t val = (int64_t)brel - q.off + Dl[((w % 24 % ns) * N + c + 1) * N];
-      if (val < 0 || val > q.hz) continue;
-      const uint64_t cand = ((uint64_t)val << 24) | ((uint64_t)c << 16) | (uint64_t)brel;
-      best = cand < best ? cand : best;
-    }
-  }
-#pragma unroll
-  for (int o = WL / 2; o > 0; o >>= 1) {
-    const uint64_t v = __shfl_xor(best, o, WL);
-    best = v < best ? v : best;
-  }
-  if (best == ~0ull) {
+  const uint32_t dur = batch_tdp_walk<T>(tab, Dl, n, W, ns, q, full, tl, live, tour);
+  if (dur == 0xffffffffu) {
     if (tl < n) tour[tl] = 0;
     if (tl == 0) a.keys[req] = ~0ull;
     return;
   }
-  int c = (int)(best >> 16 & 0xff), brel = (int)(best & 0xffff);
-  for (int pos = n - 1; pos >= 1; --pos) {
-    if (tl == 0) tour[pos] = (int16_t)(c + 1);
-    S ^= 1u << c;
-    const int sw = brel / 60 + 1;   // source words that can reach the clock
-    uint64_t step = ~0ull;
-    for (int e = tl; e < n * sw; e += WL) {
-      const int i = e / sw, w = e - i * sw;
-      if (!(S >> i & 1u)) continue;
-      const uint64_t x = tab[(size_t)(i * half + batch_dp_squeeze(S, i)) * W + w];
-      const int64_t m = (int64_t)brel - 60 * w - Dl[((w % 24 % ns) * N + i + 1) * N + c + 1];
-      if (m < 0 || m >= 60 || !(x >> m & 1ull)) continue;
-      const uint64_t cand = ((uint64_t)i << 16) | (uint64_t)(60 * w + m);
-      step = cand < step ? cand : step;
-    }
-#pragma unroll
-    for (int o = WL / 2; o > 0; o >>= 1) {
-      const uint64_t v = __shfl_xor(step, o, WL);
-      step = v < step ? v : step;
-    }
-    if (step == ~0ull) {  // unreachable for a table the layers wrote
-      if (tl < n) tour[tl] = 0;
-      if (tl == 0) a.keys[req] = ~0ull;
-      return;
-    }
-    c = (int)(step >> 16);
-    brel = (int)(step & 0xffff);
-  }
-  if (tl == 0) {
-    tour[0] = (int16_t)(c + 1);
-    a.keys[req] = pack_key(0, (uint32_t)(best >> 24), 0);
-  }
+  if (tl == 0) a.keys[req] = pack_key(0, dur, 0);
 }
 
 template <int T>
 static hipError_t batch_tdp_launch(const BatchTdpArgs& a, size_t lds, hipStream_t s) {
-  const bool atomic = kBatchTdpFill == 2 ? a.W >= kBatchTdpAtomicWords : kBatchTdpFill == 1;
+  const bool atomic = batch_tdp_atomic(a.W);
   const void* fn = atomic ? reinterpret_cast<const void*>(tsp_batch_tdp_kernel<T, 1>)
                           : reinterpret_cast<const void*>(tsp_batch_tdp_kernel<T, 0>);
   if (lds > 65536) {

@@ -478,6 +478,53 @@ class ExactTdpBatcher(TspBatcher):
             return solver.batch_tdp_launch(solver.context(dev), cis, bounds)
 
 
+class ExactTdspBatcher(TspBatcher):
+    """Coalesces concurrent exact time-dependent small-fleet requests --
+    ("vrp", "tdsp") on the inline route -- into one `vrp_batch_tdsp` launch per
+    (node count, fleet size, hour count, number of distinct start times,
+    objective) (spec A21: each request's time-expanded partition DP in LDS).
+    The queue, the window, the device round-robin and the error fan-out are
+    TspBatcher's; a job carries its own upper bound and objective, and the
+    launch takes the group's bounds next to its instances.  A batched answer
+    does not depend on the batch: it is the unbatched answer of the same
+    request."""
+
+    def __init__(self, app, window_s: float = 0.005, max_batch: int = 16384, launch=None):
+        super().__init__(app, window_s, steps=0, max_batch=max_batch, launch=launch)
+
+    @classmethod
+    def accepts(cls, ci, bound=None) -> bool:
+        """Requests inside A21's LDS domain for their bound
+        (solver.batch_tdsp_fits) that pass the int32 guards vrpms_set_instance
+        applies on the unbatched path; anything else takes the unbatched path,
+        so both paths share one error contract."""
+        from . import solver
+        return solver.batch_tdsp_fits(ci, bound) and solver.batch_sp_guard(ci)
+
+    @staticmethod
+    def group_key(job):
+        ci = job["ci"]
+        return (ci.N, len(ci.capacities), ci.durations.shape[0],
+                len(set(int(s) for s in ci.start_times)), job["objective"])
+
+    def solve(self, ci, bound, objective: str = "sum") -> dict:
+        """Blocks until the request's launch finished -> the VRP slot dict."""
+        from . import solver
+        job = {"ci": ci, "bound": int(bound), "objective": "max" if objective == "max" else "sum",
+               "done": threading.Event()}
+        self._wait(job)
+        return solver.sp_result(ci, list(job["tour"]), job["duration"])
+
+    _run = ExactTdpBatcher._run
+
+    def _gpu_launch(self, key, cis, bounds, device=None):
+        """-> (tours, route durations) on `device` (default: the app's first)."""
+        from . import solver
+        dev = self.devices[0] if device is None else device
+        with self.app.locks[dev]:
+            return solver.batch_tdsp_launch(solver.context(dev), cis, bounds, key[4])
+
+
 # ---------------------------------------------------------------------------
 # the endpoint logic
 # ---------------------------------------------------------------------------
@@ -499,7 +546,8 @@ class App:
                  solve=None, batch_tsp: bool = False, batch_window_s: float = 0.005,
                  batch_steps: int = 2000, batch_launch=None, devices=None,
                  island_min_n: int = 150, batch_exact: bool = False, batch_exact_launch=None,
-                 batch_exact_vrp_launch=None, batch_exact_tdp_launch=None):
+                 batch_exact_vrp_launch=None, batch_exact_tdp_launch=None,
+                 batch_exact_tdsp: bool = False, batch_exact_tdsp_launch=None):
         self.store = store
         self.devices = list(devices) if devices else [device]
         self.device = self.devices[0]
@@ -524,6 +572,11 @@ class App:
         self.exact_tdp_batcher = ExactTdpBatcher(self, batch_window_s,
                                                  launch=batch_exact_tdp_launch) \
             if batch_exact else None
+        # exact time-dependent small-fleet requests share vrp_batch_tdsp
+        # launches: opt-in on its own (batch_exact alone leaves tdsp scheduled)
+        self.exact_tdsp_batcher = ExactTdspBatcher(self, batch_window_s,
+                                                   launch=batch_exact_tdsp_launch) \
+            if batch_exact_tdsp else None
 
     def _scheduled(self, problem, algorithm, params, knobs, locations, durations):
         """Run the solve on a device: all of them (in order, as an island
@@ -591,6 +644,20 @@ class App:
                                 params["start_time"] or 0)
         bound = solver.batch_tdp_bound(ci, upper_bound)
         return (ci, bound) if self.exact_tdp_batcher.accepts(ci, bound) else None
+
+    def _batched_tdsp(self, params, durations, locations, objective="sum", upper_bound=None):
+        """(compact instance, bound, objective) when this ("vrp", "tdsp")
+        request rides the exact time-dependent fleet batcher, else None.  A
+        request outside A17's domain raises here what the unbatched path
+        raises for it."""
+        if self.exact_tdsp_batcher is None:
+            return None
+        from . import solver
+        ci = solver.compact_vrp(durations, locations, params["capacities"], params["start_times"],
+                                params["ignored_customers"], params["completed_customers"])
+        bound = solver._check_tdsp(ci, solver.OBJ_MAX if objective == "max" else solver.OBJ_SUM,
+                                   upper_bound)
+        return (ci, bound, objective) if self.exact_tdsp_batcher.accepts(ci, bound) else None
 
     def _gpu_solve(self, problem, algorithm, params, knobs, locations, durations):
         """knobs may carry "seed", "time_limit" and "objective" (the /solve
@@ -735,8 +802,14 @@ class App:
             tdp = self._batched_tdp(params, vals["durations"],
                                     knobs["inline"].get("upper_bound")) \
                 if (problem, algorithm) == ("tsp", "tdp") else None
+            tdsp = self._batched_tdsp(params, vals["durations"], locations,
+                                      knobs.get("objective", "sum"),
+                                      knobs["inline"].get("upper_bound")) \
+                if (problem, algorithm) == ("vrp", "tdsp") else None
             if ci is not None:
                 result = self.exact_batcher.solve(ci)
+            elif tdsp is not None:
+                result = self.exact_tdsp_batcher.solve(*tdsp)
             elif tdp is not None:
                 result = self.exact_tdp_batcher.solve(*tdp)
             elif vrp_ci is not None:
@@ -858,6 +931,11 @@ def main(argv=None):
                          "static or hour-indexed matrix, 1..11 customers, an upper bound whose "
                          "hour words fit the LDS) into tsp_batch_tdp launches; the answers equal "
                          "the unbatched ones")
+    ap.add_argument("--batch-exact-tdsp", action="store_true",
+                    help="coalesce concurrent exact time-dependent small-fleet requests "
+                         "(/solve/vrp/tdsp, static or hour-indexed matrix, 1..11 customers, a "
+                         "fleet and an upper bound whose state fits the LDS) into vrp_batch_tdsp "
+                         "launches; the answers equal the unbatched ones")
     ap.add_argument("--batch-window-ms", type=float, default=5.0)
     ap.add_argument("--batch-steps", type=int, default=2000)
     ap.add_argument("--workers", type=int, default=0,
@@ -895,7 +973,8 @@ def main(argv=None):
         return
     app = App(store, device=args.device, seed=args.seed, max_seconds=args.max_seconds,
               batch_tsp=args.batch_tsp, batch_window_s=args.batch_window_ms * 1e-3,
-              batch_steps=args.batch_steps, devices=devices, batch_exact=args.batch_exact)
+              batch_steps=args.batch_steps, devices=devices, batch_exact=args.batch_exact,
+              batch_exact_tdsp=args.batch_exact_tdsp)
     srv = serve(app, args.host, args.port)
     print(f"vrpms_amd service on http://{args.host}:{args.port}/api", flush=True)
     try:

@@ -99,6 +99,13 @@ BATCH_TDP_LDS_BYTES = 160 * 1024
 TDSP_MAX_CUSTOMERS = 19
 TDSP_MAX_VEHICLES = 64
 TDSP_MAX_WORKSPACE = 16 << 30
+# batched time-expanded partition DP (A21): one request's compact A16 table, the
+# slices its words use, G route tables and K partition layers have to fit one
+# CU's LDS (vrpms_vrp_batch_tdsp_lds gives the bytes for (n, K, G, H, W));
+# DESIGN.md §4.3l has the largest W per (n, K, G).  12 customers never fit.
+# Other requests of a batch take the single-request path
+BATCH_TDSP_MAX_CUSTOMERS = 11
+BATCH_TDSP_LDS_BYTES = 160 * 1024
 # SA on tours of more than SA_WINDOW_MIN_N customers samples A11 windowed
 # moves (second position within SA_WINDOW of the first)
 SA_WINDOW, SA_WINDOW_MIN_N = 32, 150
@@ -846,7 +853,8 @@ def solve_vrp_batch(algorithm: str, requests, *, objective: str = "sum",
     (batch_sp_fits) are grouped by (N, K), one upload and one vrp_batch_sp
     launch per group, and their result dicts are built on the host from the
     tour tokens and the route durations; no customer, 13..20 customers and
-    fleets beyond the LDS take solve_vrp("sp"), one by one."""
+    fleets beyond the LDS take solve_vrp("sp"), one by one.  "tdsp" has a
+    batched kernel of its own behind solve_vrp_tdsp_batch (spec A21)."""
     if algorithm != "sp":
         raise ValueError(f'solve_vrp_batch: no batched kernel for algorithm {algorithm!r}; only '
                          '"sp" (exact set partitioning) is batched')
@@ -882,6 +890,131 @@ def solve_vrp_batch(algorithm: str, requests, *, objective: str = "sum",
         ctx = context(device)
         for xs in groups.values():
             tours, durs = batch_sp_launch(ctx, [cis[x] for x in xs], objective)
+            for x, tour, d in zip(xs, tours, durs):
+                out[x] = sp_result(cis[x], tour, d, with_unvisited)
+    return out
+
+
+def batch_tdsp_words(ci: CompactInstance, bound) -> int:
+    """The hour words a request's rows need: the largest tdp_words(start_k,
+    bound) over its vehicles."""
+    return max((int(s) % 60 + int(bound)) // 60 + 1 for s in ci.start_times)
+
+
+def batch_tdsp_fits(ci: CompactInstance, bound) -> bool:
+    """A21's domain: 1..BATCH_TDSP_MAX_CUSTOMERS customers, 1..64 vehicles, a
+    static or 24-slice matrix, and the request's own (n, K, G, H, W) -- G its
+    distinct start times, W the hour words of `bound` from its starts -- within
+    BATCH_TDSP_LDS_BYTES.  Needs the library, no GPU."""
+    from .core import vrp_batch_tdsp_lds
+    if ci.problem != CVRP or not 1 <= ci.n <= BATCH_TDSP_MAX_CUSTOMERS or bound is None:
+        return False
+    K, H = len(ci.capacities), ci.durations.shape[0]
+    if not 1 <= K <= TDSP_MAX_VEHICLES or H not in (1, 24) or int(bound) < 0:
+        return False
+    starts = [int(s) for s in ci.start_times]
+    if min(starts) < 0 or max(starts) + int(bound) >= 2**31:
+        return False
+    W = batch_tdsp_words(ci, bound)
+    if W > TDP_MAX_WORDS:
+        return False
+    return vrp_batch_tdsp_lds(ci.n, K, len(set(starts)), H, W) <= BATCH_TDSP_LDS_BYTES
+
+
+def batch_tdsp_launch(ctx: Context, cis, bounds, objective: str = "sum"):
+    """One upload and one vrp_batch_tdsp launch for compact instances of one
+    (N, K, H, number of distinct starts) (each passed batch_sp_guard and
+    batch_tdsp_fits with its bound), W the largest of their row widths ->
+    (tours, durations): per instance the n + K tour tokens and the K route
+    durations."""
+    import torch
+    N, K, H = cis[0].N, len(cis[0].capacities), cis[0].durations.shape[0]
+    mats = np.empty((len(cis), H, N, N), dtype=np.int32)
+    dem = np.empty((len(cis), N), dtype=np.int32)
+    caps = np.empty((len(cis), K), dtype=np.int32)
+    starts = np.empty((len(cis), K), dtype=np.int64)
+    for x, ci in enumerate(cis):
+        mats[x], dem[x], caps[x], starts[x] = ci.durations, ci.demand, ci.capacities, ci.start_times
+    G = max(len(set(row)) for row in starts.tolist())
+    W = max(batch_tdsp_words(ci, b) for ci, b in zip(cis, bounds))
+    tours, keys, durs = ctx.vrp_batch_tdsp(torch.from_numpy(mats).to(ctx.dev),
+                                           torch.from_numpy(dem).to(ctx.dev),
+                                           torch.from_numpy(caps).to(ctx.dev), starts,
+                                           np.array([int(b) for b in bounds], dtype=np.int64),
+                                           OBJ_MAX if objective == "max" else OBJ_SUM, G=G, W=W)
+    if (keys == -1).any().item():
+        raise RuntimeError("vrp_batch_tdsp: a request was outside the launch's contract")
+    return tours.cpu().tolist(), durs.cpu().tolist()
+
+
+def _guard_message(ci: CompactInstance) -> str:
+    mx = int(ci.durations.max()) if ci.durations.size else 0
+    if int(ci.start_times.max()) + (ci.N + len(ci.capacities) + 1) * mx >= 2**31:
+        return "start + (N+K+1)*max_duration overflows int32 (A9 guard)"
+    return "capacity + demand overflows int32"
+
+
+def solve_vrp_tdsp_batch(requests, *, objective: str = "sum", with_unvisited: bool = False,
+                         device: int = 0) -> list:
+    """[solve_vrp("tdsp", *r, objective=objective, with_unvisited=...,
+    upper_bound=...) for r in requests], element for element, with the small
+    requests sharing launches (spec A21).  `requests`: (durations, locations,
+    capacities, start_times[, ignored_customers, completed_customers[,
+    upper_bound]]) tuples, or dicts with those keys; the upper bound is the
+    knob of solve_vrp("tdsp") (default: runners.tdsp_default_bound).  Every
+    request is compacted and checked on the host before any device is touched
+    (_check_tdsp, batch_sp_guard); a bad one raises solve_vrp("tdsp")'s message
+    prefixed with its index.  Requests inside A21's LDS domain
+    (batch_tdsp_fits: 1..11 customers, the row width the bound implies) are
+    grouped by (node count, fleet size, hour count, number of distinct start
+    times), one upload and one vrp_batch_tdsp launch per group at the group's
+    largest row width, and their result dicts are built on the host from the
+    tour tokens and the route durations; no customer, 12..19 customers and an
+    (n, K, G, W) outside the LDS take solve_vrp("tdsp"), one by one."""
+    obj = OBJ_MAX if objective == "max" else OBJ_SUM
+    reqs, cis, bounds, knobs = [], [], [], []
+    for x, r in enumerate(requests):
+        if isinstance(r, dict):
+            r = tuple(r.get(k) for k in _VRP_REQUEST_KEYS[:4]) + \
+                (r.get("ignored_customers", ()), r.get("completed_customers", ()),
+                 r.get("upper_bound"))
+        seq = (tuple, list, np.ndarray)
+        if not isinstance(r, (tuple, list)) or not 4 <= len(r) <= 7 or \
+                not all(isinstance(v, seq) for v in r[1:4]):
+            raise ValueError(f"request {x}: a VRP request is (durations, locations, capacities, "
+                             "start_times[, ignored_customers, completed_customers[, "
+                             "upper_bound]]) or a dict with those keys")
+        r = tuple(r)
+        ub = r[6] if len(r) > 6 else None
+        r = r[:6] + ((),) * (6 - len(r[:6]))
+        try:
+            ci = compact_vrp(*r)
+            bound = _check_tdsp(ci, obj, ub)
+            if not batch_sp_guard(ci):
+                raise ValueError(_guard_message(ci))
+        except ValueError as e:
+            raise ValueError(f"request {x}: {e}") from None
+        reqs.append(r)
+        cis.append(ci)
+        bounds.append(bound)
+        knobs.append({} if ub is None else {"upper_bound": ub})
+    single = dict(objective=objective, with_unvisited=with_unvisited)
+    if _remote() is not None:      # no local GPU: the GPU box answers each request
+        return [solve_vrp("tdsp", *r, **single, **k) for r, k in zip(reqs, knobs)]
+    out = [None] * len(cis)
+    groups: dict = {}
+    for x, ci in enumerate(cis):
+        if batch_tdsp_fits(ci, bounds[x]):
+            key = (ci.N, len(ci.capacities), ci.durations.shape[0],
+                   len(set(int(s) for s in ci.start_times)))
+            groups.setdefault(key, []).append(x)
+        else:
+            out[x] = solve_vrp("tdsp", *reqs[x], device=device, **single, **knobs[x])
+    if groups:
+        ctx = context(device)
+        for xs in groups.values():
+            tours, durs = batch_tdsp_launch(ctx, [cis[x] for x in xs], [bounds[x] for x in xs],
+                                            objective)
             for x, tour, d in zip(xs, tours, durs):
                 out[x] = sp_result(cis[x], tour, d, with_unvisited)
     return out
