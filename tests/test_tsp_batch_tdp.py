@@ -314,6 +314,24 @@ def test_batch_tdp_fits_and_batcher_accepts_at_the_domain_edges(lib):
     assert solver.batch_tdp_bound(_ci(0)) is None
 
 
+def test_a_clamped_key_is_priced_on_the_host_by_one_fallback():
+    """A key at the 2^28 - 1 clamp has its duration priced by the one host
+    fallback dp and tdp share: the static edge sum for H = 1, the A3 clock for
+    H = 24; a key below the clamp is read as it is, an all-ones key is None."""
+    tour = [3, 1, 5, 2, 4]
+    path = [0] + tour + [0]
+    clamped = spec.tsp_key(2**28 - 1)
+    static, hourly = _ci(5, seed=4, start_time=1390, H=1), _ci(5, seed=4, start_time=1390)
+    edge_sum = sum(int(static.durations[0][a][b]) for a, b in zip(path, path[1:]))
+    clock = spec.eval_tsp(hourly.durations, tour, 1390)
+    assert clock != sum(int(hourly.durations[0][a][b]) for a, b in zip(path, path[1:]))
+    assert solver._td_duration(static, tour) == edge_sum
+    assert solver._td_duration(hourly, tour) == clock
+    assert solver._key_durations([static, hourly, static, hourly], [tour] * 4,
+                                 [clamped, clamped, spec.tsp_key(77), -1]) == \
+        [edge_sum, clock, 77, None]
+
+
 class _FakeApp:
     devices = [0]
     device = 0

@@ -10,6 +10,7 @@ import pytest
 
 import value_edges as ve
 from oracle import spec
+from vrpms_amd import solver
 
 
 @pytest.mark.parametrize("name", list(ve.BUILDERS))
@@ -140,3 +141,39 @@ def test_small_search_cases_sit_on_the_same_thresholds():
     inst = ve.small("e4_in")
     f = ve.tour_facts(inst, [1, 5, 6, 2, 3, 4, 7, 8, 9, 10, 11, 12])
     assert f["close"] and f["refuse"]
+
+
+def _compact(inst, problem=solver.CVRP, capacities=None):
+    tsp = problem == solver.TSP
+    caps = inst.capacities if capacities is None else np.asarray(capacities)
+    return solver.CompactInstance(problem, np.asarray(inst.durations), list(range(inst.N)),
+                                  None if tsp else np.asarray(inst.demand),
+                                  None if tsp else caps, np.asarray(inst.start_times)[:1 if tsp else None])
+
+
+def test_batch_guard_message_names_the_failing_guard():
+    """solver.batch_guard_message on the E8 pairs: None exactly where
+    batch_dp_guard / batch_sp_guard hold (and vrpms_set_instance accepts), else
+    the message of the guard the pair is about; with both failing, A9's."""
+    a9, cap = "start + (N+K+1)*max_duration overflows int32 (A9 guard)", \
+        "capacity + demand overflows int32"
+    for name, want in (("e8_time", a9), ("e8_hour", a9), ("e8_cap", cap), ("e8_het", cap)):
+        for e in ve.pair(name):
+            ci = _compact(e.inst)
+            assert solver.batch_sp_guard(ci) == ve.accepted(e.inst) == (not e.refused)
+            assert solver.batch_guard_message(ci) == (want if e.refused else None), e.name
+    time_out, cap_out = ve.pair("e8_time")[1].inst, ve.pair("e8_cap")[1].inst
+    both = _compact(time_out, capacities=[int(cap_out.capacities.max())] * time_out.K)
+    assert int(both.capacities.max()) + int(both.demand.max()) < 2**31    # small demands here
+    both.demand = both.demand.copy()       # the pair's own array is shared with other tests
+    both.demand[1] = 2**30
+    assert int(both.capacities.max()) + int(both.demand.max()) >= 2**31
+    assert solver.batch_guard_message(both) == a9 and not solver.batch_sp_guard(both)
+    # a TSP counts one vehicle and has no capacity guard: the limit is start + (N + 2) * max
+    inst = ve.pair("e8_time")[0].inst
+    md = int(np.asarray(inst.durations).max())
+    for start, ok in ((2**31 - 1 - (inst.N + 2) * md, True), (2**31 - (inst.N + 2) * md, False)):
+        tsp = _compact(inst, solver.TSP)
+        tsp.start_times = np.array([start])
+        assert solver.batch_dp_guard(tsp) == ok
+        assert solver.batch_guard_message(tsp) == (None if ok else a9)

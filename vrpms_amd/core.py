@@ -452,6 +452,37 @@ class Context:
                                           tours.data_ptr(), keys.data_ptr(), self.stream()))
         return tours, keys
 
+    def _batch_mats(self, torch, mats, rank: int):
+        """The batched wrappers' `mats` check: contiguous int32 [R][N][N]
+        (rank 3) or [R][H][N][N] (rank 4, [R][N][N] taken as H = 1) here."""
+        if rank == 4 and mats.dim() == 3:
+            mats = mats.unsqueeze(1)
+        if mats.device != self.dev or mats.dim() != rank or mats.shape[-2] != mats.shape[-1] or \
+                mats.dtype != torch.int32 or not mats.is_contiguous():
+            raise ValueError(f"mats must be a contiguous int32 [R]{'[H]' * (rank - 3)}[N][N] "
+                             f"tensor on {self.dev}")
+        return mats
+
+    def _batch_rows(self, torch, demand, caps, R: int, N: int):
+        """demand is a contiguous int32 [R][N] tensor here, caps an [R][K] one."""
+        for name, t, cols in (("demand", demand, N), ("caps", caps, None)):
+            if t.device != self.dev or t.dim() != 2 or t.shape[0] != R or t.dtype != torch.int32 or \
+                    not t.is_contiguous() or (cols is not None and t.shape[1] != cols):
+                raise ValueError(f"{name} must be a contiguous int32 [R][{'N' if cols else 'K'}] "
+                                 f"tensor on {self.dev}")
+
+    def _host_minutes(self, torch, starts, shape, horizons, R: int, explicit: bool):
+        """starts (of `shape`) and horizons ([R]) as int64 host arrays for the
+        caller to check and upload, or None when both are int32 tensors of
+        those shapes here and the launch's widths are `explicit`: uploaded and
+        checked by the caller, passed through as they are."""
+        if explicit and all([isinstance(t, torch.Tensor) and t.device == self.dev and
+                             t.dtype == torch.int32 and t.shape == sh and t.is_contiguous()
+                             for t, sh in ((starts, shape), (horizons, (R,)))]):
+            return None
+        return [(t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(np.int64)
+                for t in (starts, horizons)]
+
     def tsp_batch_dp(self, mats):
         """Exact optimum of every request in one launch (spec A18, at most 12
         customers): mats int32 [R][N][N] on the device -> (tours int16
@@ -460,10 +491,7 @@ class Context:
         builds `mats` from host data checks it before uploading.
         Asynchronous on the current stream."""
         torch = _torch()
-        if mats.device != self.dev or mats.dim() != 3 or mats.shape[1] != mats.shape[2] or \
-                mats.dtype != torch.int32 or not mats.is_contiguous():
-            raise ValueError(f"mats must be a contiguous int32 [R][N][N] tensor on {self.dev}")
-        R, N, _ = mats.shape
+        R, N, _ = self._batch_mats(torch, mats, 3).shape
         tours = torch.empty((R, max(N - 1, 1)), dtype=torch.int16, device=self.dev)
         keys = torch.empty(R, dtype=torch.int64, device=self.dev)
         check(self.lib.vrpms_tsp_batch_dp(self._ctx, mats.data_ptr(), R, N, tours.data_ptr(),
@@ -483,15 +511,8 @@ class Context:
         host data checks them before uploading.  Asynchronous on the current
         stream."""
         torch = _torch()
-        if mats.device != self.dev or mats.dim() != 3 or mats.shape[1] != mats.shape[2] or \
-                mats.dtype != torch.int32 or not mats.is_contiguous():
-            raise ValueError(f"mats must be a contiguous int32 [R][N][N] tensor on {self.dev}")
-        R, N, _ = mats.shape
-        for name, t, cols in (("demand", demand, N), ("caps", caps, None)):
-            if t.device != self.dev or t.dim() != 2 or t.shape[0] != R or t.dtype != torch.int32 or \
-                    not t.is_contiguous() or (cols is not None and t.shape[1] != cols):
-                raise ValueError(f"{name} must be a contiguous int32 [R][{'N' if cols else 'K'}] "
-                                 f"tensor on {self.dev}")
+        R, N, _ = self._batch_mats(torch, mats, 3).shape
+        self._batch_rows(torch, demand, caps, R, N)
         K = caps.shape[1]
         tours = torch.empty((R, max(N - 1 + K, 1)), dtype=torch.int16, device=self.dev)
         keys = torch.empty(R, dtype=torch.int64, device=self.dev)
@@ -518,28 +539,18 @@ class Context:
         not depend on it).  Non-negative durations are the caller's promise.
         Asynchronous on the current stream."""
         torch = _torch()
-        if mats.dim() == 3:
-            mats = mats.unsqueeze(1)
-        if mats.device != self.dev or mats.dim() != 4 or mats.shape[2] != mats.shape[3] or \
-                mats.dtype != torch.int32 or not mats.is_contiguous():
-            raise ValueError(f"mats must be a contiguous int32 [R][H][N][N] tensor on {self.dev}")
+        mats = self._batch_mats(torch, mats, 4)
         R, H, N, _ = mats.shape
-        on_device = [isinstance(t, torch.Tensor) and t.device == self.dev and
-                     t.dtype == torch.int32 and t.shape == (R,) and t.is_contiguous()
-                     for t in (starts, horizons)]
-        if all(on_device) and W is not None:
-            d_st, d_hz = starts, horizons      # uploaded and checked by the caller
+        host = self._host_minutes(torch, starts, (R,), horizons, R, W is not None)
+        if host is None:
+            d_st, d_hz = starts, horizons
         else:
-            host = []
-            for name, t in (("starts", starts), ("horizons", horizons)):
-                a = t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
-                a = a.astype(np.int64).reshape(-1)
+            st, hz = host[0].reshape(-1), host[1].reshape(-1)
+            for name, a in (("starts", st), ("horizons", hz)):
                 if a.shape[0] != R:
                     raise ValueError(f"{name} must have one entry per request ({R})")
                 if R and (a.min() < 0 or a.max() >= 2**31):
                     raise ValueError(f"{name} must be non-negative int32 minutes")
-                host.append(a)
-            st, hz = host
             if R and int((st + hz).max()) >= 2**31:
                 raise ValueError("start + horizon must stay below 2^31")
             if W is None:
@@ -575,27 +586,16 @@ class Context:
         non-negative durations, demands and capacities are the caller's
         promise.  Asynchronous on the current stream."""
         torch = _torch()
-        if mats.dim() == 3:
-            mats = mats.unsqueeze(1)
-        if mats.device != self.dev or mats.dim() != 4 or mats.shape[2] != mats.shape[3] or \
-                mats.dtype != torch.int32 or not mats.is_contiguous():
-            raise ValueError(f"mats must be a contiguous int32 [R][H][N][N] tensor on {self.dev}")
+        mats = self._batch_mats(torch, mats, 4)
         R, H, N, _ = mats.shape
-        for name, t, cols in (("demand", demand, N), ("caps", caps, None)):
-            if t.device != self.dev or t.dim() != 2 or t.shape[0] != R or t.dtype != torch.int32 or \
-                    not t.is_contiguous() or (cols is not None and t.shape[1] != cols):
-                raise ValueError(f"{name} must be a contiguous int32 [R][{'N' if cols else 'K'}] "
-                                 f"tensor on {self.dev}")
+        self._batch_rows(torch, demand, caps, R, N)
         K = caps.shape[1]
-        on_device = [isinstance(t, torch.Tensor) and t.device == self.dev and
-                     t.dtype == torch.int32 and t.shape == shape and t.is_contiguous()
-                     for t, shape in ((starts, (R, K)), (horizons, (R,)))]
-        if all(on_device) and W is not None and G is not None:
-            d_st, d_hz = starts, horizons      # uploaded and checked by the caller
+        host = self._host_minutes(torch, starts, (R, K), horizons, R,
+                                  W is not None and G is not None)
+        if host is None:
+            d_st, d_hz = starts, horizons
         else:
-            st = starts.cpu().numpy() if isinstance(starts, torch.Tensor) else np.asarray(starts)
-            hz = horizons.cpu().numpy() if isinstance(horizons, torch.Tensor) else np.asarray(horizons)
-            st, hz = st.astype(np.int64), hz.astype(np.int64).reshape(-1)
+            st, hz = host[0], host[1].reshape(-1)
             if st.size != R * K:
                 raise ValueError(f"starts must have one row of {K} start times per request ({R})")
             st = st.reshape(R, K)

@@ -34,6 +34,7 @@
 
 #include <string>
 
+#include "batch_launch.hpp"
 #include "common.hpp"
 #include "ctx.hpp"
 #include "tsp_batch_dp.hpp"
@@ -108,20 +109,6 @@ __global__ __launch_bounds__(256) void tsp_batch_dp_kernel(BatchDpArgs a) {
   }
 }
 
-template <int T>
-static hipError_t batch_dp_launch(const BatchDpArgs& a, size_t lds, hipStream_t s) {
-  if (lds > 65536) {
-    const hipError_t e =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(tsp_batch_dp_kernel<T>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  const int per_wg = 256 / T;
-  const unsigned blocks = (unsigned)(((int64_t)a.R + per_wg - 1) / per_wg);
-  tsp_batch_dp_kernel<T><<<blocks, 256, lds, s>>>(a);
-  return hipGetLastError();
-}
-
 }  // namespace vrpms
 
 using namespace vrpms;
@@ -146,14 +133,9 @@ extern "C" int vrpms_tsp_batch_dp(vrpms_ctx* ctx, const int32_t* d_mats, int32_t
   VRPMS_HIP(hipSetDevice(ctx->device));
   const BatchDpArgs a{d_mats, R, N, d_tours, d_keys};
   hipStream_t s = (hipStream_t)stream;
-  hipError_t e = hipSuccess;
-  switch (T) {
-    case 16: e = batch_dp_launch<16>(a, lds, s); break;
-    case 32: e = batch_dp_launch<32>(a, lds, s); break;
-    case 64: e = batch_dp_launch<64>(a, lds, s); break;
-    case 128: e = batch_dp_launch<128>(a, lds, s); break;
-    default: e = batch_dp_launch<256>(a, lds, s); break;
-  }
+  const hipError_t e = batch_with_team(T, [&](auto t) {
+    return batch_launch(tsp_batch_dp_kernel<decltype(t)::value>, a, R, T, lds, s);
+  });
   VRPMS_HIP(e);
   return VRPMS_OK;
 }

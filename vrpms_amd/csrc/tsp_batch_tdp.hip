@@ -46,6 +46,7 @@
 
 #include <string>
 
+#include "batch_launch.hpp"
 #include "common.hpp"
 #include "ctx.hpp"
 #include "tsp_batch_dp.hpp"
@@ -131,25 +132,6 @@ __global__ __launch_bounds__(256) void tsp_batch_tdp_kernel(BatchTdpArgs a) {
   if (tl == 0) a.keys[req] = pack_key(0, dur, 0);
 }
 
-template <int T>
-static hipError_t batch_tdp_launch(const BatchTdpArgs& a, size_t lds, hipStream_t s) {
-  const bool atomic = batch_tdp_atomic(a.W);
-  const void* fn = atomic ? reinterpret_cast<const void*>(tsp_batch_tdp_kernel<T, 1>)
-                          : reinterpret_cast<const void*>(tsp_batch_tdp_kernel<T, 0>);
-  if (lds > 65536) {
-    const hipError_t e =
-        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  const int per_wg = 256 / T;
-  const unsigned blocks = (unsigned)(((int64_t)a.R + per_wg - 1) / per_wg);
-  if (atomic)
-    tsp_batch_tdp_kernel<T, 1><<<blocks, 256, lds, s>>>(a);
-  else
-    tsp_batch_tdp_kernel<T, 0><<<blocks, 256, lds, s>>>(a);
-  return hipGetLastError();
-}
-
 static int batch_tdp_check(const char* who, int n, int H, int W, int team) {
   const std::string f(who);
   if (n < 1 || n > kBatchTdpMaxN)
@@ -161,9 +143,7 @@ static int batch_tdp_check(const char* who, int n, int H, int W, int team) {
   if (W < 1 || W > kTdpMaxWords)
     return fail(VRPMS_EINVAL, f + ": a row has 1 <= W <= 512 hour words (" + std::to_string(W) +
                                   " given)");
-  if (!batch_tdp_team_ok(team))
-    return fail(VRPMS_EINVAL, f + ": team must be 0 (auto), 16, 32, 64, 128 or 256 (" +
-                                  std::to_string(team) + " given)");
+  if (!batch_team_ok(team)) return batch_team_fail(who, team);
   return VRPMS_OK;
 }
 
@@ -202,14 +182,12 @@ extern "C" int vrpms_tsp_batch_tdp(vrpms_ctx* ctx, const int32_t* d_mats, const 
   VRPMS_HIP(hipSetDevice(ctx->device));
   const BatchTdpArgs a{d_mats, d_start, d_horizon, R, N, H, W, d_tours, d_keys};
   hipStream_t s = (hipStream_t)stream;
-  hipError_t e = hipSuccess;
-  switch (T) {
-    case 16: e = batch_tdp_launch<16>(a, lds, s); break;
-    case 32: e = batch_tdp_launch<32>(a, lds, s); break;
-    case 64: e = batch_tdp_launch<64>(a, lds, s); break;
-    case 128: e = batch_tdp_launch<128>(a, lds, s); break;
-    default: e = batch_tdp_launch<256>(a, lds, s); break;
-  }
+  const bool atomic = batch_tdp_atomic(W);
+  const hipError_t e = batch_with_team(T, [&](auto t) {
+    constexpr int TT = decltype(t)::value;
+    return batch_launch(atomic ? tsp_batch_tdp_kernel<TT, 1> : tsp_batch_tdp_kernel<TT, 0>, a, R, T,
+                        lds, s);
+  });
   VRPMS_HIP(e);
   return VRPMS_OK;
 }

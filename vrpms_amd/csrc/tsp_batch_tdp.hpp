@@ -45,10 +45,6 @@ constexpr int kBatchTdpTeam[kBatchTdpMaxN + 1] = {16, 16, 16, 16, 16, 16, 32, 32
 // matrix slices one request stages
 inline int batch_tdp_slices(int H, int W) { return H == 1 ? 1 : (W < 24 ? W : 24); }
 
-inline bool batch_tdp_team_ok(int team) {
-  return team == 0 || team == 16 || team == 32 || team == 64 || team == 128 || team == 256;
-}
-
 inline bool batch_tdp_atomic(int W) { return kBatchTdpFill == 2 ? W >= kBatchTdpAtomicWords : kBatchTdpFill == 1; }
 
 template <int FILL>

@@ -42,6 +42,7 @@
 
 #include <string>
 
+#include "batch_launch.hpp"
 #include "common.hpp"
 #include "ctx.hpp"
 #include "tsp_batch_dp.hpp"
@@ -236,23 +237,6 @@ __global__ __launch_bounds__(256) void vrp_batch_sp_kernel(BatchSpArgs a) {
   }
 }
 
-template <int T>
-static hipError_t batch_sp_launch(const BatchSpArgs& a, int objective, size_t lds, hipStream_t s) {
-  const void* fn = objective == VRPMS_OBJ_MAX ? reinterpret_cast<const void*>(vrp_batch_sp_kernel<T, 1>)
-                                              : reinterpret_cast<const void*>(vrp_batch_sp_kernel<T, 0>);
-  if (lds > 65536) {
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  const int per_wg = 256 / T;
-  const unsigned blocks = (unsigned)(((int64_t)a.R + per_wg - 1) / per_wg);
-  if (objective == VRPMS_OBJ_MAX)
-    vrp_batch_sp_kernel<T, 1><<<blocks, 256, lds, s>>>(a);
-  else
-    vrp_batch_sp_kernel<T, 0><<<blocks, 256, lds, s>>>(a);
-  return hipGetLastError();
-}
-
 }  // namespace vrpms
 
 using namespace vrpms;
@@ -265,9 +249,7 @@ extern "C" int vrpms_vrp_batch_sp_lds(int32_t n, int32_t K, int32_t team, uint64
   if (K < 1 || K > kBatchSpMaxK)
     return fail(VRPMS_EINVAL, "vrpms_vrp_batch_sp_lds: set partitioning needs 1 <= K <= 64 (" +
                                   std::to_string(K) + " given)");
-  if (!batch_sp_team_ok(team))
-    return fail(VRPMS_EINVAL, "vrpms_vrp_batch_sp_lds: team must be 0 (auto), 16, 32, 64, 128 or 256 (" +
-                                  std::to_string(team) + " given)");
+  if (!batch_team_ok(team)) return batch_team_fail("vrpms_vrp_batch_sp_lds", team);
   *bytes = batch_sp_lds_bytes(n, K, team ? team : batch_sp_auto_team(n, K));
   return VRPMS_OK;
 }
@@ -286,9 +268,7 @@ extern "C" int vrpms_vrp_batch_sp(vrpms_ctx* ctx, const int32_t* d_mats, const i
                                   std::to_string(K) + " given)");
   if (objective != VRPMS_OBJ_SUM && objective != VRPMS_OBJ_MAX)
     return fail(VRPMS_EINVAL, "vrpms_vrp_batch_sp: objective must be VRPMS_OBJ_SUM or VRPMS_OBJ_MAX");
-  if (!batch_sp_team_ok(team))
-    return fail(VRPMS_EINVAL, "vrpms_vrp_batch_sp: team must be 0 (auto), 16, 32, 64, 128 or 256 (" +
-                                  std::to_string(team) + " given)");
+  if (!batch_team_ok(team)) return batch_team_fail("vrpms_vrp_batch_sp", team);
   if (R == 0) return VRPMS_OK;
   if (!d_mats || !d_demand || !d_cap || !d_tours || !d_keys || !d_durs)
     return fail(VRPMS_EINVAL, "vrpms_vrp_batch_sp: NULL matrix/demand/capacity/tour/key/duration buffer");
@@ -303,14 +283,11 @@ extern "C" int vrpms_vrp_batch_sp(vrpms_ctx* ctx, const int32_t* d_mats, const i
   VRPMS_HIP(hipSetDevice(ctx->device));
   const BatchSpArgs a{d_mats, d_demand, d_cap, R, N, K, d_tours, d_keys, d_durs};
   hipStream_t s = (hipStream_t)stream;
-  hipError_t e = hipSuccess;
-  switch (T) {
-    case 16: e = batch_sp_launch<16>(a, objective, lds, s); break;
-    case 32: e = batch_sp_launch<32>(a, objective, lds, s); break;
-    case 64: e = batch_sp_launch<64>(a, objective, lds, s); break;
-    case 128: e = batch_sp_launch<128>(a, objective, lds, s); break;
-    default: e = batch_sp_launch<256>(a, objective, lds, s); break;
-  }
+  const bool mx = objective == VRPMS_OBJ_MAX;
+  const hipError_t e = batch_with_team(T, [&](auto t) {
+    constexpr int TT = decltype(t)::value;
+    return batch_launch(mx ? vrp_batch_sp_kernel<TT, 1> : vrp_batch_sp_kernel<TT, 0>, a, R, T, lds, s);
+  });
   VRPMS_HIP(e);
   return VRPMS_OK;
 }

@@ -28,10 +28,6 @@ static_assert(kBatchSpGroupLog >= 0 && kBatchSpGroupLog <= 4, "a group lies insi
 // 2^n words padded to four (n = 1 has two)
 inline size_t batch_sp_set_words(int n) { return (((size_t)1 << n) + 3) & ~(size_t)3; }
 
-inline bool batch_sp_team_ok(int team) {
-  return team == 0 || team == 16 || team == 32 || team == 64 || team == 128 || team == 256;
-}
-
 // the demand of T, saturated at unreachable (as vrp_sp_route_kernel's)
 VRPMS_DEV uint32_t batch_sp_demand(const uint32_t* dem, uint32_t T) {
   uint64_t dm = 0;

@@ -57,6 +57,7 @@
 
 #include <string>
 
+#include "batch_launch.hpp"
 #include "common.hpp"
 #include "ctx.hpp"
 #include "tsp_batch_dp.hpp"
@@ -333,23 +334,6 @@ __global__ __launch_bounds__(256) void vrp_batch_tdsp_kernel(BatchTdspArgs a) {
   a.keys[req] = cvrp_key((uint32_t)(n - __popc(served)), dsum, dmax, OBJ);
 }
 
-template <int T>
-static hipError_t batch_tdsp_launch(const BatchTdspArgs& a, int objective, size_t lds, hipStream_t s) {
-  const bool atomic = batch_tdp_atomic(a.W), mx = objective == VRPMS_OBJ_MAX;
-  void (*fn)(BatchTdspArgs) =
-      atomic ? (mx ? vrp_batch_tdsp_kernel<T, 1, 1> : vrp_batch_tdsp_kernel<T, 1, 0>)
-             : (mx ? vrp_batch_tdsp_kernel<T, 0, 1> : vrp_batch_tdsp_kernel<T, 0, 0>);
-  if (lds > 65536) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  const int per_wg = 256 / T;
-  const unsigned blocks = (unsigned)(((int64_t)a.R + per_wg - 1) / per_wg);
-  fn<<<blocks, 256, lds, s>>>(a);
-  return hipGetLastError();
-}
-
 // the argument checks both entry points share, in the established order; N
 // is n + 1 and what the message names is chosen by `launch`
 static int batch_tdsp_check(const char* who, bool launch, int n, int K, int G, int H, int W) {
@@ -374,13 +358,6 @@ static int batch_tdsp_check(const char* who, bool launch, int n, int K, int G, i
   return VRPMS_OK;
 }
 
-static int batch_tdsp_team_check(const char* who, int team) {
-  if (!batch_tdp_team_ok(team))
-    return fail(VRPMS_EINVAL, std::string(who) + ": team must be 0 (auto), 16, 32, 64, 128 or 256 (" +
-                                  std::to_string(team) + " given)");
-  return VRPMS_OK;
-}
-
 }  // namespace vrpms
 
 using namespace vrpms;
@@ -388,9 +365,9 @@ using namespace vrpms;
 extern "C" int vrpms_vrp_batch_tdsp_lds(int32_t n, int32_t K, int32_t G, int32_t H, int32_t W,
                                         int32_t team, uint64_t* bytes) {
   if (!bytes) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_tdsp_lds: bytes is NULL");
-  int rc = batch_tdsp_check("vrpms_vrp_batch_tdsp_lds", false, n, K, G, H, W);
+  const int rc = batch_tdsp_check("vrpms_vrp_batch_tdsp_lds", false, n, K, G, H, W);
   if (rc != VRPMS_OK) return rc;
-  if ((rc = batch_tdsp_team_check("vrpms_vrp_batch_tdsp_lds", team)) != VRPMS_OK) return rc;
+  if (!batch_team_ok(team)) return batch_team_fail("vrpms_vrp_batch_tdsp_lds", team);
   *bytes = batch_tdsp_lds_bytes(n, K, G, H, W, team ? team : batch_tdsp_auto_team(n, K, G, H, W));
   return VRPMS_OK;
 }
@@ -403,11 +380,11 @@ extern "C" int vrpms_vrp_batch_tdsp(vrpms_ctx* ctx, const int32_t* d_mats, const
                                     void* stream) {
   if (!ctx) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_tdsp: ctx is NULL");
   if (R < 0) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_tdsp: R must not be negative");
-  int rc = batch_tdsp_check("vrpms_vrp_batch_tdsp", true, N - 1, K, G, H, W);
+  const int rc = batch_tdsp_check("vrpms_vrp_batch_tdsp", true, N - 1, K, G, H, W);
   if (rc != VRPMS_OK) return rc;
   if (objective != VRPMS_OBJ_SUM && objective != VRPMS_OBJ_MAX)
     return fail(VRPMS_EINVAL, "vrpms_vrp_batch_tdsp: objective must be VRPMS_OBJ_SUM or VRPMS_OBJ_MAX");
-  if ((rc = batch_tdsp_team_check("vrpms_vrp_batch_tdsp", team)) != VRPMS_OK) return rc;
+  if (!batch_team_ok(team)) return batch_team_fail("vrpms_vrp_batch_tdsp", team);
   if (R == 0) return VRPMS_OK;
   if (!d_mats || !d_demand || !d_cap || !d_start || !d_horizon || !d_tours || !d_keys || !d_durs)
     return fail(VRPMS_EINVAL,
@@ -424,14 +401,13 @@ extern "C" int vrpms_vrp_batch_tdsp(vrpms_ctx* ctx, const int32_t* d_mats, const
   VRPMS_HIP(hipSetDevice(ctx->device));
   const BatchTdspArgs a{d_mats, d_demand, d_cap, d_start, d_horizon, R, N, K, G, H, W, d_tours, d_keys, d_durs};
   hipStream_t s = (hipStream_t)stream;
-  hipError_t e = hipSuccess;
-  switch (T) {
-    case 16: e = batch_tdsp_launch<16>(a, objective, lds, s); break;
-    case 32: e = batch_tdsp_launch<32>(a, objective, lds, s); break;
-    case 64: e = batch_tdsp_launch<64>(a, objective, lds, s); break;
-    case 128: e = batch_tdsp_launch<128>(a, objective, lds, s); break;
-    default: e = batch_tdsp_launch<256>(a, objective, lds, s); break;
-  }
+  const bool atomic = batch_tdp_atomic(W), mx = objective == VRPMS_OBJ_MAX;
+  const hipError_t e = batch_with_team(T, [&](auto t) {
+    constexpr int TT = decltype(t)::value;
+    return batch_launch(atomic ? (mx ? vrp_batch_tdsp_kernel<TT, 1, 1> : vrp_batch_tdsp_kernel<TT, 1, 0>)
+                               : (mx ? vrp_batch_tdsp_kernel<TT, 0, 1> : vrp_batch_tdsp_kernel<TT, 0, 0>),
+                        a, R, T, lds, s);
+  });
   VRPMS_HIP(e);
   return VRPMS_OK;
 }

@@ -212,6 +212,7 @@ class TspBatcher:
     replicas only), one launch thread per device, so they run together."""
 
     MIN_N, MAX_N = 4, 190        # compact nodes; N*N int32 must fit the LDS
+    FIELDS = ()                  # per-job fields a launch takes, one list each, after the instances
 
     def __init__(self, app, window_s: float = 0.005, steps: int = 2000, max_batch: int = 16384,
                  launch=None):
@@ -263,12 +264,15 @@ class TspBatcher:
         """Blocks until the request's launch finished -> the TSP slot dict."""
         job = {"ci": ci, "done": threading.Event()}
         self._wait(job)
-        path = [0] + list(job["tour"]) + [0]
+        return self._result(job)
+
+    @staticmethod
+    def _result(job) -> dict:
+        from . import solver
         duration = job.get("duration")
         if duration is None:  # a launch that returns tours only (tests' stand-in launches)
-            D = ci.durations[0]
-            duration = int(sum(int(D[a][b]) for a, b in zip(path, path[1:])))
-        return {"duration": duration, "vehicle": [ci.nodes[c] for c in path]}
+            duration = solver._td_duration(job["ci"], job["tour"])
+        return solver.tsp_result(job["ci"], job["tour"], duration)
 
     def _loop(self):
         while True:
@@ -281,20 +285,18 @@ class TspBatcher:
             groups = {}
             for job in batch:
                 groups.setdefault(self.group_key(job), []).append(job)
-            for N, jobs in groups.items():
+            for key, jobs in groups.items():
                 dev = self.devices[self._rr % len(self.devices)]
                 self._rr += 1
                 if self._pool is None:
-                    self._run(N, jobs, dev)
+                    self._run(key, jobs, dev)
                 else:
-                    self._pool.submit(self._run, N, jobs, dev)
+                    self._pool.submit(self._run, key, jobs, dev)
 
-    def _run(self, N, jobs, dev):
+    def _run(self, key, jobs, dev):
         try:
-            if len(self.devices) > 1:
-                res = self._launch(N, [j["ci"] for j in jobs], dev)
-            else:
-                res = self._launch(N, [j["ci"] for j in jobs])
+            args = [key, [j["ci"] for j in jobs]] + [[j[f] for j in jobs] for f in self.FIELDS]
+            res = self._launch(*args, dev) if len(self.devices) > 1 else self._launch(*args)
             tours, durs = res if isinstance(res, tuple) else (res, None)
             with self._cv:
                 self.launches += 1
@@ -338,191 +340,117 @@ class TspBatcher:
         return tours, durs
 
 
-class ExactTspBatcher(TspBatcher):
-    """Coalesces concurrent exact small-TSP requests -- ("tsp", "dp") on the
-    inline route and ("tsp", "bf") on the endpoint -- into one `tsp_batch_dp`
-    launch per node count (spec A18: each request's Held-Karp table in LDS).
-    The queue, the window, the grouping, the device round-robin and the error
-    fan-out are TspBatcher's; only the admission rule and the launch differ.
-    Unlike the SA batcher's, a batched answer does not depend on the batch: it
-    is the unbatched answer of the same request, key and tour."""
-
-    MIN_N, MAX_N = 2, 13         # 1..12 customers (solver.BATCH_DP_MAX_CUSTOMERS)
-
-    def __init__(self, app, window_s: float = 0.005, max_batch: int = 16384, launch=None):
-        super().__init__(app, window_s, steps=0, max_batch=max_batch, launch=launch)
-
-    @classmethod
-    def accepts(cls, ci) -> bool:
-        """Static matrices of 1..12 customers that pass the A9 int32 guard
-        vrpms_set_instance applies on the unbatched path (with the request's
-        start time, as there); anything else takes the unbatched path, so
-        both paths share one error contract."""
-        from . import solver
-        if ci.durations.shape[0] != 1 or not cls.MIN_N <= ci.N <= cls.MAX_N:
-            return False
-        return solver.batch_dp_guard(ci)
-
-    def _gpu_launch(self, N, cis, device=None):
-        """-> (tours, durations) on `device` (default: the app's first)."""
-        from . import solver
-        dev = self.devices[0] if device is None else device
-        with self.app.locks[dev]:
-            return solver.batch_dp_launch(solver.context(dev), cis)
-
-
-class ExactVrpBatcher(TspBatcher):
-    """Coalesces concurrent exact small-fleet requests -- ("vrp", "sp") on the
-    inline route -- into one `vrp_batch_sp` launch per (node count, fleet size,
-    objective) (spec A19: each request's partition DP in LDS).  The queue, the
-    window, the device round-robin and the error fan-out are TspBatcher's.  A
-    batched answer does not depend on the batch: it is the unbatched answer of
-    the same request.  ("vrp", "bf") does not ride it: bf is the optimum over
-    greedy-split giant tours, a different and sometimes worse answer."""
-
-    def __init__(self, app, window_s: float = 0.005, max_batch: int = 16384, launch=None):
-        super().__init__(app, window_s, steps=0, max_batch=max_batch, launch=launch)
-
-    @classmethod
-    def accepts(cls, ci) -> bool:
-        """Static matrices of at least one customer whose (n, K) is inside
-        A19's LDS domain (solver.batch_sp_fits) and that pass the int32 guards
-        vrpms_set_instance applies on the unbatched path; anything else takes
-        the unbatched path, so both paths share one error contract."""
-        from . import solver
-        return solver.batch_sp_fits(ci) and solver.batch_sp_guard(ci)
-
-    @staticmethod
-    def group_key(job):
-        return job["ci"].N, len(job["ci"].capacities), job["objective"]
-
-    def solve(self, ci, objective: str = "sum") -> dict:
-        """Blocks until the request's launch finished -> the VRP slot dict."""
-        from . import solver
-        job = {"ci": ci, "objective": "max" if objective == "max" else "sum",
-               "done": threading.Event()}
-        self._wait(job)
-        return solver.sp_result(ci, list(job["tour"]), job["duration"])
-
-    def _gpu_launch(self, key, cis, device=None):
-        """-> (tours, route durations) on `device` (default: the app's first)."""
-        from . import solver
-        dev = self.devices[0] if device is None else device
-        with self.app.locks[dev]:
-            return solver.batch_sp_launch(solver.context(dev), cis, key[2])
-
-
-class ExactTdpBatcher(TspBatcher):
-    """Coalesces concurrent exact time-dependent small-TSP requests -- ("tsp",
-    "tdp") on the inline route -- into one `tsp_batch_tdp` launch per (node
-    count, hour count) (spec A20: each request's time-expanded table in LDS).
+class ExactBatcher(TspBatcher):
+    """What the exact batchers share: one launch of solver.BATCH_KINDS[KIND]
+    per group key (the kind's, plus the objective where the jobs carry one).
     The queue, the window, the device round-robin and the error fan-out are
-    TspBatcher's; a job carries its own upper bound, and the launch takes the
-    group's bounds next to its instances.  A batched answer does not depend on
+    TspBatcher's.  Unlike the SA batcher's, a batched answer does not depend on
     the batch: it is the unbatched answer of the same request."""
 
+    KIND = None
+
     def __init__(self, app, window_s: float = 0.005, max_batch: int = 16384, launch=None):
         super().__init__(app, window_s, steps=0, max_batch=max_batch, launch=launch)
 
     @classmethod
     def accepts(cls, ci, bound=None) -> bool:
-        """Requests inside A20's LDS domain for their bound (solver.
-        batch_tdp_fits: 1..11 customers, static or 24 slices, the row width
-        the bound implies) that pass the A9 int32 guard vrpms_set_instance
-        applies on the unbatched path; anything else takes the unbatched path,
-        so both paths share one error contract."""
+        """Requests inside the kind's LDS domain (for their bound, where the
+        kind has one) that pass the int32 guards vrpms_set_instance applies on
+        the unbatched path; anything else takes the unbatched path, so both
+        paths share one error contract."""
         from . import solver
-        return solver.batch_tdp_fits(ci, bound) and solver.batch_dp_guard(ci)
+        return solver.BATCH_KINDS[cls.KIND].fits(ci, bound) and \
+            solver.batch_guard_message(ci) is None
 
-    @staticmethod
-    def group_key(job):
-        return job["ci"].N, job["ci"].durations.shape[0]
+    @classmethod
+    def group_key(cls, job):
+        from . import solver
+        key = solver.BATCH_KINDS[cls.KIND].key(job["ci"])
+        return key + (job["objective"],) if "objective" in job else key
+
+    def _solved(self, ci, **fields):
+        """Blocks until the request's launch finished -> its slot dict."""
+        from . import solver
+        job = {"ci": ci, "done": threading.Event(), **fields}
+        self._wait(job)
+        if ci.problem != solver.TSP:
+            return solver.sp_result(ci, list(job["tour"]), job["duration"])
+        if "duration" not in job and "bound" in job and not any(job["tour"]) and ci.n > 0:
+            raise ValueError(f"no tour within upper_bound = {job['bound']} minutes")
+        return self._result(job)
+
+    def _gpu_launch(self, key, cis, *rest):
+        """-> (tours, durations) on the device that follows the job fields in
+        `rest` (default: the app's first)."""
+        from . import solver
+        bounds = rest[0] if self.FIELDS else None
+        dev = rest[len(self.FIELDS)] if len(rest) > len(self.FIELDS) else self.devices[0]
+        objective = key[-1] if cis[0].problem != solver.TSP else "sum"
+        with self.app.locks[dev]:
+            return solver.BATCH_KINDS[self.KIND].launch(solver.context(dev), cis, bounds, objective)
+
+
+def _objective(objective):
+    return "max" if objective == "max" else "sum"
+
+
+class ExactTspBatcher(ExactBatcher):
+    """("tsp", "dp") on the inline route and ("tsp", "bf") on the endpoint: one
+    `tsp_batch_dp` launch per node count (spec A18: each request's Held-Karp
+    table in LDS)."""
+
+    KIND = "dp"
+    MIN_N, MAX_N = 2, 13         # 1..12 customers (solver.BATCH_DP_MAX_CUSTOMERS)
+
+    @classmethod
+    def accepts(cls, ci) -> bool:
+        """Static matrices of 1..12 customers that pass the A9 guard (with the
+        request's start time, as vrpms_set_instance applies it)."""
+        from . import solver
+        return ci.durations.shape[0] == 1 and cls.MIN_N <= ci.N <= cls.MAX_N and \
+            solver.batch_dp_guard(ci)
+
+    def solve(self, ci) -> dict:
+        return self._solved(ci)
+
+
+class ExactVrpBatcher(ExactBatcher):
+    """("vrp", "sp") on the inline route: one `vrp_batch_sp` launch per (node
+    count, fleet size, objective) (spec A19: each request's partition DP in
+    LDS).  ("vrp", "bf") does not ride it: bf is the optimum over greedy-split
+    giant tours, a different and sometimes worse answer."""
+
+    KIND = "sp"
+
+    def solve(self, ci, objective: str = "sum") -> dict:
+        return self._solved(ci, objective=_objective(objective))
+
+
+class ExactTdpBatcher(ExactBatcher):
+    """("tsp", "tdp") on the inline route: one `tsp_batch_tdp` launch per (node
+    count, hour count) (spec A20: each request's time-expanded table in LDS).
+    A job carries its own upper bound, and the launch takes the group's bounds
+    next to its instances."""
+
+    KIND = "tdp"
+    FIELDS = ("bound",)
 
     def solve(self, ci, bound) -> dict:
-        """Blocks until the request's launch finished -> the TSP slot dict."""
-        from . import solver
-        job = {"ci": ci, "bound": int(bound), "done": threading.Event()}
-        self._wait(job)
-        duration = job.get("duration")
-        if duration is None and not any(job["tour"]) and ci.n > 0:
-            raise ValueError(f"no tour within upper_bound = {int(bound)} minutes")
-        if duration is None:  # a launch that returns tours only (tests' stand-in launches)
-            duration = solver._td_duration(ci, job["tour"])
-        path = [0] + list(job["tour"]) + [0]
-        return {"duration": duration, "vehicle": [ci.nodes[c] for c in path]}
-
-    def _run(self, key, jobs, dev):
-        try:
-            args = (key, [j["ci"] for j in jobs], [j["bound"] for j in jobs])
-            res = self._launch(*args, dev) if len(self.devices) > 1 else self._launch(*args)
-            tours, durs = res if isinstance(res, tuple) else (res, None)
-            with self._cv:
-                self.launches += 1
-                self.requests += len(jobs)
-                self.per_device[dev] += len(jobs)
-            for x, (j, t) in enumerate(zip(jobs, tours)):
-                j["tour"] = t
-                if durs is not None and durs[x] is not None:
-                    j["duration"] = durs[x]
-        except Exception as e:         # every waiter of the group sees it
-            for j in jobs:
-                j["error"] = e
-        for j in jobs:
-            j["done"].set()
-
-    def _gpu_launch(self, key, cis, bounds, device=None):
-        """-> (tours, durations) on `device` (default: the app's first)."""
-        from . import solver
-        dev = self.devices[0] if device is None else device
-        with self.app.locks[dev]:
-            return solver.batch_tdp_launch(solver.context(dev), cis, bounds)
+        return self._solved(ci, bound=int(bound))
 
 
-class ExactTdspBatcher(TspBatcher):
-    """Coalesces concurrent exact time-dependent small-fleet requests --
-    ("vrp", "tdsp") on the inline route -- into one `vrp_batch_tdsp` launch per
+class ExactTdspBatcher(ExactBatcher):
+    """("vrp", "tdsp") on the inline route: one `vrp_batch_tdsp` launch per
     (node count, fleet size, hour count, number of distinct start times,
     objective) (spec A21: each request's time-expanded partition DP in LDS).
-    The queue, the window, the device round-robin and the error fan-out are
-    TspBatcher's; a job carries its own upper bound and objective, and the
-    launch takes the group's bounds next to its instances.  A batched answer
-    does not depend on the batch: it is the unbatched answer of the same
-    request."""
+    A job carries its own upper bound and objective, and the launch takes the
+    group's bounds next to its instances."""
 
-    def __init__(self, app, window_s: float = 0.005, max_batch: int = 16384, launch=None):
-        super().__init__(app, window_s, steps=0, max_batch=max_batch, launch=launch)
-
-    @classmethod
-    def accepts(cls, ci, bound=None) -> bool:
-        """Requests inside A21's LDS domain for their bound
-        (solver.batch_tdsp_fits) that pass the int32 guards vrpms_set_instance
-        applies on the unbatched path; anything else takes the unbatched path,
-        so both paths share one error contract."""
-        from . import solver
-        return solver.batch_tdsp_fits(ci, bound) and solver.batch_sp_guard(ci)
-
-    @staticmethod
-    def group_key(job):
-        ci = job["ci"]
-        return (ci.N, len(ci.capacities), ci.durations.shape[0],
-                len(set(int(s) for s in ci.start_times)), job["objective"])
+    KIND = "tdsp"
+    FIELDS = ("bound",)
 
     def solve(self, ci, bound, objective: str = "sum") -> dict:
-        """Blocks until the request's launch finished -> the VRP slot dict."""
-        from . import solver
-        job = {"ci": ci, "bound": int(bound), "objective": "max" if objective == "max" else "sum",
-               "done": threading.Event()}
-        self._wait(job)
-        return solver.sp_result(ci, list(job["tour"]), job["duration"])
-
-    _run = ExactTdpBatcher._run
-
-    def _gpu_launch(self, key, cis, bounds, device=None):
-        """-> (tours, route durations) on `device` (default: the app's first)."""
-        from . import solver
-        dev = self.devices[0] if device is None else device
-        with self.app.locks[dev]:
-            return solver.batch_tdsp_launch(solver.context(dev), cis, bounds, key[4])
+        return self._solved(ci, bound=int(bound), objective=_objective(objective))
 
 
 # ---------------------------------------------------------------------------
@@ -585,10 +513,11 @@ class App:
         busy."""
         n = len(params.get("customers") or []) if problem == "tsp" else \
             max(0, len(locations or []) - 1)
+        from .solver import EXACT_ALGORITHMS
         knobs = dict(knobs)
         mt = multi_threaded(knobs.get("multi_threaded"))
         islands = n > self.island_min_n if mt is None else mt
-        if len(self.devices) > 1 and algorithm not in ("bf", "dp", "sp", "tdp", "tdsp") and islands:
+        if len(self.devices) > 1 and algorithm not in ("bf",) + EXACT_ALGORITHMS and islands:
             held = sorted(set(self.devices))   # each lock once, in one global order
             for d in held:
                 self.locks[d].acquire()
@@ -623,41 +552,33 @@ class App:
                                 params["start_time"] or 0)
         return ci if batcher.accepts(ci) else None
 
-    def _batched_vrp(self, params, durations, locations):
-        """The compact instance when this ("vrp", "sp") request rides the
-        exact VRP batcher, else None."""
-        if self.exact_vrp_batcher is None:
-            return None
-        from . import solver
-        ci = solver.compact_vrp(durations, locations, params["capacities"], params["start_times"],
-                                params["ignored_customers"], params["completed_customers"])
-        return ci if self.exact_vrp_batcher.accepts(ci) else None
+    def _exact_batcher(self, problem, algorithm):
+        """The exact batcher of an inline (problem, algorithm), or None."""
+        return {("tsp", "dp"): self.exact_batcher, ("vrp", "sp"): self.exact_vrp_batcher,
+                ("tsp", "tdp"): self.exact_tdp_batcher,
+                ("vrp", "tdsp"): self.exact_tdsp_batcher}.get((problem, algorithm))
 
-    def _batched_tdp(self, params, durations, upper_bound=None):
-        """(compact instance, bound) when this ("tsp", "tdp") request rides the
-        exact time-dependent batcher, else None.  A request outside A16's
-        domain raises here what the unbatched path raises for it."""
-        if self.exact_tdp_batcher is None:
-            return None
+    def _batched(self, batcher, params, knobs, locations, durations):
+        """batcher.solve's arguments when this inline request rides the exact
+        `batcher`, else None.  Where the kind has an upper bound, a request
+        outside its domain raises here what the unbatched path raises for it."""
         from . import solver
-        ci = solver.compact_tsp(durations, params["customers"], params["start_node"],
-                                params["start_time"] or 0)
-        bound = solver.batch_tdp_bound(ci, upper_bound)
-        return (ci, bound) if self.exact_tdp_batcher.accepts(ci, bound) else None
-
-    def _batched_tdsp(self, params, durations, locations, objective="sum", upper_bound=None):
-        """(compact instance, bound, objective) when this ("vrp", "tdsp")
-        request rides the exact time-dependent fleet batcher, else None.  A
-        request outside A17's domain raises here what the unbatched path
-        raises for it."""
-        if self.exact_tdsp_batcher is None:
+        kind = solver.BATCH_KINDS[batcher.KIND]
+        objective = knobs.get("objective", "sum")
+        if kind.problem == solver.TSP:
+            ci = solver.compact_tsp(durations, params["customers"], params["start_node"],
+                                    params["start_time"] or 0)
+        else:
+            ci = solver.compact_vrp(durations, locations, params["capacities"],
+                                    params["start_times"], params["ignored_customers"],
+                                    params["completed_customers"])
+        args = [ci]
+        if batcher.FIELDS:
+            args.append(kind.check(ci, solver.OBJ_MAX if objective == "max" else solver.OBJ_SUM,
+                                   knobs["inline"].get("upper_bound")))
+        if not batcher.accepts(*args):
             return None
-        from . import solver
-        ci = solver.compact_vrp(durations, locations, params["capacities"], params["start_times"],
-                                params["ignored_customers"], params["completed_customers"])
-        bound = solver._check_tdsp(ci, solver.OBJ_MAX if objective == "max" else solver.OBJ_SUM,
-                                   upper_bound)
-        return (ci, bound, objective) if self.exact_tdsp_batcher.accepts(ci, bound) else None
+        return args if kind.problem == solver.TSP else args + [objective]
 
     def _gpu_solve(self, problem, algorithm, params, knobs, locations, durations):
         """knobs may carry "seed", "time_limit" and "objective" (the /solve
@@ -795,25 +716,11 @@ class App:
             return 400, {"success": False,
                          "errors": [{"what": "Invalid request", "reason": str(e)}]}
         try:
-            ci = self._batched_tsp(params, vals["durations"], self.exact_batcher) \
-                if (problem, algorithm) == ("tsp", "dp") and self.exact_batcher is not None else None
-            vrp_ci = self._batched_vrp(params, vals["durations"], locations) \
-                if (problem, algorithm) == ("vrp", "sp") else None
-            tdp = self._batched_tdp(params, vals["durations"],
-                                    knobs["inline"].get("upper_bound")) \
-                if (problem, algorithm) == ("tsp", "tdp") else None
-            tdsp = self._batched_tdsp(params, vals["durations"], locations,
-                                      knobs.get("objective", "sum"),
-                                      knobs["inline"].get("upper_bound")) \
-                if (problem, algorithm) == ("vrp", "tdsp") else None
-            if ci is not None:
-                result = self.exact_batcher.solve(ci)
-            elif tdsp is not None:
-                result = self.exact_tdsp_batcher.solve(*tdsp)
-            elif tdp is not None:
-                result = self.exact_tdp_batcher.solve(*tdp)
-            elif vrp_ci is not None:
-                result = self.exact_vrp_batcher.solve(vrp_ci, knobs.get("objective", "sum"))
+            batcher = self._exact_batcher(problem, algorithm)
+            args = self._batched(batcher, params, knobs, locations, vals["durations"]) \
+                if batcher is not None else None
+            if args is not None:
+                result = batcher.solve(*args)
             else:
                 result = self._scheduled(problem, algorithm, params, knobs, locations,
                                          vals["durations"])

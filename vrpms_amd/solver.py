@@ -40,6 +40,9 @@ from . import runners
 from .core import CVRP, OBJ_MAX, OBJ_SUM, TSP, Context
 
 ALGORITHMS = ("bf", "ga", "sa", "aco", "dp", "sp", "tdp", "tdsp")
+# the exact algorithms with kernels of their own: one device, no island model
+# (the exhaustive "bf" shares that with them)
+EXACT_ALGORITHMS = ("dp", "sp", "tdp", "tdsp")
 # exhaustive search over n! giant tours: 13! = 6.2 G tours is ~0.1 s at the
 # measured ~64 G evals/s of bf_kernel on one MI355X (bench "search.bf") on a
 # static matrix; an hour-indexed one prices every edge at its departure
@@ -373,7 +376,7 @@ def search_islands(ci: CompactInstance, algorithm: str, devices, seed: int = 0,
     island."""
     import torch
     from . import islands
-    if ci.n <= 1 or algorithm in ("bf", "dp", "sp", "tdp", "tdsp"):
+    if ci.n <= 1 or algorithm in ("bf",) + EXACT_ALGORITHMS:
         raise ValueError("search_islands: SA / GA / ACO on two or more customers")
     rs, epochs = [], 1
     for d, dev in enumerate(devices):
@@ -442,6 +445,11 @@ def _decode(ctx: Context, tour):
     return ctx.decode(t, len(tour))
 
 
+def tsp_result(ci: CompactInstance, tour, duration) -> dict:
+    """The TSP slot dict from a compact tour, mapped back through ci.nodes."""
+    return {"duration": duration, "vehicle": [ci.nodes[c] for c in [0] + list(tour) + [0]]}
+
+
 def _remote():
     """VRPMS_REMOTE set and no local GPU: the GPU box's URL (vrpms_amd.remote)."""
     from . import remote
@@ -454,11 +462,12 @@ def _remote():
 def _searched(ci, algorithm, seed, time_limit, device, devices, objective, knobs):
     """(context holding the instance, compact tour): one device, or the
     island model across `devices` (two or more) for SA / GA / ACO."""
-    if devices is not None and len(devices) > 1 and algorithm not in ("bf", "dp", "sp", "tdp", "tdsp") and ci.n > 1:
+    if devices is not None and len(devices) > 1 and ci.n > 1 and \
+            algorithm not in ("bf",) + EXACT_ALGORITHMS:
         _, tour = search_islands(ci, algorithm, list(devices), seed=seed, time_limit=time_limit,
                                  objective=objective, **knobs)
         return context(devices[0]), tour
-    if algorithm in ("dp", "sp", "tdp", "tdsp") and devices:
+    if algorithm in EXACT_ALGORITHMS and devices:
         device = devices[0]
     ctx = context(device)
     load(ctx, ci, objective)
@@ -499,209 +508,7 @@ def solve_tsp(algorithm: str, durations, customers, start_node, start_time=0, *,
         ci = compact_tsp(durations, customers, start_node, start_time)
     ctx, tour = _searched(ci, algorithm, seed, time_limit, device, devices, OBJ_SUM, knobs)
     _, dur = _decode(ctx, tour)
-    vehicle = [ci.nodes[0]] + [ci.nodes[c] for c in tour] + [ci.nodes[0]]
-    return {"duration": int(dur[0]), "vehicle": vehicle}
-
-
-def batch_dp_guard(ci: CompactInstance) -> bool:
-    """The A9 int32 guard vrpms_set_instance applies to this request on the
-    single-request path (start + (N + K + 1) * max_duration < 2^31, K = 1);
-    it implies A18's N * max(D) < 2^31."""
-    mx = int(ci.durations.max()) if ci.durations.size else 0
-    return int(ci.start_times[0]) + (ci.N + 2) * mx < 2**31
-
-
-def batch_dp_launch(ctx: Context, cis):
-    """One upload and one tsp_batch_dp launch for compact instances of one
-    node count (each passed batch_dp_guard) -> (tours, durations), one row per
-    instance.  A duration is the key's primary field (A8: a TSP key is
-    duration << 28), exact below the 2^28 - 1 clamp; a clamped one is summed
-    on the host."""
-    import torch
-    N = cis[0].N
-    host = np.empty((len(cis), N, N), dtype=np.int32)
-    for x, ci in enumerate(cis):
-        host[x] = ci.durations[0]
-    tours, keys = ctx.tsp_batch_dp(torch.from_numpy(host).to(ctx.dev))
-    tours, keys = tours.cpu().tolist(), keys.cpu().tolist()
-    clamp = (1 << 28) - 1
-    durs = []
-    for ci, tour, k in zip(cis, tours, keys):
-        d = (k >> 28) & clamp
-        if d == clamp:
-            path = [0] + tour + [0]
-            d = int(sum(int(ci.durations[0][a][b]) for a, b in zip(path, path[1:])))
-        durs.append(int(d))
-    return tours, durs
-
-
-def batch_tdp_bound(ci: CompactInstance, upper_bound=None):
-    """_check_tdp for a request that may ride a tsp_batch_tdp launch -> the
-    bound its row width follows from.  One customer has the single path's
-    trivial answer whatever `upper_bound` says, so its bound is its one tour's
-    duration; no customer has none."""
-    bound = _check_tdp(ci, upper_bound)
-    if ci.n == 1:
-        bound = runners.nearest_neighbour_duration(ci.durations, 1, int(ci.start_times[0]))
-    return bound
-
-
-def batch_tdp_fits(ci: CompactInstance, bound) -> bool:
-    """A20's domain: 1..BATCH_TDP_MAX_CUSTOMERS customers and one request of
-    (n, H, W) -- W the hour words of `bound` from the request's start -- within
-    BATCH_TDP_LDS_BYTES.  Needs the library, no GPU."""
-    from .core import tdp_words, tsp_batch_tdp_lds
-    if ci.problem != TSP or not 1 <= ci.n <= BATCH_TDP_MAX_CUSTOMERS or bound is None:
-        return False
-    H = ci.durations.shape[0]
-    start = int(ci.start_times[0])
-    W = tdp_words(start, bound)
-    if H not in (1, 24) or W > TDP_MAX_WORDS or start + int(bound) >= 2**31:
-        return False
-    return tsp_batch_tdp_lds(ci.n, H, W) <= BATCH_TDP_LDS_BYTES
-
-
-def _td_duration(ci: CompactInstance, tour) -> int:
-    """The tour's duration under the A3 clock, on the host."""
-    D, H = ci.durations, ci.durations.shape[0]
-    t0 = t = int(ci.start_times[0])
-    path = [0] + list(tour) + [0]
-    for a, b in zip(path, path[1:]):
-        t += int(D[(t // 60) % H][a][b])
-    return t - t0
-
-
-def batch_tdp_launch(ctx: Context, cis, bounds):
-    """One upload and one tsp_batch_tdp launch for compact instances of one
-    (N, H) (each passed batch_dp_guard and batch_tdp_fits with its bound), W
-    the largest of their row widths -> (tours, durations), one row per
-    instance; the duration is None where no tour fits the request's bound.  A
-    duration is the key's primary field, exact below the 2^28 - 1 clamp; a
-    clamped one is summed on the host."""
-    import torch
-    N, H = cis[0].N, cis[0].durations.shape[0]
-    host = np.empty((len(cis), H, N, N), dtype=np.int32)
-    for x, ci in enumerate(cis):
-        host[x] = ci.durations
-    starts = np.array([int(ci.start_times[0]) for ci in cis], dtype=np.int64)
-    tours, keys = ctx.tsp_batch_tdp(torch.from_numpy(host).to(ctx.dev), starts,
-                                    np.array([int(b) for b in bounds], dtype=np.int64))
-    tours, keys = tours.cpu().tolist(), keys.cpu().tolist()
-    clamp = (1 << 28) - 1
-    durs = []
-    for ci, tour, k in zip(cis, tours, keys):
-        if k == -1:
-            durs.append(None)
-            continue
-        d = (k >> 28) & clamp
-        durs.append(_td_duration(ci, tour) if d == clamp else int(d))
-    return tours, durs
-
-
-def _solve_tdp_batch(requests, device: int) -> list:
-    """solve_tsp_batch("tdp")."""
-    reqs, cis, bounds, knobs = [], [], [], []
-    for x, r in enumerate(requests):
-        if isinstance(r, dict):
-            r = (r["durations"], r["customers"], r["start_node"], r.get("start_time", 0),
-                 r.get("upper_bound"))
-        r = tuple(r)
-        r = r + (0,) * (4 - len(r)) if len(r) < 4 else r
-        ub = r[4] if len(r) > 4 else None
-        try:
-            ci = compact_tsp(*r[:4])
-            bound = batch_tdp_bound(ci, ub)
-            if not batch_dp_guard(ci):
-                raise ValueError("start + (N+K+1)*max_duration overflows int32 (A9 guard)")
-        except ValueError as e:
-            raise ValueError(f"request {x}: {e}") from None
-        reqs.append(r[:4])
-        cis.append(ci)
-        bounds.append(bound)
-        knobs.append({} if ub is None else {"upper_bound": ub})
-    if _remote() is not None:      # no local GPU: the GPU box answers each request
-        return [solve_tsp("tdp", *r, **k) for r, k in zip(reqs, knobs)]
-    out = [None] * len(cis)
-    groups: dict = {}
-    for x, ci in enumerate(cis):
-        if batch_tdp_fits(ci, bounds[x]):
-            groups.setdefault((ci.N, ci.durations.shape[0]), []).append(x)
-        else:
-            out[x] = solve_tsp("tdp", *reqs[x], device=device, **knobs[x])
-    if groups:
-        ctx = context(device)
-        for xs in groups.values():
-            tours, durs = batch_tdp_launch(ctx, [cis[x] for x in xs], [bounds[x] for x in xs])
-            for x, tour, dur in zip(xs, tours, durs):
-                if dur is None:
-                    raise ValueError(f"request {x}: no tour within upper_bound = "
-                                     f"{int(bounds[x])} minutes")
-                nodes = cis[x].nodes
-                out[x] = {"duration": dur,
-                          "vehicle": [nodes[0]] + [nodes[c] for c in tour] + [nodes[0]]}
-    return out
-
-
-def solve_tsp_batch(algorithm: str, requests, *, device: int = 0) -> list:
-    """[solve_tsp(algorithm, *r) for r in requests], element for element, with
-    the small requests sharing launches.  `requests`: (durations, customers,
-    start_node, start_time) tuples, or dicts with those keys.  "dp" (spec A18)
-    and "tdp" (spec A20) have batched kernels.  Every request is compacted and
-    checked on the host before anything is launched; a bad one raises
-    solve_tsp's message for that algorithm prefixed with its index.
-
-    "dp" (bad: hour-indexed, more than DP_MAX_CUSTOMERS customers, A9 guard):
-    requests of 2..BATCH_DP_MAX_CUSTOMERS customers are grouped by node count,
-    one upload and one tsp_batch_dp launch per group; none or one customer
-    take solve_tsp's trivial path, and 13..24 customers its single-request
-    Held-Karp, one by one.
-
-    "tdp" (static or hour-indexed; bad: more than TDP_MAX_CUSTOMERS customers,
-    a negative bound, a table or a row above the caps, A9 guard): a request may
-    carry a fifth tuple element or an "upper_bound" key, the knob of
-    solve_tsp("tdp") (default: the nearest-neighbour tour's duration).
-    Requests inside A20's LDS domain (batch_tdp_fits: 1..11 customers, the row
-    width the bound implies) are grouped by (node count, hour count), one
-    upload and one tsp_batch_tdp launch per group at the group's largest row
-    width; no customer, 12..20 customers and an (n, W) outside the LDS take
-    solve_tsp("tdp"), one by one."""
-    if algorithm == "tdp":
-        return _solve_tdp_batch(requests, device)
-    if algorithm != "dp":
-        raise ValueError(f'solve_tsp_batch: no batched kernel for algorithm {algorithm!r}; only '
-                         '"dp" (exact Held-Karp) and "tdp" (exact time-expanded DP) are batched')
-    reqs, cis = [], []
-    for x, r in enumerate(requests):
-        if isinstance(r, dict):
-            r = (r["durations"], r["customers"], r["start_node"], r.get("start_time", 0))
-        r = tuple(r) + (0,) * (4 - len(r))
-        try:
-            ci = compact_tsp(*r[:4])
-            _check_dp(ci)
-            if not batch_dp_guard(ci):
-                raise ValueError("start + (N+K+1)*max_duration overflows int32 (A9 guard)")
-        except ValueError as e:
-            raise ValueError(f"request {x}: {e}") from None
-        reqs.append(r[:4])
-        cis.append(ci)
-    if _remote() is not None:      # no local GPU: the GPU box answers each request
-        return [solve_tsp("dp", *r) for r in reqs]
-    out = [None] * len(cis)
-    groups: dict = {}
-    for x, ci in enumerate(cis):
-        if 2 <= ci.n <= BATCH_DP_MAX_CUSTOMERS:
-            groups.setdefault(ci.N, []).append(x)
-        else:
-            out[x] = solve_tsp("dp", *reqs[x], device=device)
-    if groups:
-        ctx = context(device)
-        for N, xs in groups.items():
-            tours, durs = batch_dp_launch(ctx, [cis[x] for x in xs])
-            for x, tour, dur in zip(xs, tours, durs):
-                nodes = cis[x].nodes
-                out[x] = {"duration": dur,
-                          "vehicle": [nodes[0]] + [nodes[c] for c in tour] + [nodes[0]]}
-    return out
+    return tsp_result(ci, tour, int(dur[0]))
 
 
 def solve_vrp(algorithm: str, durations, locations, capacities, start_times,
@@ -775,16 +582,119 @@ def solve_vrp(algorithm: str, durations, locations, capacities, start_times,
     return out
 
 
-def batch_sp_guard(ci: CompactInstance) -> bool:
-    """The two int32 range checks vrpms_set_instance applies to this request
-    on the single-request path: max(start) + (N + K + 1) * max_duration < 2^31
-    (A9; it implies A19's (N + K + 1) * max(D) < 2^31) and max(capacity) +
-    max(demand) < 2^31."""
+# ---------------------------------------------------------------------------
+# batched exact solvers (A18-A21): many small requests share launches
+# ---------------------------------------------------------------------------
+def batch_guard_message(ci: CompactInstance):
+    """The int32 range checks vrpms_set_instance applies to this request on the
+    single-request path -> the failing one's message, or None: max(start) +
+    (N + K + 1) * max_duration < 2^31 (A9, K = 1 for a TSP; it implies the
+    batched kernels' own (N + K + 1) * max(D) < 2^31) and, for a VRP,
+    max(capacity) + max(demand) < 2^31."""
     mx = int(ci.durations.max()) if ci.durations.size else 0
-    K = len(ci.capacities)
+    K = 1 if ci.problem == TSP else len(ci.capacities)
     if int(ci.start_times.max()) + (ci.N + K + 1) * mx >= 2**31:
+        return "start + (N+K+1)*max_duration overflows int32 (A9 guard)"
+    if ci.problem == CVRP and int(ci.capacities.max()) + int(ci.demand.max()) >= 2**31:
+        return "capacity + demand overflows int32"
+    return None
+
+
+def batch_dp_guard(ci: CompactInstance) -> bool:
+    """The request passes batch_guard_message: a TSP the A9 guard with K = 1, a
+    VRP (as batch_sp_guard) the A9 guard and capacity + demand."""
+    return batch_guard_message(ci) is None
+
+
+batch_sp_guard = batch_dp_guard
+
+
+def _stage(ctx: Context, cis, hours: bool = False) -> list:
+    """The int32 device buffers of one launch's instances: the matrices
+    [R][N][N] ([R][H][N][N] with `hours`) and, for a VRP, the demand [R][N] and
+    capacity [R][K] rows.  One staging buffer each, no per-request copies."""
+    import torch
+    D = cis[0].durations
+    host = [np.empty((len(cis),) + (D.shape if hours else D.shape[1:]), dtype=np.int32)]
+    if cis[0].problem == CVRP:
+        host += [np.empty((len(cis), cis[0].N), dtype=np.int32),
+                 np.empty((len(cis), len(cis[0].capacities)), dtype=np.int32)]
+    for x, ci in enumerate(cis):
+        host[0][x] = ci.durations if hours else ci.durations[0]
+        if len(host) > 1:
+            host[1][x], host[2][x] = ci.demand, ci.capacities
+    return [torch.from_numpy(a).to(ctx.dev) for a in host]
+
+
+def _td_duration(ci: CompactInstance, tour) -> int:
+    """The tour's duration under the A3 clock, on the host (on a static
+    matrix: the sum of its edges)."""
+    D, H = ci.durations, ci.durations.shape[0]
+    t0 = t = int(ci.start_times[0])
+    path = [0] + list(tour) + [0]
+    for a, b in zip(path, path[1:]):
+        t += int(D[(t // 60) % H][a][b])
+    return t - t0
+
+
+def _key_durations(cis, tours, keys) -> list:
+    """Per TSP instance the duration its key carries: the primary field (A8: a
+    TSP key is duration << 28), exact below the 2^28 - 1 clamp; a clamped one
+    is priced on the host, and an all-ones key (no tour) gives None."""
+    clamp = (1 << 28) - 1
+    durs = []
+    for ci, tour, k in zip(cis, tours, keys):
+        d = (k >> 28) & clamp
+        durs.append(None if k == -1 else _td_duration(ci, tour) if d == clamp else int(d))
+    return durs
+
+
+def batch_dp_launch(ctx: Context, cis):
+    """One upload and one tsp_batch_dp launch for compact instances of one
+    node count (each passed batch_dp_guard) -> (tours, durations), one row per
+    instance (_key_durations)."""
+    tours, keys = ctx.tsp_batch_dp(*_stage(ctx, cis))
+    tours = tours.cpu().tolist()
+    return tours, _key_durations(cis, tours, keys.cpu().tolist())
+
+
+def batch_tdp_bound(ci: CompactInstance, upper_bound=None):
+    """_check_tdp for a request that may ride a tsp_batch_tdp launch -> the
+    bound its row width follows from.  One customer has the single path's
+    trivial answer whatever `upper_bound` says, so its bound is its one tour's
+    duration; no customer has none."""
+    bound = _check_tdp(ci, upper_bound)
+    if ci.n == 1:
+        bound = runners.nearest_neighbour_duration(ci.durations, 1, int(ci.start_times[0]))
+    return bound
+
+
+def batch_tdp_fits(ci: CompactInstance, bound) -> bool:
+    """A20's domain: 1..BATCH_TDP_MAX_CUSTOMERS customers and one request of
+    (n, H, W) -- W the hour words of `bound` from the request's start -- within
+    BATCH_TDP_LDS_BYTES.  Needs the library, no GPU."""
+    from .core import tdp_words, tsp_batch_tdp_lds
+    if ci.problem != TSP or not 1 <= ci.n <= BATCH_TDP_MAX_CUSTOMERS or bound is None:
         return False
-    return int(ci.capacities.max()) + int(ci.demand.max()) < 2**31
+    H = ci.durations.shape[0]
+    start = int(ci.start_times[0])
+    W = tdp_words(start, bound)
+    if H not in (1, 24) or W > TDP_MAX_WORDS or start + int(bound) >= 2**31:
+        return False
+    return tsp_batch_tdp_lds(ci.n, H, W) <= BATCH_TDP_LDS_BYTES
+
+
+def batch_tdp_launch(ctx: Context, cis, bounds):
+    """One upload and one tsp_batch_tdp launch for compact instances of one
+    (N, H) (each passed batch_dp_guard and batch_tdp_fits with its bound), W
+    the largest of their row widths -> (tours, durations), one row per
+    instance (_key_durations); the duration is None where no tour fits the
+    request's bound."""
+    starts = np.array([int(ci.start_times[0]) for ci in cis], dtype=np.int64)
+    tours, keys = ctx.tsp_batch_tdp(*_stage(ctx, cis, hours=True), starts,
+                                    np.array([int(b) for b in bounds], dtype=np.int64))
+    tours = tours.cpu().tolist()
+    return tours, _key_durations(cis, tours, keys.cpu().tolist())
 
 
 def batch_sp_fits(ci: CompactInstance) -> bool:
@@ -803,16 +713,7 @@ def batch_sp_launch(ctx: Context, cis, objective: str = "sum"):
     (N, K) (each passed batch_sp_guard and batch_sp_fits) -> (tours,
     durations): per instance the n + K tour tokens and the K route
     durations."""
-    import torch
-    N, K = cis[0].N, len(cis[0].capacities)
-    mats = np.empty((len(cis), N, N), dtype=np.int32)
-    dem = np.empty((len(cis), N), dtype=np.int32)
-    caps = np.empty((len(cis), K), dtype=np.int32)
-    for x, ci in enumerate(cis):
-        mats[x], dem[x], caps[x] = ci.durations[0], ci.demand, ci.capacities
-    tours, _, durs = ctx.vrp_batch_sp(torch.from_numpy(mats).to(ctx.dev),
-                                      torch.from_numpy(dem).to(ctx.dev),
-                                      torch.from_numpy(caps).to(ctx.dev),
+    tours, _, durs = ctx.vrp_batch_sp(*_stage(ctx, cis),
                                       OBJ_MAX if objective == "max" else OBJ_SUM)
     return tours.cpu().tolist(), durs.cpu().tolist()
 
@@ -832,66 +733,6 @@ def sp_result(ci: CompactInstance, tour, durs, with_unvisited: bool = False) -> 
     out = {"durationMax": int(max(durs)), "durationSum": int(sum(durs)), "vehicles": vehicles}
     if with_unvisited:
         out["unvisited"] = [ci.nodes[c] for c in tour[at:]]
-    return out
-
-
-_VRP_REQUEST_KEYS = ("durations", "locations", "capacities", "start_times", "ignored_customers",
-                     "completed_customers")
-
-
-def solve_vrp_batch(algorithm: str, requests, *, objective: str = "sum",
-                    with_unvisited: bool = False, device: int = 0) -> list:
-    """[solve_vrp(algorithm, *r, objective=objective, with_unvisited=...) for r
-    in requests], element for element, with the small requests sharing
-    launches.  `requests`: (durations, locations, capacities, start_times[,
-    ignored_customers, completed_customers]) tuples, or dicts with those keys.
-    Only "sp" has a batched kernel (spec A19).  Every request is compacted and
-    checked on the host before anything is launched; a bad one (hour-indexed,
-    more than SP_MAX_CUSTOMERS customers or SP_MAX_VEHICLES vehicles, the int32
-    guards) raises solve_vrp("sp")'s message prefixed with its index.  Requests
-    of 1..BATCH_SP_MAX_CUSTOMERS customers whose (n, K) fits the LDS
-    (batch_sp_fits) are grouped by (N, K), one upload and one vrp_batch_sp
-    launch per group, and their result dicts are built on the host from the
-    tour tokens and the route durations; no customer, 13..20 customers and
-    fleets beyond the LDS take solve_vrp("sp"), one by one.  "tdsp" has a
-    batched kernel of its own behind solve_vrp_tdsp_batch (spec A21)."""
-    if algorithm != "sp":
-        raise ValueError(f'solve_vrp_batch: no batched kernel for algorithm {algorithm!r}; only '
-                         '"sp" (exact set partitioning) is batched')
-    reqs, cis = [], []
-    for x, r in enumerate(requests):
-        if isinstance(r, dict):
-            r = (r["durations"], r["locations"], r["capacities"], r["start_times"],
-                 r.get("ignored_customers", ()), r.get("completed_customers", ()))
-        r = tuple(r) + ((),) * (6 - len(r))
-        try:
-            ci = compact_vrp(*r[:6])
-            _check_sp(ci)
-            if not batch_sp_guard(ci):
-                mx = int(ci.durations.max()) if ci.durations.size else 0
-                if int(ci.start_times.max()) + (ci.N + len(ci.capacities) + 1) * mx >= 2**31:
-                    raise ValueError("start + (N+K+1)*max_duration overflows int32 (A9 guard)")
-                raise ValueError("capacity + demand overflows int32")
-        except ValueError as e:
-            raise ValueError(f"request {x}: {e}") from None
-        reqs.append(r[:6])
-        cis.append(ci)
-    single = dict(objective=objective, with_unvisited=with_unvisited)
-    if _remote() is not None:      # no local GPU: the GPU box answers each request
-        return [solve_vrp("sp", *r, **single) for r in reqs]
-    out = [None] * len(cis)
-    groups: dict = {}
-    for x, ci in enumerate(cis):
-        if batch_sp_fits(ci):
-            groups.setdefault((ci.N, len(ci.capacities)), []).append(x)
-        else:
-            out[x] = solve_vrp("sp", *reqs[x], device=device, **single)
-    if groups:
-        ctx = context(device)
-        for xs in groups.values():
-            tours, durs = batch_sp_launch(ctx, [cis[x] for x in xs], objective)
-            for x, tour, d in zip(xs, tours, durs):
-                out[x] = sp_result(cis[x], tour, d, with_unvisited)
     return out
 
 
@@ -927,19 +768,10 @@ def batch_tdsp_launch(ctx: Context, cis, bounds, objective: str = "sum"):
     batch_tdsp_fits with its bound), W the largest of their row widths ->
     (tours, durations): per instance the n + K tour tokens and the K route
     durations."""
-    import torch
-    N, K, H = cis[0].N, len(cis[0].capacities), cis[0].durations.shape[0]
-    mats = np.empty((len(cis), H, N, N), dtype=np.int32)
-    dem = np.empty((len(cis), N), dtype=np.int32)
-    caps = np.empty((len(cis), K), dtype=np.int32)
-    starts = np.empty((len(cis), K), dtype=np.int64)
-    for x, ci in enumerate(cis):
-        mats[x], dem[x], caps[x], starts[x] = ci.durations, ci.demand, ci.capacities, ci.start_times
+    starts = np.array([ci.start_times for ci in cis], dtype=np.int64)
     G = max(len(set(row)) for row in starts.tolist())
     W = max(batch_tdsp_words(ci, b) for ci, b in zip(cis, bounds))
-    tours, keys, durs = ctx.vrp_batch_tdsp(torch.from_numpy(mats).to(ctx.dev),
-                                           torch.from_numpy(dem).to(ctx.dev),
-                                           torch.from_numpy(caps).to(ctx.dev), starts,
+    tours, keys, durs = ctx.vrp_batch_tdsp(*_stage(ctx, cis, hours=True), starts,
                                            np.array([int(b) for b in bounds], dtype=np.int64),
                                            OBJ_MAX if objective == "max" else OBJ_SUM, G=G, W=W)
     if (keys == -1).any().item():
@@ -947,11 +779,173 @@ def batch_tdsp_launch(ctx: Context, cis, bounds, objective: str = "sum"):
     return tours.cpu().tolist(), durs.cpu().tolist()
 
 
-def _guard_message(ci: CompactInstance) -> str:
-    mx = int(ci.durations.max()) if ci.durations.size else 0
-    if int(ci.start_times.max()) + (ci.N + len(ci.capacities) + 1) * mx >= 2**31:
-        return "start + (N+K+1)*max_duration overflows int32 (A9 guard)"
-    return "capacity + demand overflows int32"
+def _tsp_request(r):
+    """A TSP batch request -> (compact_tsp's four arguments, upper bound or None)."""
+    if isinstance(r, dict):
+        r = (r["durations"], r["customers"], r["start_node"], r.get("start_time", 0),
+             r.get("upper_bound"))
+    r = tuple(r)
+    r += (0,) * (4 - len(r))
+    return r[:4], r[4] if len(r) > 4 else None
+
+
+def _sp_request(r):
+    """A VRP batch request -> (compact_vrp's six arguments, None)."""
+    if isinstance(r, dict):
+        r = (r["durations"], r["locations"], r["capacities"], r["start_times"],
+             r.get("ignored_customers", ()), r.get("completed_customers", ()))
+    r = tuple(r) + ((),) * (6 - len(r))
+    return r[:6], None
+
+
+def _tdsp_request(r):
+    """A VRP batch request -> (compact_vrp's six arguments, upper bound or
+    None); a malformed one is refused here, in words of its own."""
+    if isinstance(r, dict):
+        r = tuple(r.get(k) for k in ("durations", "locations", "capacities", "start_times")) + \
+            (r.get("ignored_customers", ()), r.get("completed_customers", ()),
+             r.get("upper_bound"))
+    seq = (tuple, list, np.ndarray)
+    if not isinstance(r, (tuple, list)) or not 4 <= len(r) <= 7 or \
+            not all(isinstance(v, seq) for v in r[1:4]):
+        raise ValueError("a VRP request is (durations, locations, capacities, "
+                         "start_times[, ignored_customers, completed_customers[, "
+                         "upper_bound]]) or a dict with those keys")
+    r = tuple(r)
+    return r[:6] + ((),) * (6 - len(r[:6])), r[6] if len(r) > 6 else None
+
+
+@dataclass(frozen=True)
+class BatchKind:
+    """What one batched exact algorithm does differently from the others."""
+    problem: int       # TSP or CVRP: compact_tsp / solve_tsp / tsp_result, or the VRP's
+    request: object    # request -> (the compact_* arguments, upper bound or None)
+    check: object      # (ci, objective code, upper bound) -> the bound of the run, or None
+    fits: object       # (ci, bound) -> rides a launch (else: the single-request path)
+    key: object        # ci -> what the instances of one launch share
+    launch: object     # (ctx, cis, bounds, objective) -> (tours, durations)
+
+
+BATCH_KINDS = {
+    "dp": BatchKind(TSP, lambda r: (_tsp_request(r)[0], None),
+                    lambda ci, obj, ub: _check_dp(ci),
+                    lambda ci, bound: 2 <= ci.n <= BATCH_DP_MAX_CUSTOMERS,
+                    lambda ci: ci.N,
+                    lambda ctx, cis, bounds, objective: batch_dp_launch(ctx, cis)),
+    "sp": BatchKind(CVRP, _sp_request,
+                    lambda ci, obj, ub: _check_sp(ci),
+                    lambda ci, bound: batch_sp_fits(ci),
+                    lambda ci: (ci.N, len(ci.capacities)),
+                    lambda ctx, cis, bounds, objective: batch_sp_launch(ctx, cis, objective)),
+    "tdp": BatchKind(TSP, _tsp_request,
+                     lambda ci, obj, ub: batch_tdp_bound(ci, ub),
+                     batch_tdp_fits,
+                     lambda ci: (ci.N, ci.durations.shape[0]),
+                     lambda ctx, cis, bounds, objective: batch_tdp_launch(ctx, cis, bounds)),
+    "tdsp": BatchKind(CVRP, _tdsp_request, _check_tdsp, batch_tdsp_fits,
+                      lambda ci: (ci.N, len(ci.capacities), ci.durations.shape[0],
+                                  len(set(int(s) for s in ci.start_times))),
+                      batch_tdsp_launch),
+}
+
+
+def _solve_batch(algorithm: str, requests, device: int, objective: str = "sum",
+                 with_unvisited: bool = False) -> list:
+    """The batch entry points' one loop: every request normalised, compacted,
+    checked and guarded on the host (a bad one raises with its index); with no
+    local GPU each goes to the GPU box; else those that fit the LDS share one
+    launch per group key and the rest take the single-request path."""
+    kind = BATCH_KINDS[algorithm]
+    tsp = kind.problem == TSP
+    compact, single = (compact_tsp, solve_tsp) if tsp else (compact_vrp, solve_vrp)
+    shared = {} if tsp else dict(objective=objective, with_unvisited=with_unvisited)
+    reqs, cis, bounds, knobs = [], [], [], []
+    for x, r in enumerate(requests):
+        try:
+            r, ub = kind.request(r)
+            ci = compact(*r)
+            bound = kind.check(ci, OBJ_MAX if objective == "max" else OBJ_SUM, ub)
+            msg = batch_guard_message(ci)
+            if msg is not None:
+                raise ValueError(msg)
+        except ValueError as e:
+            raise ValueError(f"request {x}: {e}") from None
+        reqs.append(r)
+        cis.append(ci)
+        bounds.append(bound)
+        knobs.append(shared if ub is None else dict(shared, upper_bound=ub))
+    if _remote() is not None:      # no local GPU: the GPU box answers each request
+        return [single(algorithm, *r, **k) for r, k in zip(reqs, knobs)]
+    out = [None] * len(cis)
+    groups: dict = {}
+    for x, ci in enumerate(cis):
+        if kind.fits(ci, bounds[x]):
+            groups.setdefault(kind.key(ci), []).append(x)
+        else:
+            out[x] = single(algorithm, *reqs[x], device=device, **knobs[x])
+    if groups:
+        ctx = context(device)
+        for xs in groups.values():
+            tours, durs = kind.launch(ctx, [cis[x] for x in xs], [bounds[x] for x in xs],
+                                      objective)
+            for x, tour, dur in zip(xs, tours, durs):
+                if dur is None:
+                    raise ValueError(f"request {x}: no tour within upper_bound = "
+                                     f"{int(bounds[x])} minutes")
+                out[x] = tsp_result(cis[x], tour, dur) if tsp else \
+                    sp_result(cis[x], tour, dur, with_unvisited)
+    return out
+
+
+def solve_tsp_batch(algorithm: str, requests, *, device: int = 0) -> list:
+    """[solve_tsp(algorithm, *r) for r in requests], element for element, with
+    the small requests sharing launches.  `requests`: (durations, customers,
+    start_node, start_time) tuples, or dicts with those keys.  "dp" (spec A18)
+    and "tdp" (spec A20) have batched kernels.  Every request is compacted and
+    checked on the host before anything is launched; a bad one raises
+    solve_tsp's message for that algorithm prefixed with its index.
+
+    "dp" (bad: hour-indexed, more than DP_MAX_CUSTOMERS customers, A9 guard):
+    requests of 2..BATCH_DP_MAX_CUSTOMERS customers are grouped by node count,
+    one upload and one tsp_batch_dp launch per group; none or one customer
+    take solve_tsp's trivial path, and 13..24 customers its single-request
+    Held-Karp, one by one.
+
+    "tdp" (static or hour-indexed; bad: more than TDP_MAX_CUSTOMERS customers,
+    a negative bound, a table or a row above the caps, A9 guard): a request may
+    carry a fifth tuple element or an "upper_bound" key, the knob of
+    solve_tsp("tdp") (default: the nearest-neighbour tour's duration).
+    Requests inside A20's LDS domain (batch_tdp_fits: 1..11 customers, the row
+    width the bound implies) are grouped by (node count, hour count), one
+    upload and one tsp_batch_tdp launch per group at the group's largest row
+    width; no customer, 12..20 customers and an (n, W) outside the LDS take
+    solve_tsp("tdp"), one by one."""
+    if algorithm not in ("dp", "tdp"):
+        raise ValueError(f'solve_tsp_batch: no batched kernel for algorithm {algorithm!r}; only '
+                         '"dp" (exact Held-Karp) and "tdp" (exact time-expanded DP) are batched')
+    return _solve_batch(algorithm, requests, device)
+
+
+def solve_vrp_batch(algorithm: str, requests, *, objective: str = "sum",
+                    with_unvisited: bool = False, device: int = 0) -> list:
+    """[solve_vrp(algorithm, *r, objective=objective, with_unvisited=...) for r
+    in requests], element for element, with the small requests sharing
+    launches.  `requests`: (durations, locations, capacities, start_times[,
+    ignored_customers, completed_customers]) tuples, or dicts with those keys.
+    Only "sp" has a batched kernel (spec A19).  Every request is compacted and
+    checked on the host before anything is launched; a bad one (hour-indexed,
+    more than SP_MAX_CUSTOMERS customers or SP_MAX_VEHICLES vehicles, the int32
+    guards) raises solve_vrp("sp")'s message prefixed with its index.  Requests
+    of 1..BATCH_SP_MAX_CUSTOMERS customers whose (n, K) fits the LDS
+    (batch_sp_fits) are grouped by (N, K), one upload and one vrp_batch_sp
+    launch per group, and their result dicts are built on the host from the
+    tour tokens and the route durations; no customer, 13..20 customers and
+    fleets beyond the LDS take solve_vrp("sp"), one by one.  "tdsp" has a
+    batched kernel of its own behind solve_vrp_tdsp_batch (spec A21)."""
+    if algorithm != "sp":
+        raise ValueError(f'solve_vrp_batch: no batched kernel for algorithm {algorithm!r}; only '
+                         '"sp" (exact set partitioning) is batched')
+    return _solve_batch("sp", requests, device, objective, with_unvisited)
 
 
 def solve_vrp_tdsp_batch(requests, *, objective: str = "sum", with_unvisited: bool = False,
@@ -971,53 +965,7 @@ def solve_vrp_tdsp_batch(requests, *, objective: str = "sum", with_unvisited: bo
     largest row width, and their result dicts are built on the host from the
     tour tokens and the route durations; no customer, 12..19 customers and an
     (n, K, G, W) outside the LDS take solve_vrp("tdsp"), one by one."""
-    obj = OBJ_MAX if objective == "max" else OBJ_SUM
-    reqs, cis, bounds, knobs = [], [], [], []
-    for x, r in enumerate(requests):
-        if isinstance(r, dict):
-            r = tuple(r.get(k) for k in _VRP_REQUEST_KEYS[:4]) + \
-                (r.get("ignored_customers", ()), r.get("completed_customers", ()),
-                 r.get("upper_bound"))
-        seq = (tuple, list, np.ndarray)
-        if not isinstance(r, (tuple, list)) or not 4 <= len(r) <= 7 or \
-                not all(isinstance(v, seq) for v in r[1:4]):
-            raise ValueError(f"request {x}: a VRP request is (durations, locations, capacities, "
-                             "start_times[, ignored_customers, completed_customers[, "
-                             "upper_bound]]) or a dict with those keys")
-        r = tuple(r)
-        ub = r[6] if len(r) > 6 else None
-        r = r[:6] + ((),) * (6 - len(r[:6]))
-        try:
-            ci = compact_vrp(*r)
-            bound = _check_tdsp(ci, obj, ub)
-            if not batch_sp_guard(ci):
-                raise ValueError(_guard_message(ci))
-        except ValueError as e:
-            raise ValueError(f"request {x}: {e}") from None
-        reqs.append(r)
-        cis.append(ci)
-        bounds.append(bound)
-        knobs.append({} if ub is None else {"upper_bound": ub})
-    single = dict(objective=objective, with_unvisited=with_unvisited)
-    if _remote() is not None:      # no local GPU: the GPU box answers each request
-        return [solve_vrp("tdsp", *r, **single, **k) for r, k in zip(reqs, knobs)]
-    out = [None] * len(cis)
-    groups: dict = {}
-    for x, ci in enumerate(cis):
-        if batch_tdsp_fits(ci, bounds[x]):
-            key = (ci.N, len(ci.capacities), ci.durations.shape[0],
-                   len(set(int(s) for s in ci.start_times)))
-            groups.setdefault(key, []).append(x)
-        else:
-            out[x] = solve_vrp("tdsp", *reqs[x], device=device, **single, **knobs[x])
-    if groups:
-        ctx = context(device)
-        for xs in groups.values():
-            tours, durs = batch_tdsp_launch(ctx, [cis[x] for x in xs], [bounds[x] for x in xs],
-                                            objective)
-            for x, tour, d in zip(xs, tours, durs):
-                out[x] = sp_result(cis[x], tour, d, with_unvisited)
-    return out
+    return _solve_batch("tdsp", requests, device, objective, with_unvisited)
 
 
 # ---------------------------------------------------------------------------
