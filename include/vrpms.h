@@ -537,6 +537,46 @@ int vrpms_vrp_batch_tdsp(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d
                          int32_t objective, int32_t team, int16_t* d_tours, uint64_t* d_keys,
                          int32_t* d_durs, void* stream);
 
+/* Throughput mode of the VRP annealer: R independent CVRP
+ * requests of one node count N >= 2 (n = N - 1 customers, node 0 the depot),
+ * one fleet size K, 1 <= K <= 64, one hour count H (1 or 24), one objective,
+ * one step count and one seed, each with its own int32 [H][N][N] matrix
+ * (d_mats [R][H][N][N]), demands (d_demand [R][N], entry 0 ignored),
+ * capacities (d_cap [R][K], in vehicle order; they may differ or be 0), start
+ * times (d_start [R][K], minutes) and starting inverse temperature (d_inv_t0
+ * [R]).  ONE WORKGROUP PER REQUEST: the request's whole instance is staged
+ * into LDS once -- the matrix as uint16 with wide = 0, as int32 with wide = 1
+ * -- and its four wavefronts run four SA chains of `steps` steps over tours of
+ * ntok = n + K - 1 tokens (customers and K - 1 separators, A10): Philox
+ * Fisher-Yates starts packed first fit (vrpms_pack_separators' rule), A13's
+ * one-word moves, 64 candidates a step priced by full re-evaluation (A5-A8,
+ * A3), the temperature multiplied by inv_alpha after every step; no step when
+ * ntok < 2.  The Philox counters name the chain (0..3), not the request's row,
+ * so a request's answer depends on the request, steps, its inv_t0, inv_alpha,
+ * seed and objective alone: not on the launch it rode in nor on its row in it
+ * (vrpms_tsp_batch_sa's counters do carry the row).  vrpms_vrp_batch_sa_lds
+ * gives the launch's dynamic-LDS bytes for (N, K, H, wide) (host only, no
+ * context); a launch that needs more than the device has is refused with that
+ * byte count in the message.  (N + K + 1) * max(D) + max(start) < 2^31 and cap
+ * + demand < 2^31 (A9) are the caller's promise.  Out, per request, the best
+ * (key, chain) of the four: d_tours [R][ntok], d_keys [R] (its A8 key), d_durs
+ * [R][K] (the K route durations of that tour, unclamped, 0 for an empty route)
+ * and d_veh [R][ntok] (the vehicle of every token, -1 for an unvisited
+ * customer, -2 for a separator).  A request whose matrix has a negative entry,
+ * or with wide = 0 one above 65535, gets UINT64_MAX, an all-zero tour, zero
+ * durations and vehicles of -1, runs no step and touches nothing else.  No
+ * instance and no workspace needed; asynchronous on `stream`.  R = 0 launches
+ * nothing.  VRPMS_EINVAL, with nothing launched and nothing written, for a
+ * NULL ctx, R < 0, N outside 2..65535, K outside 1..64, H other than 1 or 24,
+ * an unknown wide or objective, steps < 0, a NULL buffer with R > 0, or an LDS
+ * need above the device's. */
+int vrpms_vrp_batch_sa_lds(int32_t N, int32_t K, int32_t H, int32_t wide, uint64_t* bytes);
+int vrpms_vrp_batch_sa(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_demand,
+                       const int32_t* d_cap, const int32_t* d_start, const float* d_inv_t0,
+                       int32_t R, int32_t N, int32_t K, int32_t H, int32_t objective, int32_t wide,
+                       int32_t steps, float inv_alpha, uint64_t seed, uint16_t* d_tours,
+                       uint64_t* d_keys, int32_t* d_durs, int8_t* d_veh, void* stream);
+
 /* ------------------------------------------------------------------------
  * Populations and the island model.  A pool is a set of
  * tours with their A8 keys: SA chains, a GA population ([islands][pop],

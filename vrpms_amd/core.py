@@ -72,6 +72,17 @@ def vrp_batch_tdsp_lds(n: int, K: int, G: int, H: int, W: int, team: int = 0) ->
     return int(nbytes.value)
 
 
+def vrp_batch_sa_lds(N: int, K: int, H: int, wide) -> int:
+    """vrpms_vrp_batch_sa_lds: the dynamic-LDS bytes of a vrp_batch_sa launch
+    for N nodes, K vehicles, H hour slices (1 or 24) and a uint16 (`wide`
+    false) or int32 (`wide` true) matrix.  Host only: needs the library, no
+    GPU."""
+    nbytes = ctypes.c_uint64()
+    check(_lib.load().vrpms_vrp_batch_sa_lds(int(N), int(K), int(H), int(wide),
+                                             ctypes.byref(nbytes)))
+    return int(nbytes.value)
+
+
 def tdp_words(start: int, horizon: int) -> int:
     """Hour words of one A16 row: the words from the start's hour to the one
     of start + horizon."""
@@ -620,6 +631,51 @@ class Context:
                                             tours.data_ptr(), keys.data_ptr(), durs.data_ptr(),
                                             self.stream()))
         return tours, keys, durs
+
+    def vrp_batch_sa(self, mats, demand, caps, starts, inv_t0, objective: int, steps: int,
+                     inv_alpha: float, seed: int, wide=None):
+        """Four annealing chains per request, one workgroup per request, one
+        launch for all (spec A22; all requests of one N, K, H and objective):
+        mats int32 [R][H][N][N] (H = 1 or 24; [R][N][N] is taken as H = 1),
+        demand int32 [R][N] (entry 0 ignored), caps and starts int32 [R][K]
+        and inv_t0 float32 [R] on the device -> (tours int16 [R][ntok], keys
+        int64 [R], durs int32 [R][K], veh int8 [R][ntok]) with ntok = N - 1 +
+        K - 1: per request the best tour of its four chains, its A8 key, its K
+        route durations (unclamped, 0 for an empty route) and the vehicle of
+        every token (-1 unvisited, -2 separator).  A request's row depends on
+        the request, `steps`, its inv_t0, `inv_alpha`, `seed` and `objective`
+        alone, not on the batch.  `wide`: False stages the matrices as uint16
+        (a request with an entry above 65535 then gets an all-ones key, a zero
+        tour, zero durations and veh = -1), True as int32; whoever builds
+        `mats` from host data knows which, so None -- the default -- asks the
+        device for the batch's largest entry, which synchronises.  The A9
+        guard and non-negative demands and capacities are the caller's
+        promise.  Asynchronous on the current stream."""
+        torch = _torch()
+        mats = self._batch_mats(torch, mats, 4)
+        R, H, N, _ = mats.shape
+        self._batch_rows(torch, demand, caps, R, N)
+        K = caps.shape[1]
+        if starts.device != self.dev or starts.shape != caps.shape or starts.dtype != torch.int32 \
+                or not starts.is_contiguous():
+            raise ValueError(f"starts must be a contiguous int32 [R][K] tensor on {self.dev}")
+        if inv_t0.device != self.dev or inv_t0.shape != (R,) or inv_t0.dtype != torch.float32 or \
+                not inv_t0.is_contiguous():
+            raise ValueError(f"inv_t0 must be a contiguous float32 [R] tensor on {self.dev}")
+        if wide is None:
+            wide = bool(R) and int(mats.max().item()) > 65535
+        ntok = N - 1 + K - 1
+        tours = torch.empty((R, max(ntok, 1)), dtype=torch.int16, device=self.dev)
+        keys = torch.empty(R, dtype=torch.int64, device=self.dev)
+        durs = torch.empty((R, max(K, 1)), dtype=torch.int32, device=self.dev)
+        veh = torch.empty((R, max(ntok, 1)), dtype=torch.int8, device=self.dev)
+        check(self.lib.vrpms_vrp_batch_sa(self._ctx, mats.data_ptr(), demand.data_ptr(),
+                                          caps.data_ptr(), starts.data_ptr(), inv_t0.data_ptr(), R,
+                                          N, K, H, int(objective), int(bool(wide)), int(steps),
+                                          float(inv_alpha), int(seed) & (2**64 - 1),
+                                          tours.data_ptr(), keys.data_ptr(), durs.data_ptr(),
+                                          veh.data_ptr(), self.stream()))
+        return tours, keys, durs, veh
 
     def set_batch_dp_team(self, T: int):
         """Threads per request of tsp_batch_dp: 0 = auto (the n -> T table),

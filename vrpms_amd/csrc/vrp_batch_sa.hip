@@ -1,0 +1,366 @@
+// Throughput mode of the VRP annealer: R independent
+// small-fleet CVRP requests of one (N, K, H, objective) share one launch, ONE
+// WORKGROUP PER REQUEST.  The workgroup stages its request's whole instance --
+// the [H][N][N] matrix (uint16, or int32 when `wide`), the demand row, the
+// capacity row and the start-time row -- into LDS once and checks it on the way
+// (a negative entry, or one above 65535 under wide = 0, ends the request with
+// an all-ones key; its neighbours in the launch never see it).  Its four
+// wavefronts are four SA chains w = 0..3:
+//
+//   start   Philox Fisher-Yates of 1..n, counters (0xffffffff, 0xffffffff, w, i),
+//           then spec.pack_separators: first fit into K routes, one lane per
+//           route (the fitting routes by one ballot), K - 1 separators;
+//   step s  lane l decodes word s & 3 of the block (s >> 2, 0, w, l) with A13's
+//           decode_move1 over the ntok = n + K - 1 tokens and prices the moved
+//           tour by eval_tour<true> over moved_index (the greedy split and the
+//           departure times make a delta non-local); the (key, lane) minimum of
+//           the wave is the proposal; the acceptance draw is word s & 3 of the
+//           block (s >> 2, 1, w, 0) -- wave-uniform counters, so it sits on the
+//           scalar unit;
+//   answer  the best (key, w); that wavefront walks its best tour once more
+//           and writes the K route durations and every token's vehicle.
+//
+// The counters carry w, not 4 r + w as tsp_batch_sa's do: a request's answer
+// does not depend on the launch it rode in or on its row in it.
+//
+// LDS, every part as the kernel carves it (vrpms_vrp_batch_sa_lds):
+//   align16(H N N (wide ? 4 : 2))            the matrix
+// + 4 align4(N) + 2 * 4 align4(K)            demand, capacities, start times (int32)
+// + 4 * 3 * 2 align8(ntok)                   4 chains x (current, scratch, best) uint16 tours
+// + 4 * 8                                    the chains' best keys
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "common.hpp"
+#include "ctx.hpp"
+#include "staging.hpp"
+#include "tour.hpp"
+
+namespace vrpms {
+
+constexpr int kBatchSaMaxK = 64;      // one lane per route in the first-fit start
+constexpr int kBatchSaMaxN = 65535;   // tokens are uint16
+
+struct VrpBatchSaArgs {
+  const int32_t* mats;    // [R][H][N][N]
+  const int32_t* demand;  // [R][N]
+  const int32_t* cap;     // [R][K]
+  const int32_t* start;   // [R][K]
+  const float* inv_t0;    // [R]
+  int R, N, K, H, objective, steps;
+  float inv_alpha;
+  uint32_t seed_lo, seed_hi;
+  uint16_t* tours;        // [R][ntok]
+  uint64_t* keys;         // [R]
+  int32_t* durs;          // [R][K]
+  int8_t* veh;            // [R][ntok]
+};
+
+struct BatchSaLds {
+  size_t mat, dem, row, tour, total;   // bytes of the matrix, the demand row, one K row, one tour
+};
+
+inline BatchSaLds batch_sa_lds(int N, int K, int H, int wide) {
+  BatchSaLds l;
+  l.mat = ((size_t)H * N * N * (wide ? 4 : 2) + 15) & ~(size_t)15;
+  l.dem = (((size_t)N + 3) & ~(size_t)3) * 4;
+  l.row = (((size_t)K + 3) & ~(size_t)3) * 4;
+  l.tour = (((size_t)N - 1 + K - 1 + 7) & ~(size_t)7) * 2;
+  l.total = l.mat + l.dem + 2 * l.row + 4 * 3 * l.tour + 4 * 8;
+  return l;
+}
+
+template <typename MatT, int HM>
+__global__ __launch_bounds__(256) void vrp_batch_sa_kernel(VrpBatchSaArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char batch_sa_lds_mem[];
+  const int N = a.N, n = N - 1, K = a.K, ntok = n + K - 1;
+  const int64_t r = blockIdx.x;
+  const uint32_t cells = (uint32_t)HM * (uint32_t)N * (uint32_t)N;
+  const uint32_t mat_bytes = (cells * (uint32_t)sizeof(MatT) + 15u) & ~15u;
+  const uint32_t dem_words = ((uint32_t)N + 3u) & ~3u, row_words = ((uint32_t)K + 3u) & ~3u;
+  const uint32_t tpad = ((uint32_t)ntok + 7u) & ~7u;
+  MatT* M = reinterpret_cast<MatT*>(batch_sa_lds_mem);
+  int32_t* dem = reinterpret_cast<int32_t*>(batch_sa_lds_mem + mat_bytes);
+  int32_t* cap = dem + dem_words;
+  int32_t* start = cap + row_words;
+  uint16_t* tours = reinterpret_cast<uint16_t*>(start + row_words);
+  uint64_t* wbest = reinterpret_cast<uint64_t*>(tours + 4 * 3 * tpad);
+
+  // stage and check the request
+  const int32_t* src = a.mats + r * (int64_t)cells;
+  // the verdict goes through a word of the dynamic LDS (wbest, free until the
+  // chains end): __syncthreads_or would add static LDS on top of the bytes
+  // vrpms_vrp_batch_sa_lds promises
+  uint32_t* flag = reinterpret_cast<uint32_t*>(wbest);
+  if (threadIdx.x == 0) *flag = 0;
+  __syncthreads();
+  bool bad = false;
+  for (uint32_t i = threadIdx.x; i < cells; i += 256) {
+    const int32_t v = src[i];
+    bad |= v < 0 || (sizeof(MatT) == 2 && v > 65535);
+    M[i] = (MatT)v;
+  }
+  for (int i = threadIdx.x; i < N; i += 256) dem[i] = a.demand[r * N + i];
+  for (int k = threadIdx.x; k < K; k += 256) {
+    cap[k] = a.cap[r * K + k];
+    start[k] = a.start[r * K + k];
+  }
+  uint16_t* gtour = a.tours + r * ntok;
+  int8_t* gveh = a.veh + r * ntok;
+  int32_t* gdurs = a.durs + r * K;
+  if (bad) *flag = 1;
+  __syncthreads();
+  bad = *flag != 0;
+  __syncthreads();   // every wavefront has read the word before any chain's key replaces it
+  if (bad) {  // outside the launch's promise: no step
+    for (int q = threadIdx.x; q < ntok; q += 256) {
+      gtour[q] = 0;
+      gveh[q] = -1;
+    }
+    for (int k = threadIdx.x; k < K; k += 256) gdurs[k] = 0;
+    if (threadIdx.x == 0) a.keys[r] = ~0ull;
+    return;
+  }
+
+  const int wave = (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = lane_id();
+  uint16_t* A = tours + wave * 3 * tpad;   // current tour
+  uint16_t* B = A + tpad;                  // scratch for the accepted move
+  uint16_t* Best = A + 2 * tpad;
+  const MatView<MatT, HM> D{M, (uint32_t)N, (uint32_t)N * (uint32_t)N, HM};
+  const SplitParams sp{dem, cap, start, K, a.objective};
+
+  // Philox Fisher-Yates start as in tsp_batch_body: lane l draws the block of
+  // i = 64 c + l for a chunk of 64 swaps at once, lane 0 swaps
+  for (int q = lane; q < n; q += 64) A[q] = (uint16_t)(q + 1);
+  wave_sync();
+  uint32_t jv = 0;
+  for (int i = n - 1; i >= 1; --i) {
+    if (i == n - 1 || (i & 63) == 63) {
+      const uint32_t il = (uint32_t)(i & ~63) + (uint32_t)lane;
+      const u32x4 x = philox(0xffffffffu, 0xffffffffu, (uint32_t)wave, il, a.seed_lo, a.seed_hi);
+      jv = x.x % (il + 1u);
+    }
+    const int j = __builtin_amdgcn_readlane((int)jv, i & 63);
+    if (lane == 0) {
+      const uint16_t t = A[i];
+      A[i] = A[j];
+      A[j] = t;
+    }
+  }
+  wave_sync();
+  // spec.pack_separators(perm, K - 1): lane b holds route b's load and room;
+  // customer q goes to the first route that has room for it, to the last one
+  // when none has (B[q] = its route), then the routes are laid out in order
+  // with a separator between them
+  {
+    const int64_t room = lane < K ? (int64_t)cap[lane] : -1;
+    int64_t load = 0;
+    int cnt = 0;
+    for (int q = 0; q < n; ++q) {
+      const int64_t d = dem[A[q]];
+      const uint64_t fits = __builtin_amdgcn_ballot_w64(lane < K && load + d <= room);
+      const int b = fits ? (int)__builtin_ctzll(fits) : K - 1;
+      if (lane == b) {
+        load += d;
+        ++cnt;
+      }
+      if (lane == 0) B[q] = (uint16_t)b;
+    }
+    int off = 0, run = 0;   // route b starts at (customers of the routes before it) + b
+    for (int b = 0; b < K; ++b) {
+      if (lane == b) off = run + b;
+      run += __builtin_amdgcn_readlane(cnt, b);
+    }
+    for (int q = lane; q < ntok; q += 64) Best[q] = 0;
+    wave_sync();
+    for (int q = 0; q < n; ++q) {
+      const int b = __builtin_amdgcn_readfirstlane((int)B[q]);
+      const int pos = __builtin_amdgcn_readlane(off, b);
+      if (lane == b) ++off;
+      if (lane == 0) Best[pos] = A[q];
+    }
+    wave_sync();
+    uint16_t* t = A;   // the packed tour becomes the current one
+    A = Best;
+    Best = t;
+  }
+
+  uint64_t ck = eval_tour<true>(D, sp, [&](int i) { return (uint32_t)A[i]; }, ntok).key;
+  uint64_t bk = ck;
+  for (int q = lane; q < ntok; q += 64) Best[q] = A[q];
+  wave_sync();
+  float invT = a.inv_t0[r];
+  // one SA step: xm = the lane's move word, xa = the chain's acceptance draw
+  auto step = [&](uint32_t xm, uint32_t xa) __attribute__((always_inline)) {
+    const Move m = decode_move1(xm, ntok);
+    int bl;
+    const uint64_t k = wave_argmin_lane(
+        eval_tour<true>(D, sp, [&](int q) { return (uint32_t)A[moved_index(q, m)]; }, ntok).key, bl);
+    bool accept = k <= ck;
+    if (!accept) {
+      const uint64_t d = (k >> 28) - (ck >> 28);
+      const uint32_t dp = d > 0xffffffffull ? 0xffffffffu : (uint32_t)d;
+      accept = accept_test(dp, invT, xa >> 8);   // (xa >> 8) < accept_threshold(dp, invT)
+    }
+    if (accept) {  // bl is wave-uniform: the winner's move by v_readlane
+      Move mb;
+      mb.typ = (uint32_t)wave_bcast((int)m.typ, bl);
+      mb.i = wave_bcast(m.i, bl);
+      mb.j = wave_bcast(m.j, bl);
+      for (int q = lane; q < ntok; q += 64) B[q] = A[moved_index(q, mb)];
+      wave_sync();
+      uint16_t* t = A;
+      A = B;
+      B = t;
+      ck = k;
+      if (ck < bk) {
+        bk = ck;
+        for (int q = lane; q < ntok; q += 64) Best[q] = A[q];
+      }
+      wave_sync();
+    }
+    invT = invT * a.inv_alpha;
+  };
+  // A13: one Philox block per lane serves four steps, one per chain their
+  // acceptance draws; unrolled by four, so each step reads its words without a
+  // select
+  if (ntok >= 2) {
+    int s = 0;
+    for (; s + 4 <= a.steps; s += 4) {
+      const u32x4 rb = philox((uint32_t)(s >> 2), 0u, (uint32_t)wave, (uint32_t)lane, a.seed_lo, a.seed_hi);
+      const u32x4 ra = philox((uint32_t)(s >> 2), 1u, (uint32_t)wave, 0u, a.seed_lo, a.seed_hi);
+      step(rb.x, ra.x);
+      step(rb.y, ra.y);
+      step(rb.z, ra.z);
+      step(rb.w, ra.w);
+    }
+    if (s < a.steps) {  // the last 1..3 steps
+      const u32x4 rb = philox((uint32_t)(s >> 2), 0u, (uint32_t)wave, (uint32_t)lane, a.seed_lo, a.seed_hi);
+      const u32x4 ra = philox((uint32_t)(s >> 2), 1u, (uint32_t)wave, 0u, a.seed_lo, a.seed_hi);
+      for (int h = 0; s + h < a.steps; ++h)
+        step(h == 0 ? rb.x : h == 1 ? rb.y : rb.z, h == 0 ? ra.x : h == 1 ? ra.y : ra.z);
+    }
+  }
+  if (lane == 0) wbest[wave] = bk;
+  __syncthreads();
+  int bw = 0;
+  for (int w = 1; w < 4; ++w)
+    if (wbest[w] < wbest[bw]) bw = w;
+  if (wave != bw) return;
+
+  // the winner's best tour once more, as spec.eval_cvrp walks it: every lane
+  // walks alike, lane k keeps route k's duration, lane 0 notes the vehicles
+  // (as int16 in the chain's scratch tour)
+  int16_t* V = reinterpret_cast<int16_t*>(B);
+  int mydur = 0;
+  {
+    int k = 0, load = 0, t = start[0], prev = 0;
+    auto close_route = [&]() {
+      if (prev) {
+        t += D(t, (uint32_t)prev, 0);
+        if (lane == k) mydur = t - start[k];
+      }
+      ++k;
+      if (k < K) {
+        load = 0;
+        t = start[k];
+        prev = 0;
+      }
+    };
+    for (int i = 0; i < ntok; ++i) {
+      const int c = (int)min((uint32_t)Best[i], (uint32_t)n);
+      int v;
+      if (c == 0) {
+        v = -2;
+        if (k < K) close_route();
+      } else {
+        const int dc = dem[c];
+        while (k < K && load + dc > cap[k]) close_route();
+        if (k < K) {
+          t += D(t, (uint32_t)prev, (uint32_t)c);
+          load += dc;
+          prev = c;
+          v = k;
+        } else {
+          v = -1;
+        }
+      }
+      if (lane == 0) V[i] = (int16_t)v;
+    }
+    if (k < K) close_route();
+  }
+  wave_sync();
+  for (int q = lane; q < ntok; q += 64) {
+    gtour[q] = Best[q];
+    gveh[q] = (int8_t)V[q];
+  }
+  if (lane < K) gdurs[lane] = mydur;
+  if (lane == 0) a.keys[r] = bk;
+}
+
+// the shape checks both entry points share; 0 or the refusal's code
+static int batch_sa_check(const char* who, int32_t N, int32_t K, int32_t H, int32_t wide) {
+  const std::string w(who);
+  if (N < 2 || N > kBatchSaMaxN)
+    return fail(VRPMS_EINVAL, w + ": needs 2 <= N <= 65535 (" + std::to_string(N) + " given)");
+  if (K < 1 || K > kBatchSaMaxK)
+    return fail(VRPMS_EINVAL, w + ": one lane per route needs 1 <= K <= 64 (" + std::to_string(K) + " given)");
+  if (H != 1 && H != 24)
+    return fail(VRPMS_EINVAL, w + ": H must be 1 or 24 (" + std::to_string(H) + " given)");
+  if (wide != 0 && wide != 1)
+    return fail(VRPMS_EINVAL, w + ": wide must be 0 (uint16 matrix) or 1 (int32) (" + std::to_string(wide) +
+                                  " given)");
+  return VRPMS_OK;
+}
+
+}  // namespace vrpms
+
+using namespace vrpms;
+
+extern "C" int vrpms_vrp_batch_sa_lds(int32_t N, int32_t K, int32_t H, int32_t wide, uint64_t* bytes) {
+  if (!bytes) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_sa_lds: bytes is NULL");
+  const int rc = batch_sa_check("vrpms_vrp_batch_sa_lds", N, K, H, wide);
+  if (rc) return rc;
+  *bytes = batch_sa_lds(N, K, H, wide).total;
+  return VRPMS_OK;
+}
+
+extern "C" int vrpms_vrp_batch_sa(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_demand,
+                                  const int32_t* d_cap, const int32_t* d_start, const float* d_inv_t0,
+                                  int32_t R, int32_t N, int32_t K, int32_t H, int32_t objective,
+                                  int32_t wide, int32_t steps, float inv_alpha, uint64_t seed,
+                                  uint16_t* d_tours, uint64_t* d_keys, int32_t* d_durs, int8_t* d_veh,
+                                  void* stream) {
+  if (!ctx) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_sa: ctx is NULL");
+  if (R < 0) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_sa: R must not be negative");
+  const int rc = batch_sa_check("vrpms_vrp_batch_sa", N, K, H, wide);
+  if (rc) return rc;
+  if (objective != VRPMS_OBJ_SUM && objective != VRPMS_OBJ_MAX)
+    return fail(VRPMS_EINVAL, "vrpms_vrp_batch_sa: objective must be VRPMS_OBJ_SUM or VRPMS_OBJ_MAX");
+  if (steps < 0) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_sa: steps must not be negative");
+  if (R == 0) return VRPMS_OK;
+  if (!d_mats || !d_demand || !d_cap || !d_start || !d_inv_t0 || !d_tours || !d_keys || !d_durs || !d_veh)
+    return fail(VRPMS_EINVAL,
+                "vrpms_vrp_batch_sa: NULL matrix/demand/capacity/start/inv_t0/tour/key/duration/vehicle buffer");
+  const size_t lds = batch_sa_lds(N, K, H, wide).total;
+  if (lds > ctx->max_lds)
+    return fail(VRPMS_EINVAL, "vrpms_vrp_batch_sa: a request of N = " + std::to_string(N) + ", K = " +
+                                  std::to_string(K) + ", H = " + std::to_string(H) +
+                                  (wide ? " (int32 matrix)" : " (uint16 matrix)") + " needs " +
+                                  std::to_string(lds) + " bytes of LDS (" + std::to_string(ctx->max_lds) +
+                                  " available)");
+  VRPMS_HIP(hipSetDevice(ctx->device));
+  const VrpBatchSaArgs a{d_mats, d_demand, d_cap,  d_start, d_inv_t0, R,      N,      K,
+                         H,      objective, steps, inv_alpha, (uint32_t)seed, (uint32_t)(seed >> 32),
+                         d_tours, d_keys, d_durs, d_veh};
+  void (*kernel)(VrpBatchSaArgs) =
+      wide ? (H == 24 ? vrp_batch_sa_kernel<int32_t, 24> : vrp_batch_sa_kernel<int32_t, 1>)
+           : (H == 24 ? vrp_batch_sa_kernel<uint16_t, 24> : vrp_batch_sa_kernel<uint16_t, 1>);
+  if (lds > 65536)
+    VRPMS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  kernel<<<(unsigned)R, 256, lds, (hipStream_t)stream>>>(a);
+  VRPMS_HIP(hipGetLastError());
+  return VRPMS_OK;
+}

@@ -453,6 +453,49 @@ class ExactTdspBatcher(ExactBatcher):
         return self._solved(ci, bound=int(bound), objective=_objective(objective))
 
 
+class VrpSaBatcher(TspBatcher):
+    """Coalesces concurrent /api/vrp/sa and /solve/vrp/sa requests into one
+    `vrp_batch_sa` launch per (node count, fleet size, hour count, cell width,
+    objective) (spec A22: one workgroup per request, its whole instance in
+    LDS, four chains of `steps` steps).  The queue, the window, the device
+    round-robin and the error fan-out are TspBatcher's.  Unlike TspBatcher's,
+    a batched answer does not depend on the batch: every request runs on its
+    own temperature schedule and chain counters, so it is
+    solver.solve_vrp_sa_batch([request], steps, the app's seed)'s.  It is not
+    the unbatched endpoint's answer (four chains here, 1,024 there).  A launch
+    returns (tours, [(veh, durs), ...]): the second list rides TspBatcher's
+    per-job duration field."""
+
+    @classmethod
+    def accepts(cls, ci) -> bool:
+        """Requests inside A22's LDS domain that pass the int32 guards
+        vrpms_set_instance applies on the unbatched path; anything else takes
+        the unbatched path, so both paths share one error contract."""
+        from . import solver
+        return solver.batch_sa_fits(ci) and solver.batch_guard_message(ci) is None
+
+    @staticmethod
+    def group_key(job):
+        from . import solver
+        return solver.batch_sa_key(job["ci"]) + (job["objective"],)
+
+    def solve(self, ci, objective: str = "sum") -> dict:
+        """Blocks until the request's launch finished -> the VRP slot dict."""
+        from . import solver
+        job = {"ci": ci, "done": threading.Event(), "objective": _objective(objective)}
+        self._wait(job)
+        veh, durs = job["duration"]
+        return solver.sa_result(ci, list(job["tour"]), veh, durs)
+
+    def _gpu_launch(self, key, cis, device=None):
+        from . import solver
+        dev = self.devices[0] if device is None else device
+        with self.app.locks[dev]:
+            tours, veh, durs = solver.batch_sa_launch(solver.context(dev), cis, self.steps,
+                                                      self.app.seed, key[-1])
+        return tours, list(zip(veh, durs))
+
+
 # ---------------------------------------------------------------------------
 # the endpoint logic
 # ---------------------------------------------------------------------------
@@ -475,7 +518,8 @@ class App:
                  batch_steps: int = 2000, batch_launch=None, devices=None,
                  island_min_n: int = 150, batch_exact: bool = False, batch_exact_launch=None,
                  batch_exact_vrp_launch=None, batch_exact_tdp_launch=None,
-                 batch_exact_tdsp: bool = False, batch_exact_tdsp_launch=None):
+                 batch_exact_tdsp: bool = False, batch_exact_tdsp_launch=None,
+                 batch_vrp_sa: bool = False, batch_vrp_sa_launch=None):
         self.store = store
         self.devices = list(devices) if devices else [device]
         self.device = self.devices[0]
@@ -505,6 +549,11 @@ class App:
         self.exact_tdsp_batcher = ExactTdspBatcher(self, batch_window_s,
                                                    launch=batch_exact_tdsp_launch) \
             if batch_exact_tdsp else None
+        # small-fleet VRP SA requests share vrp_batch_sa launches (off by
+        # default: the batched answer is not the unbatched endpoint's)
+        self.vrp_sa_batcher = VrpSaBatcher(self, batch_window_s, batch_steps,
+                                           launch=batch_vrp_sa_launch) \
+            if batch_vrp_sa else None
 
     def _scheduled(self, problem, algorithm, params, knobs, locations, durations):
         """Run the solve on a device: all of them (in order, as an island
@@ -551,6 +600,18 @@ class App:
         ci = solver.compact_tsp(durations, params["customers"], params["start_node"],
                                 params["start_time"] or 0)
         return ci if batcher.accepts(ci) else None
+
+    def _batched_vrp_sa(self, problem, algorithm, params, knobs, locations, durations):
+        """The compact instance when this request rides the VRP SA batcher,
+        else None: the flag is on, the route is vrp / sa, the request names
+        no inline knob of its own and it is inside the batcher's domain."""
+        if self.vrp_sa_batcher is None or (problem, algorithm) != ("vrp", "sa") or \
+                knobs.get("inline"):
+            return None
+        from . import solver
+        ci = solver.compact_vrp(durations, locations, params["capacities"], params["start_times"],
+                                params["ignored_customers"], params["completed_customers"])
+        return ci if self.vrp_sa_batcher.accepts(ci) else None
 
     def _exact_batcher(self, problem, algorithm):
         """The exact batcher of an inline (problem, algorithm), or None."""
@@ -627,8 +688,11 @@ class App:
             batcher = {("tsp", "sa"): self.batcher,
                        ("tsp", "bf"): self.exact_batcher}.get((problem, algorithm))
             ci = self._batched_tsp(params, durations, batcher) if batcher is not None else None
+            vci = self._batched_vrp_sa(problem, algorithm, params, knobs, locations, durations)
             if ci is not None:
                 result = batcher.solve(ci)
+            elif vci is not None:
+                result = self.vrp_sa_batcher.solve(vci, knobs.get("objective", "sum"))
             else:
                 result = self._scheduled(problem, algorithm, params, knobs, locations, durations)
         except Exception as e:   # bad instance shape, GPU unavailable, ...
@@ -719,8 +783,12 @@ class App:
             batcher = self._exact_batcher(problem, algorithm)
             args = self._batched(batcher, params, knobs, locations, vals["durations"]) \
                 if batcher is not None else None
+            vci = self._batched_vrp_sa(problem, algorithm, params, knobs, locations,
+                                       vals["durations"])
             if args is not None:
                 result = batcher.solve(*args)
+            elif vci is not None:
+                result = self.vrp_sa_batcher.solve(vci, knobs.get("objective", "sum"))
             else:
                 result = self._scheduled(problem, algorithm, params, knobs, locations,
                                          vals["durations"])
@@ -843,6 +911,13 @@ def main(argv=None):
                          "(/solve/vrp/tdsp, static or hour-indexed matrix, 1..11 customers, a "
                          "fleet and an upper bound whose state fits the LDS) into vrp_batch_tdsp "
                          "launches; the answers equal the unbatched ones")
+    ap.add_argument("--batch-vrp-sa", action="store_true",
+                    help="coalesce concurrent small-fleet VRP SA requests (/api/vrp/sa and "
+                         "/solve/vrp/sa, static or hour-indexed matrix, 1..64 vehicles, an "
+                         "instance that fits the LDS) into vrp_batch_sa launches of --batch-steps "
+                         "steps: four chains per request, so the answer differs from the "
+                         "unbatched endpoint's; it depends on the request alone, not on the "
+                         "batch it rode in")
     ap.add_argument("--batch-window-ms", type=float, default=5.0)
     ap.add_argument("--batch-steps", type=int, default=2000)
     ap.add_argument("--workers", type=int, default=0,
@@ -881,7 +956,7 @@ def main(argv=None):
     app = App(store, device=args.device, seed=args.seed, max_seconds=args.max_seconds,
               batch_tsp=args.batch_tsp, batch_window_s=args.batch_window_ms * 1e-3,
               batch_steps=args.batch_steps, devices=devices, batch_exact=args.batch_exact,
-              batch_exact_tdsp=args.batch_exact_tdsp)
+              batch_exact_tdsp=args.batch_exact_tdsp, batch_vrp_sa=args.batch_vrp_sa)
     srv = serve(app, args.host, args.port)
     print(f"vrpms_amd service on http://{args.host}:{args.port}/api", flush=True)
     try:

@@ -109,6 +109,13 @@ TDSP_MAX_WORKSPACE = 16 << 30
 # Other requests of a batch take the single-request path
 BATCH_TDSP_MAX_CUSTOMERS = 11
 BATCH_TDSP_LDS_BYTES = 160 * 1024
+# batched VRP annealing (A22): one request's whole [H][N][N] matrix (uint16
+# cells unless an entry is above 65535), its demand, capacity and start-time
+# rows and 4 chains x 3 tours have to fit one CU's LDS (vrpms_vrp_batch_sa_lds
+# gives the bytes for (N, K, H, wide)); DESIGN.md §4.3m has the largest N per
+# (K, H, wide).  Other requests of a batch take the single-request path
+BATCH_SA_MAX_VEHICLES = 64
+BATCH_SA_LDS_BYTES = 160 * 1024
 # SA on tours of more than SA_WINDOW_MIN_N customers samples A11 windowed
 # moves (second position within SA_WINDOW of the first)
 SA_WINDOW, SA_WINDOW_MIN_N = 32, 150
@@ -966,6 +973,146 @@ def solve_vrp_tdsp_batch(requests, *, objective: str = "sum", with_unvisited: bo
     tour tokens and the route durations; no customer, 12..19 customers and an
     (n, K, G, W) outside the LDS take solve_vrp("tdsp"), one by one."""
     return _solve_batch("tdsp", requests, device, objective, with_unvisited)
+
+
+# ---------------------------------------------------------------------------
+# batched VRP annealing (A22): small-fleet requests share launches
+# ---------------------------------------------------------------------------
+def batch_sa_wide(ci: CompactInstance) -> bool:
+    """The request's matrix needs int32 cells in LDS (an entry above 65535)."""
+    return bool(ci.durations.size) and int(ci.durations.max()) > 65535
+
+
+def batch_sa_schedule(ci: CompactInstance, steps: int):
+    """(inv_t0, inv_alpha) of a request's four chains: TspBatcher's constants
+    -- a starting temperature of half the mean positive entry, cooled to 0.002
+    of the mean over `steps` steps -- but from the request's own matrix (all
+    hour slices; 1.0 when it has no positive entry), so the company a request
+    rides with does not change its answer."""
+    nz = ci.durations[ci.durations > 0]
+    edge = float(nz.mean()) if nz.size else None
+    return (1.0 / (0.5 * edge) if edge else 1.0), (0.5 / 0.002) ** (1.0 / max(1, int(steps)))
+
+
+def batch_sa_key(ci: CompactInstance):
+    """What the instances of one vrp_batch_sa launch share (next to the
+    objective, the steps and the seed): (N, K, H, wide)."""
+    return ci.N, len(ci.capacities), ci.durations.shape[0], batch_sa_wide(ci)
+
+
+def batch_sa_fits(ci: CompactInstance) -> bool:
+    """A22's LDS domain: a CVRP of at least one customer, 1..64 vehicles and a
+    static or 24-slice matrix whose whole instance and twelve tours fit
+    BATCH_SA_LDS_BYTES (vrpms_vrp_batch_sa_lds; uint16 cells unless an entry
+    is above 65535).  Needs the library, no GPU."""
+    from .core import vrp_batch_sa_lds
+    if ci.problem != CVRP or ci.n < 1 or ci.N > 65535:
+        return False
+    N, K, H, wide = batch_sa_key(ci)
+    if not 1 <= K <= BATCH_SA_MAX_VEHICLES or H not in (1, 24):
+        return False
+    return vrp_batch_sa_lds(N, K, H, wide) <= BATCH_SA_LDS_BYTES
+
+
+def batch_sa_launch(ctx: Context, cis, steps: int, seed: int, objective: str = "sum"):
+    """One upload and one vrp_batch_sa launch for compact instances of one
+    batch_sa_key (each passed batch_guard_message and batch_sa_fits), every
+    request on its own batch_sa_schedule -> (tours, veh, durs): per instance
+    the n + K - 1 tour tokens, each token's vehicle (-1 unvisited, -2 a
+    separator) and the K route durations."""
+    import torch
+    mats, demand, caps = _stage(ctx, cis, hours=True)
+    starts = torch.from_numpy(np.array([ci.start_times for ci in cis], dtype=np.int32)).to(ctx.dev)
+    sched = [batch_sa_schedule(ci, steps) for ci in cis]
+    inv_t0 = torch.from_numpy(np.array([s[0] for s in sched], dtype=np.float32)).to(ctx.dev)
+    tours, keys, durs, veh = ctx.vrp_batch_sa(mats, demand, caps, starts, inv_t0,
+                                              OBJ_MAX if objective == "max" else OBJ_SUM,
+                                              int(steps), sched[0][1], seed,
+                                              wide=batch_sa_wide(cis[0]))
+    if (keys == -1).any().item():
+        raise RuntimeError("vrp_batch_sa: a request was outside the launch's contract")
+    return tours.cpu().tolist(), veh.cpu().tolist(), durs.cpu().tolist()
+
+
+def sa_result(ci: CompactInstance, tour, veh, durs, with_unvisited: bool = False) -> dict:
+    """solve_vrp's slot dict from a giant tour's tokens, each token's vehicle
+    (-1 unvisited, -2 a separator: vrpms_decode's and vrp_batch_sa's) and the K
+    route durations, compact indices mapped back through ci.nodes."""
+    K = len(ci.capacities)
+    routes = [[] for _ in range(K)]
+    unvisited = []
+    for c, v in zip(tour, veh):
+        if v == -2:
+            continue
+        (routes[v] if v >= 0 else unvisited).append(ci.nodes[c])
+    vehicles = [{"tour": [ci.nodes[0]] + r + [ci.nodes[0]], "duration": int(d)}
+                for r, d in zip(routes, durs)]
+    out = {"durationMax": int(max(durs) if len(durs) else 0), "durationSum": int(sum(durs)),
+           "vehicles": vehicles}
+    if with_unvisited:
+        out["unvisited"] = unvisited
+    return out
+
+
+def solve_vrp_sa_batch(requests, *, steps: int = 2000, seed: int = 0, objective: str = "sum",
+                       with_unvisited: bool = False, device: int = 0) -> list:
+    """Simulated annealing for many small-fleet VRP requests, the requests
+    that fit sharing launches (spec A22): one workgroup per request, its whole
+    instance in LDS, four chains of `steps` steps.  `requests`:
+    solve_vrp_batch's (durations, locations, capacities, start_times[,
+    ignored_customers, completed_customers]) tuples, or dicts with those keys
+    -> one solve_vrp slot dict per request.
+
+    This is NOT solve_vrp("sa")'s answer: four chains with A13's one-word
+    moves and a schedule from the request's own matrix (batch_sa_schedule)
+    here, 1,024 chains there.  It is deterministic per request: the dict
+    depends on the request, `steps`, `seed` and `objective` alone, not on the
+    other requests of the call or on its place among them.
+
+    Every request is compacted and passed through batch_guard_message on the
+    host before any device is touched; a bad one raises ValueError("request
+    {x}: ...").  With no local GPU each request goes to solve_vrp("sa") on the
+    GPU box.  Requests inside the LDS domain (batch_sa_fits) are grouped by
+    (N, K, H, wide), one upload and one vrp_batch_sa launch per group, and
+    their dicts are built on the host from the tour tokens, their vehicles and
+    the route durations; no customer has solve_vrp's trivial answer; a
+    request outside the domain takes solve_vrp("sa", seed=seed,
+    objective=objective), one by one."""
+    if objective not in ("sum", "max"):
+        raise ValueError("objective must be 'sum' or 'max'")
+    if int(steps) < 0:
+        raise ValueError("steps must not be negative")
+    reqs, cis = [], []
+    for x, r in enumerate(requests):
+        try:
+            r, _ = _sp_request(r)
+            ci = compact_vrp(*r)
+            msg = batch_guard_message(ci)
+            if msg is not None:
+                raise ValueError(msg)
+        except ValueError as e:
+            raise ValueError(f"request {x}: {e}") from None
+        reqs.append(r)
+        cis.append(ci)
+    shared = dict(seed=seed, objective=objective, with_unvisited=with_unvisited)
+    if _remote() is not None:      # no local GPU: the GPU box answers each request
+        return [solve_vrp("sa", *r, **shared) for r in reqs]
+    out = [None] * len(cis)
+    groups: dict = {}
+    for x, ci in enumerate(cis):
+        if ci.n == 0:
+            out[x] = sa_result(ci, [], [], [0] * len(ci.capacities), with_unvisited)
+        elif batch_sa_fits(ci):
+            groups.setdefault(batch_sa_key(ci), []).append(x)
+        else:
+            out[x] = solve_vrp("sa", *reqs[x], device=device, **shared)
+    if groups:
+        ctx = context(device)
+        for xs in groups.values():
+            rows = batch_sa_launch(ctx, [cis[x] for x in xs], steps, seed, objective)
+            for x, tour, veh, durs in zip(xs, *rows):
+                out[x] = sa_result(cis[x], tour, veh, durs, with_unvisited)
+    return out
 
 
 # ---------------------------------------------------------------------------
