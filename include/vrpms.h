@@ -577,6 +577,49 @@ int vrpms_vrp_batch_sa(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_d
                        int32_t steps, float inv_alpha, uint64_t seed, uint16_t* d_tours,
                        uint64_t* d_keys, int32_t* d_durs, int8_t* d_veh, void* stream);
 
+/* Throughput mode of the VRP genetic algorithm: R
+ * independent CVRP requests of one node count N >= 2 (n = N - 1 customers,
+ * node 0 the depot), one fleet size K, 1 <= K <= 64, one hour count H (1 or
+ * 24), one objective, one population size P, 2 <= P <= 256, one generation
+ * count G >= 0, one mutation threshold pmut and one seed, each with its own
+ * int32 [H][N][N] matrix (d_mats [R][H][N][N]), demands (d_demand [R][N],
+ * entry 0 ignored), capacities (d_cap [R][K], in vehicle order; they may
+ * differ or be 0) and start times (d_start [R][K], minutes).  ONE WORKGROUP
+ * PER REQUEST: the request's whole instance is staged into LDS once -- the
+ * matrix as uint16 with wide = 0, as int32 with wide = 1 -- next to 2P tours
+ * of n customers (no separators; the greedy split A5-A7 prices them).  Member
+ * i starts as the Philox Fisher-Yates shuffle of 1..n with counters
+ * (0xffffffff, 0xffffffff, i, q); generation g is vrpms_ga_generation's on
+ * island 0 with child ids 0..P-1 (blocks (g, 0, child, 0) and (g, 0, child,
+ * 1): two tournaments of two, OX1, a three-word decode_move mutation iff the
+ * third word of the second block < pmut, the P best of parents and children by
+ * (key, index) survive; n < 2 copies parent A).  The counters carry no request
+ * row, so a request's answer depends on the request, P, G, pmut, seed and
+ * objective alone: not on the launch it rode in nor on its row in it.
+ * vrpms_vrp_batch_ga_lds gives the launch's dynamic-LDS bytes for (N, K, H,
+ * wide, P) (host only, no context); a launch that needs more than the device
+ * has is refused with that byte count in the message.  (N + K + 1) * max(D) +
+ * max(start) < 2^31 and cap + demand < 2^31 (A9) are the caller's promise.
+ * Out, per request, the member of the least (key, index) after the last
+ * generation (among the start members for G = 0): d_tours [R][n], d_keys [R]
+ * (its A8 key), d_durs [R][K] (the K route durations of that tour, unclamped,
+ * 0 for an empty route) and d_veh [R][n] (the vehicle of every gene, -1 for an
+ * unvisited customer).  A request whose matrix has a negative entry, or with
+ * wide = 0 one above 65535, gets UINT64_MAX, an all-zero tour, zero durations
+ * and vehicles of -1, breeds nothing and touches nothing else.  No instance
+ * and no workspace needed; asynchronous on `stream`.  R = 0 launches nothing.
+ * VRPMS_EINVAL, with nothing launched and nothing written, for a NULL ctx,
+ * R < 0, N outside 2..65535, K outside 1..64, H other than 1 or 24, an unknown
+ * wide or objective, P outside 2..256, G < 0, a NULL buffer with R > 0, or an
+ * LDS need above the device's. */
+int vrpms_vrp_batch_ga_lds(int32_t N, int32_t K, int32_t H, int32_t wide, int32_t P,
+                           uint64_t* bytes);
+int vrpms_vrp_batch_ga(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_demand,
+                       const int32_t* d_cap, const int32_t* d_start, int32_t R, int32_t N,
+                       int32_t K, int32_t H, int32_t objective, int32_t wide, int32_t P, int32_t G,
+                       uint32_t pmut, uint64_t seed, uint16_t* d_tours, uint64_t* d_keys,
+                       int32_t* d_durs, int8_t* d_veh, void* stream);
+
 /* ------------------------------------------------------------------------
  * Populations and the island model.  A pool is a set of
  * tours with their A8 keys: SA chains, a GA population ([islands][pop],

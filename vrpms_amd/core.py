@@ -83,6 +83,17 @@ def vrp_batch_sa_lds(N: int, K: int, H: int, wide) -> int:
     return int(nbytes.value)
 
 
+def vrp_batch_ga_lds(N: int, K: int, H: int, wide, P: int) -> int:
+    """vrpms_vrp_batch_ga_lds: the dynamic-LDS bytes of a vrp_batch_ga launch
+    for N nodes, K vehicles, H hour slices (1 or 24), a uint16 (`wide` false)
+    or int32 (`wide` true) matrix and a population of P.  Host only: needs the
+    library, no GPU."""
+    nbytes = ctypes.c_uint64()
+    check(_lib.load().vrpms_vrp_batch_ga_lds(int(N), int(K), int(H), int(wide), int(P),
+                                             ctypes.byref(nbytes)))
+    return int(nbytes.value)
+
+
 def tdp_words(start: int, horizon: int) -> int:
     """Hour words of one A16 row: the words from the start's hour to the one
     of start + horizon."""
@@ -675,6 +686,51 @@ class Context:
                                           float(inv_alpha), int(seed) & (2**64 - 1),
                                           tours.data_ptr(), keys.data_ptr(), durs.data_ptr(),
                                           veh.data_ptr(), self.stream()))
+        return tours, keys, durs, veh
+
+    def vrp_batch_ga(self, mats, demand, caps, starts, objective: int, pop: int, gens: int,
+                     pmut: float, seed: int, wide=None):
+        """A genetic algorithm per request, one workgroup per request, one
+        launch for all (spec A23; all requests of one N, K, H and objective):
+        mats int32 [R][H][N][N] (H = 1 or 24; [R][N][N] is taken as H = 1),
+        demand int32 [R][N] (entry 0 ignored), caps and starts int32 [R][K] on
+        the device -> (tours int16 [R][n], keys int64 [R], durs int32 [R][K],
+        veh int8 [R][n]) with n = N - 1: per request the member of the least
+        (key, index) after `gens` generations of a population of `pop`
+        (2..256) separator-free tours, its A8 key, its K route durations
+        (unclamped, 0 for an empty route) and the vehicle of every gene (-1
+        unvisited).  `pmut` is the mutation probability, converted as
+        ga_generation does: min(round(pmut * 2^32), 2^32 - 1).  A request's
+        row depends on the request, `pop`, `gens`, `pmut`, `seed` and
+        `objective` alone, not on the batch.  `wide`: False stages the
+        matrices as uint16 (a request with an entry above 65535 then gets an
+        all-ones key, a zero tour, zero durations and veh = -1), True as
+        int32; None -- the default -- asks the device for the batch's largest
+        entry, which synchronises.  The A9 guard and non-negative demands and
+        capacities are the caller's promise.  Asynchronous on the current
+        stream."""
+        torch = _torch()
+        mats = self._batch_mats(torch, mats, 4)
+        R, H, N, _ = mats.shape
+        self._batch_rows(torch, demand, caps, R, N)
+        K = caps.shape[1]
+        if starts.device != self.dev or starts.shape != caps.shape or starts.dtype != torch.int32 \
+                or not starts.is_contiguous():
+            raise ValueError(f"starts must be a contiguous int32 [R][K] tensor on {self.dev}")
+        if wide is None:
+            wide = bool(R) and int(mats.max().item()) > 65535
+        pm = min(int(round(float(pmut) * 2**32)), 2**32 - 1)
+        n = N - 1
+        tours = torch.empty((R, max(n, 1)), dtype=torch.int16, device=self.dev)
+        keys = torch.empty(R, dtype=torch.int64, device=self.dev)
+        durs = torch.empty((R, max(K, 1)), dtype=torch.int32, device=self.dev)
+        veh = torch.empty((R, max(n, 1)), dtype=torch.int8, device=self.dev)
+        check(self.lib.vrpms_vrp_batch_ga(self._ctx, mats.data_ptr(), demand.data_ptr(),
+                                          caps.data_ptr(), starts.data_ptr(), R, N, K, H,
+                                          int(objective), int(bool(wide)), int(pop), int(gens), pm,
+                                          int(seed) & (2**64 - 1), tours.data_ptr(),
+                                          keys.data_ptr(), durs.data_ptr(), veh.data_ptr(),
+                                          self.stream()))
         return tours, keys, durs, veh
 
     def set_batch_dp_team(self, T: int):

@@ -32,6 +32,7 @@
 
 #include <string>
 
+#include "batch_stage.hpp"
 #include "common.hpp"
 #include "ctx.hpp"
 #include "staging.hpp"
@@ -87,39 +88,14 @@ __global__ __launch_bounds__(256) void vrp_batch_sa_kernel(VrpBatchSaArgs a) {
   uint16_t* tours = reinterpret_cast<uint16_t*>(start + row_words);
   uint64_t* wbest = reinterpret_cast<uint64_t*>(tours + 4 * 3 * tpad);
 
-  // stage and check the request
-  const int32_t* src = a.mats + r * (int64_t)cells;
-  // the verdict goes through a word of the dynamic LDS (wbest, free until the
-  // chains end): __syncthreads_or would add static LDS on top of the bytes
-  // vrpms_vrp_batch_sa_lds promises
-  uint32_t* flag = reinterpret_cast<uint32_t*>(wbest);
-  if (threadIdx.x == 0) *flag = 0;
-  __syncthreads();
-  bool bad = false;
-  for (uint32_t i = threadIdx.x; i < cells; i += 256) {
-    const int32_t v = src[i];
-    bad |= v < 0 || (sizeof(MatT) == 2 && v > 65535);
-    M[i] = (MatT)v;
-  }
-  for (int i = threadIdx.x; i < N; i += 256) dem[i] = a.demand[r * N + i];
-  for (int k = threadIdx.x; k < K; k += 256) {
-    cap[k] = a.cap[r * K + k];
-    start[k] = a.start[r * K + k];
-  }
+  // stage and check the request (batch_stage.hpp); the verdict goes through
+  // a word of wbest, free until the chains end
   uint16_t* gtour = a.tours + r * ntok;
   int8_t* gveh = a.veh + r * ntok;
   int32_t* gdurs = a.durs + r * K;
-  if (bad) *flag = 1;
-  __syncthreads();
-  bad = *flag != 0;
-  __syncthreads();   // every wavefront has read the word before any chain's key replaces it
-  if (bad) {  // outside the launch's promise: no step
-    for (int q = threadIdx.x; q < ntok; q += 256) {
-      gtour[q] = 0;
-      gveh[q] = -1;
-    }
-    for (int k = threadIdx.x; k < K; k += 256) gdurs[k] = 0;
-    if (threadIdx.x == 0) a.keys[r] = ~0ull;
+  if (batch_stage_request(a.mats, a.demand, a.cap, a.start, r, cells, N, K, M, dem, cap, start,
+                          reinterpret_cast<uint32_t*>(wbest))) {  // outside the launch's promise: no step
+    batch_refuse(gtour, gveh, gdurs, a.keys + r, ntok, K);
     return;
   }
 
@@ -253,43 +229,7 @@ __global__ __launch_bounds__(256) void vrp_batch_sa_kernel(VrpBatchSaArgs a) {
   // walks alike, lane k keeps route k's duration, lane 0 notes the vehicles
   // (as int16 in the chain's scratch tour)
   int16_t* V = reinterpret_cast<int16_t*>(B);
-  int mydur = 0;
-  {
-    int k = 0, load = 0, t = start[0], prev = 0;
-    auto close_route = [&]() {
-      if (prev) {
-        t += D(t, (uint32_t)prev, 0);
-        if (lane == k) mydur = t - start[k];
-      }
-      ++k;
-      if (k < K) {
-        load = 0;
-        t = start[k];
-        prev = 0;
-      }
-    };
-    for (int i = 0; i < ntok; ++i) {
-      const int c = (int)min((uint32_t)Best[i], (uint32_t)n);
-      int v;
-      if (c == 0) {
-        v = -2;
-        if (k < K) close_route();
-      } else {
-        const int dc = dem[c];
-        while (k < K && load + dc > cap[k]) close_route();
-        if (k < K) {
-          t += D(t, (uint32_t)prev, (uint32_t)c);
-          load += dc;
-          prev = c;
-          v = k;
-        } else {
-          v = -1;
-        }
-      }
-      if (lane == 0) V[i] = (int16_t)v;
-    }
-    if (k < K) close_route();
-  }
+  const int mydur = batch_final_walk(D, dem, cap, start, K, n, Best, ntok, V, lane);
   wave_sync();
   for (int q = lane; q < ntok; q += 64) {
     gtour[q] = Best[q];

@@ -496,6 +496,53 @@ class VrpSaBatcher(TspBatcher):
         return tours, list(zip(veh, durs))
 
 
+class VrpGaBatcher(VrpSaBatcher):
+    """Coalesces concurrent /api/vrp/ga and /solve/vrp/ga requests into one
+    `vrp_batch_ga` launch per (node count, fleet size, hour count, cell width,
+    objective, population, generations) (spec A23: one workgroup per request,
+    its whole instance and one population in LDS).  The population and the
+    generation count are the request's own randomPermutationCount and
+    iterationCount, through solve_vrp's defaults and clamp (solver.ga_knobs).
+    The queue, the window, the device round-robin and the error fan-out are
+    TspBatcher's.  A batched answer does not depend on the batch: it is
+    solver.solve_vrp_ga_batch([request], pop=, gens=, seed=the app's,
+    objective=)'s.  It is NOT the unbatched endpoint's answer, which breeds 8
+    islands from another start."""
+
+    pmut = 0.2     # solve_vrp_ga_batch's default
+
+    @classmethod
+    def accepts(cls, ci, pop: int = 256, gens: int = 400) -> bool:
+        """Requests inside A23's domain (LDS, pop <= 256, the generation cap)
+        that pass the int32 guards vrpms_set_instance applies on the unbatched
+        path; anything else takes the unbatched path."""
+        from . import solver
+        return solver.batch_ga_fits(ci, pop, gens) and solver.batch_guard_message(ci) is None
+
+    @staticmethod
+    def group_key(job):
+        from . import solver
+        return solver.batch_sa_key(job["ci"]) + (job["objective"], job["pop"], job["gens"])
+
+    def solve(self, ci, objective: str = "sum", pop: int = 256, gens: int = 400) -> dict:
+        """Blocks until the request's launch finished -> the VRP slot dict."""
+        from . import solver
+        job = {"ci": ci, "done": threading.Event(), "objective": _objective(objective),
+               "pop": int(pop), "gens": int(gens)}
+        self._wait(job)
+        veh, durs = job["duration"]
+        return solver.sa_result(ci, list(job["tour"]), veh, durs)
+
+    def _gpu_launch(self, key, cis, device=None):
+        from . import solver
+        dev = self.devices[0] if device is None else device
+        objective, pop, gens = key[-3:]
+        with self.app.locks[dev]:
+            tours, veh, durs = solver.batch_ga_launch(solver.context(dev), cis, pop, gens, self.pmut,
+                                                      self.app.seed, objective)
+        return tours, list(zip(veh, durs))
+
+
 # ---------------------------------------------------------------------------
 # the endpoint logic
 # ---------------------------------------------------------------------------
@@ -519,7 +566,8 @@ class App:
                  island_min_n: int = 150, batch_exact: bool = False, batch_exact_launch=None,
                  batch_exact_vrp_launch=None, batch_exact_tdp_launch=None,
                  batch_exact_tdsp: bool = False, batch_exact_tdsp_launch=None,
-                 batch_vrp_sa: bool = False, batch_vrp_sa_launch=None):
+                 batch_vrp_sa: bool = False, batch_vrp_sa_launch=None,
+                 batch_vrp_ga: bool = False, batch_vrp_ga_launch=None):
         self.store = store
         self.devices = list(devices) if devices else [device]
         self.device = self.devices[0]
@@ -554,6 +602,11 @@ class App:
         self.vrp_sa_batcher = VrpSaBatcher(self, batch_window_s, batch_steps,
                                            launch=batch_vrp_sa_launch) \
             if batch_vrp_sa else None
+
+        # small-fleet VRP GA requests share vrp_batch_ga launches (off by
+        # default: the batched answer is not the unbatched endpoint's)
+        self.vrp_ga_batcher = VrpGaBatcher(self, batch_window_s, launch=batch_vrp_ga_launch) \
+            if batch_vrp_ga else None
 
     def _scheduled(self, problem, algorithm, params, knobs, locations, durations):
         """Run the solve on a device: all of them (in order, as an island
@@ -612,6 +665,34 @@ class App:
         ci = solver.compact_vrp(durations, locations, params["capacities"], params["start_times"],
                                 params["ignored_customers"], params["completed_customers"])
         return ci if self.vrp_sa_batcher.accepts(ci) else None
+
+    def _batched_vrp_ga(self, problem, algorithm, params, knobs, locations, durations):
+        """(compact instance, pop, gens) when this request rides the VRP GA
+        batcher, else None: the flag is on, the route is vrp / ga, the request
+        names no inline knob of its own, its multiThreaded is not true, and
+        its population (at most 256), generations (at most the cap) and
+        instance are inside the batcher's domain."""
+        if self.vrp_ga_batcher is None or (problem, algorithm) != ("vrp", "ga") or \
+                knobs.get("inline") or multi_threaded(knobs.get("multi_threaded")) is True:
+            return None
+        from . import solver
+        pop, gens = solver.ga_knobs(knobs.get("random_permutationCount"),
+                                    knobs.get("iteration_count"))
+        ci = solver.compact_vrp(durations, locations, params["capacities"], params["start_times"],
+                                params["ignored_customers"], params["completed_customers"])
+        return (ci, pop, gens) if self.vrp_ga_batcher.accepts(ci, pop, gens) else None
+
+    def _batched_vrp(self, problem, algorithm, params, knobs, locations, durations):
+        """A thunk that solves this request on the VRP SA or GA batcher, else
+        None."""
+        objective = knobs.get("objective", "sum")
+        vci = self._batched_vrp_sa(problem, algorithm, params, knobs, locations, durations)
+        if vci is not None:
+            return lambda: self.vrp_sa_batcher.solve(vci, objective)
+        gci = self._batched_vrp_ga(problem, algorithm, params, knobs, locations, durations)
+        if gci is not None:
+            return lambda: self.vrp_ga_batcher.solve(gci[0], objective, gci[1], gci[2])
+        return None
 
     def _exact_batcher(self, problem, algorithm):
         """The exact batcher of an inline (problem, algorithm), or None."""
@@ -688,11 +769,11 @@ class App:
             batcher = {("tsp", "sa"): self.batcher,
                        ("tsp", "bf"): self.exact_batcher}.get((problem, algorithm))
             ci = self._batched_tsp(params, durations, batcher) if batcher is not None else None
-            vci = self._batched_vrp_sa(problem, algorithm, params, knobs, locations, durations)
+            vrp = self._batched_vrp(problem, algorithm, params, knobs, locations, durations)
             if ci is not None:
                 result = batcher.solve(ci)
-            elif vci is not None:
-                result = self.vrp_sa_batcher.solve(vci, knobs.get("objective", "sum"))
+            elif vrp is not None:
+                result = vrp()
             else:
                 result = self._scheduled(problem, algorithm, params, knobs, locations, durations)
         except Exception as e:   # bad instance shape, GPU unavailable, ...
@@ -783,12 +864,12 @@ class App:
             batcher = self._exact_batcher(problem, algorithm)
             args = self._batched(batcher, params, knobs, locations, vals["durations"]) \
                 if batcher is not None else None
-            vci = self._batched_vrp_sa(problem, algorithm, params, knobs, locations,
-                                       vals["durations"])
+            vrp = self._batched_vrp(problem, algorithm, params, knobs, locations,
+                                    vals["durations"])
             if args is not None:
                 result = batcher.solve(*args)
-            elif vci is not None:
-                result = self.vrp_sa_batcher.solve(vci, knobs.get("objective", "sum"))
+            elif vrp is not None:
+                result = vrp()
             else:
                 result = self._scheduled(problem, algorithm, params, knobs, locations,
                                          vals["durations"])
@@ -918,6 +999,15 @@ def main(argv=None):
                          "steps: four chains per request, so the answer differs from the "
                          "unbatched endpoint's; it depends on the request alone, not on the "
                          "batch it rode in")
+    ap.add_argument("--batch-vrp-ga", action="store_true",
+                    help="coalesce concurrent small-fleet VRP GA requests (/api/vrp/ga and "
+                         "/solve/vrp/ga, static or hour-indexed matrix, 1..64 vehicles, "
+                         "randomPermutationCount up to 256, iterationCount up to "
+                         "solver.BATCH_GA_MAX_GENERATIONS, multiThreaded not true, an instance "
+                         "and population that fit the LDS) into vrp_batch_ga launches: one "
+                         "population per request, so the answer differs from the unbatched "
+                         "endpoint's; it depends on the request alone, not on the batch it "
+                         "rode in")
     ap.add_argument("--batch-window-ms", type=float, default=5.0)
     ap.add_argument("--batch-steps", type=int, default=2000)
     ap.add_argument("--workers", type=int, default=0,
@@ -956,7 +1046,8 @@ def main(argv=None):
     app = App(store, device=args.device, seed=args.seed, max_seconds=args.max_seconds,
               batch_tsp=args.batch_tsp, batch_window_s=args.batch_window_ms * 1e-3,
               batch_steps=args.batch_steps, devices=devices, batch_exact=args.batch_exact,
-              batch_exact_tdsp=args.batch_exact_tdsp, batch_vrp_sa=args.batch_vrp_sa)
+              batch_exact_tdsp=args.batch_exact_tdsp, batch_vrp_sa=args.batch_vrp_sa,
+              batch_vrp_ga=args.batch_vrp_ga)
     srv = serve(app, args.host, args.port)
     print(f"vrpms_amd service on http://{args.host}:{args.port}/api", flush=True)
     try:

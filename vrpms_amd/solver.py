@@ -116,6 +116,15 @@ BATCH_TDSP_LDS_BYTES = 160 * 1024
 # (K, H, wide).  Other requests of a batch take the single-request path
 BATCH_SA_MAX_VEHICLES = 64
 BATCH_SA_LDS_BYTES = 160 * 1024
+# batched VRP GA (A23): next to the instance, 2 pop tours, their keys and the
+# sort pairs have to fit the same budget (vrpms_vrp_batch_ga_lds gives the bytes
+# for (N, K, H, wide, pop)); DESIGN.md §4.3n has the largest N per (H, wide,
+# pop).  A launch has no time limit, so a request of more generations than
+# BATCH_GA_MAX_GENERATIONS -- five times the endpoint's default of 400 -- takes
+# the unbatched path, which has one
+BATCH_GA_MAX_POP = 256
+BATCH_GA_MAX_GENERATIONS = 2000
+BATCH_GA_LDS_BYTES = BATCH_SA_LDS_BYTES
 # SA on tours of more than SA_WINDOW_MIN_N customers samples A11 windowed
 # moves (second position within SA_WINDOW of the first)
 SA_WINDOW, SA_WINDOW_MIN_N = 32, 150
@@ -1110,6 +1119,126 @@ def solve_vrp_sa_batch(requests, *, steps: int = 2000, seed: int = 0, objective:
         ctx = context(device)
         for xs in groups.values():
             rows = batch_sa_launch(ctx, [cis[x] for x in xs], steps, seed, objective)
+            for x, tour, veh, durs in zip(xs, *rows):
+                out[x] = sa_result(cis[x], tour, veh, durs, with_unvisited)
+    return out
+
+
+# ---------------------------------------------------------------------------
+# batched VRP GA (A23): small-fleet requests share launches
+# ---------------------------------------------------------------------------
+def batch_ga_key(ci: CompactInstance, pop: int, gens: int):
+    """What the instances of one vrp_batch_ga launch share (next to the
+    objective, pmut and the seed): (N, K, H, wide, pop, gens)."""
+    return batch_sa_key(ci) + (int(pop), int(gens))
+
+
+def batch_ga_fits(ci: CompactInstance, pop: int, gens: int) -> bool:
+    """A23's domain: a CVRP of at least one customer, 1..64 vehicles, a static
+    or 24-slice matrix, 2 <= pop <= BATCH_GA_MAX_POP, 0 <= gens <=
+    BATCH_GA_MAX_GENERATIONS, and an instance that fits BATCH_GA_LDS_BYTES
+    together with its 2 pop tours (vrpms_vrp_batch_ga_lds; uint16 cells unless
+    an entry is above 65535).  Needs the library, no GPU."""
+    from .core import vrp_batch_ga_lds
+    if ci.problem != CVRP or ci.n < 1 or ci.N > 65535:
+        return False
+    if not 2 <= int(pop) <= BATCH_GA_MAX_POP or not 0 <= int(gens) <= BATCH_GA_MAX_GENERATIONS:
+        return False
+    N, K, H, wide = batch_sa_key(ci)
+    if not 1 <= K <= BATCH_SA_MAX_VEHICLES or H not in (1, 24):
+        return False
+    return vrp_batch_ga_lds(N, K, H, wide, int(pop)) <= BATCH_GA_LDS_BYTES
+
+
+def batch_ga_launch(ctx: Context, cis, pop: int, gens: int, pmut: float, seed: int,
+                    objective: str = "sum"):
+    """One upload and one vrp_batch_ga launch for compact instances of one
+    batch_ga_key (each passed batch_guard_message and batch_ga_fits) ->
+    (tours, veh, durs): per instance the n genes of the best member, each
+    gene's vehicle (-1 unvisited) and the K route durations."""
+    import torch
+    mats, demand, caps = _stage(ctx, cis, hours=True)
+    starts = torch.from_numpy(np.array([ci.start_times for ci in cis], dtype=np.int32)).to(ctx.dev)
+    tours, keys, durs, veh = ctx.vrp_batch_ga(mats, demand, caps, starts,
+                                              OBJ_MAX if objective == "max" else OBJ_SUM,
+                                              int(pop), int(gens), float(pmut), seed,
+                                              wide=batch_sa_wide(cis[0]))
+    if (keys == -1).any().item():
+        raise RuntimeError("vrp_batch_ga: a request was outside the launch's contract")
+    return tours.cpu().tolist(), veh.cpu().tolist(), durs.cpu().tolist()
+
+
+def ga_knobs(random_permutation_count=None, iteration_count=None):
+    """(pop, gens) as solve_vrp("ga") takes a request's randomPermutationCount
+    and iterationCount: 256 / 400 when falsy, pop clamped to 2..4096."""
+    return max(2, min(int(random_permutation_count or 256), 4096)), int(iteration_count or 400)
+
+
+def solve_vrp_ga_batch(requests, *, pop: int = 256, gens: int = 400, pmut: float = 0.2,
+                       seed: int = 0, objective: str = "sum", with_unvisited: bool = False,
+                       device: int = 0) -> list:
+    """A genetic algorithm for many small-fleet VRP requests, the requests
+    that fit sharing launches (spec A23): one workgroup per request, its whole
+    instance and one population of `pop` separator-free tours in LDS, `gens`
+    generations of tournament selection, OX1, a `pmut` mutation and (mu +
+    lambda) survivors.  `requests`: solve_vrp_batch's (durations, locations,
+    capacities, start_times[, ignored_customers, completed_customers]) tuples,
+    or dicts with those keys -> one solve_vrp slot dict per request.
+
+    This is NOT solve_vrp("ga")'s answer: one population with a Philox
+    Fisher-Yates start here, 8 islands with migration and another start there.
+    It is deterministic per request: the dict depends on the request, `pop`,
+    `gens`, `pmut`, `seed` and `objective` alone, not on the other requests of
+    the call or on its place among them.
+
+    Every request is compacted and passed through batch_guard_message on the
+    host before any device is touched; a bad one raises ValueError("request
+    {x}: ...").  With no local GPU each request goes to solve_vrp("ga") on the
+    GPU box.  Requests inside the domain (batch_ga_fits) are grouped by (N, K,
+    H, wide), one upload and one vrp_batch_ga launch per group, and their
+    dicts are built on the host from the genes, their vehicles and the route
+    durations; no customer has solve_vrp's trivial answer; a request outside
+    the domain (also every request when `pop` is above BATCH_GA_MAX_POP or
+    `gens` above BATCH_GA_MAX_GENERATIONS) takes solve_vrp("ga", seed=seed,
+    objective=objective, random_permutation_count=pop, iteration_count=gens),
+    one by one."""
+    if objective not in ("sum", "max"):
+        raise ValueError("objective must be 'sum' or 'max'")
+    if int(pop) < 2:
+        raise ValueError("pop must be at least 2")
+    if int(gens) < 0:
+        raise ValueError("gens must not be negative")
+    if not 0.0 <= float(pmut) <= 1.0:
+        raise ValueError("pmut must be a probability")
+    reqs, cis = [], []
+    for x, r in enumerate(requests):
+        try:
+            r, _ = _sp_request(r)
+            ci = compact_vrp(*r)
+            msg = batch_guard_message(ci)
+            if msg is not None:
+                raise ValueError(msg)
+        except ValueError as e:
+            raise ValueError(f"request {x}: {e}") from None
+        reqs.append(r)
+        cis.append(ci)
+    shared = dict(seed=seed, objective=objective, with_unvisited=with_unvisited,
+                  random_permutation_count=int(pop), iteration_count=int(gens))
+    if _remote() is not None:      # no local GPU: the GPU box answers each request
+        return [solve_vrp("ga", *r, **shared) for r in reqs]
+    out = [None] * len(cis)
+    groups: dict = {}
+    for x, ci in enumerate(cis):
+        if ci.n == 0:
+            out[x] = sa_result(ci, [], [], [0] * len(ci.capacities), with_unvisited)
+        elif batch_ga_fits(ci, pop, gens):
+            groups.setdefault(batch_ga_key(ci, pop, gens), []).append(x)
+        else:
+            out[x] = solve_vrp("ga", *reqs[x], device=device, **shared)
+    if groups:
+        ctx = context(device)
+        for xs in groups.values():
+            rows = batch_ga_launch(ctx, [cis[x] for x in xs], pop, gens, pmut, seed, objective)
             for x, tour, veh, durs in zip(xs, *rows):
                 out[x] = sa_result(cis[x], tour, veh, durs, with_unvisited)
     return out
