@@ -155,7 +155,8 @@ int vrpms_instance_layout(vrpms_ctx* ctx, int32_t n, int32_t* out, int32_t count
  *   also used for heterogeneous fleets, A/B only). */
 #define VRPMS_OPT_WORDS_KERNEL 3
 /*   VRPMS_OPT_WORDS_ILP: candidates per lane in eval_cvrp_words2 (0 = auto:
- *   2; 2 force; 1 only in libraries built with -DVRPMS_AB, A/B). */
+ *   2; 2 force; 1 only in libraries built with -DVRPMS_AB, A/B, where 3..6
+ *   also force two per lane in workgroup shape 0..3 of launch_words2). */
 #define VRPMS_OPT_WORDS_ILP 4
 /*   VRPMS_OPT_WORDS_LOOKAHEAD: words ahead whose gathers eval_cvrp_words2
  *   keeps in flight (0 = auto, 1 or 2 force; A/B). */

@@ -280,8 +280,9 @@ int vrpms_set_option(vrpms_ctx* ctx, int32_t option, int32_t value) {
   }
   if (option == VRPMS_OPT_WORDS_ILP) {
 #ifdef VRPMS_AB
-    if (value < 0 || value > 2)
-      return fail(VRPMS_EINVAL, "vrpms_set_option: words ILP must be 0 (auto), 1 or 2");
+    // 3..6: two candidates per lane in workgroup shape 0..3 (launch_words2)
+    if (value < 0 || value > 6)
+      return fail(VRPMS_EINVAL, "vrpms_set_option: words ILP must be 0 (auto), 1, 2 or 3..6");
 #else
     if (value != 0 && value != 2)
       return fail(VRPMS_EINVAL,

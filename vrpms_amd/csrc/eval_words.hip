@@ -15,7 +15,8 @@
 //   * route closure in 2 VALU: v_and_or_b32 builds (acc & smask) | kinc with
 //     smask held in a VGPR (gfx9 VOP3 reads one SGPR), then one cndmask;
 //   * two candidates per lane (ILP = 2): two independent split chains hide
-//     each other's gather latency, one 1024-lane workgroup per CU;
+//     each other's gather latency, in two 768-lane workgroups per CU where
+//     two copies of E fit the LDS, else one of 1024 lanes (launch_words2);
 //   * the next word's address math is interleaved into the current word's
 //     split chain (sched_group_barrier), so ds_reads issue well before use.
 //
@@ -30,7 +31,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <type_traits>
+#include <mutex>
+#include <vector>
 
 #include "common.hpp"
 #include "ctx.hpp"
@@ -40,20 +42,31 @@
 
 namespace vrpms {
 
-template <int R, int ILP, int LA, bool CY>
-__global__ __launch_bounds__(1024) void eval_cvrp_words2(WordsArgs a) {
+// TPB lanes per workgroup, WPS wavefronts per SIMD the register budget must
+// leave room for (launch_words2 picks the shape).  WV: every wavefront strides
+// over tiles of 64 * ILP candidates on its own (tile t of a round goes to
+// wavefront t / grid of workgroup t % grid, so a ragged last round is spread
+// over all workgroups) instead of the workgroup over TPB * ILP; the loop has
+// no barrier.
+template <int R, int ILP, int LA, bool CY, int TPB, int WPS, bool WV>
+__global__ __launch_bounds__(TPB, WPS) void eval_cvrp_words2(WordsArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   stage_table(a.f.pack, a.f.N, smem);
   WordChains<ILP, CY> ch;
   ch.setup(a.f, smem);
   const int64_t C = a.C;
   const int n = a.n, nw = (n + 3) >> 2, nfull = n >> 2;
-  constexpr int SPAN = 1024 * ILP;  // candidates per workgroup pass
+  constexpr int SPAN = TPB * ILP;  // candidates per workgroup pass
+  constexpr int CS = WV ? 64 : TPB;  // candidates between a lane's two
   const int64_t stride = (int64_t)gridDim.x * SPAN;
   const int nblk = nfull / R;  // blocks of R full words: the fast loop
+  const uint32_t tid = WV ? threadIdx.x & 63u : threadIdx.x;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // uniform: c0 in SGPRs
+  const int64_t first = WV ? ((int64_t)wave * gridDim.x + blockIdx.x) * (64 * ILP)
+                           : blockIdx.x * (int64_t)SPAN;
 
-  for (int64_t c0 = blockIdx.x * (int64_t)SPAN; c0 < C; c0 += stride) {
-    // a lane's i-th candidate is c0 + tid + 1024 i (re-pointed at its first
+  for (int64_t c0 = first; c0 < C; c0 += stride) {
+    // a lane's i-th candidate is c0 + tid + CS i (re-pointed at its first
     // one when past the end: computed, never stored).  Word w of every
     // candidate of this pass lives at row(w) = words + w*C + c0 (uniform,
     // SGPR) plus the lane's 32-bit offset.
@@ -61,8 +74,8 @@ __global__ __launch_bounds__(1024) void eval_cvrp_words2(WordsArgs a) {
     bool live[ILP];
 #pragma unroll
     for (int i = 0; i < ILP; ++i) {
-      live[i] = c0 + threadIdx.x + 1024 * i < C;
-      lane[i] = live[i] ? threadIdx.x + 1024u * i : threadIdx.x;
+      live[i] = c0 + tid + CS * i < C;
+      lane[i] = live[i] ? tid + (uint32_t)CS * i : tid;
     }
     if (!live[0]) continue;
     const uint32_t* row = a.words + c0 * a.cstride;
@@ -159,7 +172,7 @@ __global__ __launch_bounds__(1024) void eval_cvrp_words2(WordsArgs a) {
     }
 #pragma unroll
     for (int i = 0; i < ILP; ++i) {
-      const int64_t c = c0 + threadIdx.x + 1024 * i;
+      const int64_t c = c0 + tid + CS * i;
       if (!live[i]) continue;
       // a walk that met the fleet limit is re-walked exactly
       const TourCost tc = (int32_t)ch.sa[i].dsum < 0
@@ -309,57 +322,165 @@ __global__ __launch_bounds__(1024) void eval_cvrp_rows2(RowsArgs a) {
   }
 }
 
+using Words2Kern = void (*)(WordsArgs);
+
+// Workgroup shapes of eval_cvrp_words2 (two candidates per lane in each):
+// lanes per workgroup, workgroups per CU, wavefronts per SIMD.
+//   0: 1024 x 1, 4 wavefronts
+//   1:  768 x 2, 6 wavefronts (<= 80 VGPRs)
+//   2: 1024 x 2, 8 wavefronts (<= 64 VGPRs), lookahead 1 only
+//   3: shape 1 with every wavefront striding on its own, lookahead 1 only
+// The shipped library holds shape 0 and VRPMS_WORDS_SHAPE; -DVRPMS_AB builds
+// hold all four (VRPMS_OPT_WORDS_ILP = 3 + shape forces one there).
+#ifndef VRPMS_WORDS_SHAPE
+#define VRPMS_WORDS_SHAPE 3
+#endif
+// words of gathers in flight in a two-workgroup shape unless option 5 forces
+#ifndef VRPMS_WORDS_SHAPE_LA
+#define VRPMS_WORDS_SHAPE_LA 1
+#endif
+
+// The instantiation for ring depth R (4..8, words2_ring); a shape is built
+// for R <= RMAX only and has none (null) above.
+template <int I, int L, bool C, int TPB, int WPS, bool WV, int RMAX>
+static Words2Kern words2_at(int R) {
+  switch (R) {
+    case 4: return eval_cvrp_words2<4, I, L, C, TPB, WPS, WV>;
+    case 5: return eval_cvrp_words2<5, I, L, C, TPB, WPS, WV>;
+    case 6: return eval_cvrp_words2<6, I, L, C, TPB, WPS, WV>;
+  }
+  if constexpr (RMAX >= 8) {
+    if (R == 7) return eval_cvrp_words2<7, I, L, C, TPB, WPS, WV>;
+    return eval_cvrp_words2<8, I, L, C, TPB, WPS, WV>;
+  }
+  return nullptr;
+}
+
+template <int I, int L, int TPB, int WPS, bool WV = false, int RMAX = 8>
+static Words2Kern words2_kern(int R, bool cy) {
+  return cy ? words2_at<I, L, true, TPB, WPS, WV, RMAX>(R)
+            : words2_at<I, L, false, TPB, WPS, WV, RMAX>(R);
+}
+
+// The kernel of a two-workgroup shape for this lookahead, or null where the
+// library has none.  The 768-lane shapes stop at R = 6: at R = 7 and 8 the
+// ring no longer fits 80 VGPRs and the compiler spills.
+static Words2Kern words2_shape_kern(int shape, int la, int R, bool cy) {
+#if defined(VRPMS_AB) || VRPMS_WORDS_SHAPE == 1
+  if (shape == 1)
+    return la == 2 ? words2_kern<2, 2, 768, 6, false, 6>(R, cy)
+                   : words2_kern<2, 1, 768, 6, false, 6>(R, cy);
+#endif
+#if defined(VRPMS_AB) || VRPMS_WORDS_SHAPE == 2
+  if (shape == 2 && la == 1) return words2_kern<2, 1, 1024, 8>(R, cy);
+#endif
+#if defined(VRPMS_AB) || VRPMS_WORDS_SHAPE == 3
+  if (shape == 3 && la == 1) return words2_kern<2, 1, 768, 6, true, 6>(R, cy);
+#endif
+  return nullptr;
+}
+
+// Workgroups of kern that one CU holds at this LDS size, by the runtime's
+// own count (registers and LDS allocation granularity); 0 for a kernel the
+// compiler gave scratch memory.  Asked once per (kernel, size).
+static int words2_resident(Words2Kern kern, int tpb, size_t lds) {
+  struct Seen { Words2Kern kern; size_t lds; int wgs; };
+  static std::mutex mu;
+  static std::vector<Seen> seen;
+  std::lock_guard<std::mutex> lock(mu);
+  for (const Seen& e : seen)
+    if (e.kern == kern && e.lds == lds) return e.wgs;
+  int wgs = 0;
+  const void* fn = reinterpret_cast<const void*>(kern);
+  bool ok = true;
+#ifndef VRPMS_AB  // an A/B build times a forced shape as it is
+  hipFuncAttributes attr;
+  ok = hipFuncGetAttributes(&attr, fn) == hipSuccess && attr.localSizeBytes == 0;
+#endif
+  if (!ok || hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, fn, tpb, lds) != hipSuccess) {
+    (void)hipGetLastError();
+    wgs = 0;
+  }
+  seen.push_back({kern, lds, wgs});
+  return wgs;
+}
+
 int launch_words2(const vrpms_ctx* ctx, const WordsArgs& w, int R, hipStream_t s) {
   const Instance& in = ctx->inst;
   const size_t lds = ((size_t)in.N * in.N * 8 + 15) & ~(size_t)15;
-  // Auto: two chains per lane (one 1024-lane workgroup per CU), two words of
-  // gathers in flight when the matrix is small enough for two workgroups'
-  // copies (N <= 101), else one.  Measured on CVRP-100 with the fast split
-  // (tools/words_ab.py): ILP2/LA2 36.7, ILP2/LA1 36.2-36.7, ILP1/LA2 35.1,
-  // ILP1/LA1 34.0-35.5 G evals/s.  (Before the fast split, at ~2.5 more
-  // VALU per customer, ILP1/LA2 with two workgroups per CU led: 32.5 vs 31.6.)
+  // Auto: two candidates per lane.  When two workgroups' copies of the matrix
+  // fit the LDS (N <= 101) and the ring is at most 6 words deep: two 768-lane
+  // workgroups per CU (6 wavefronts per SIMD instead of 4), one word of
+  // gathers in flight, every wavefront striding over its own 128-candidate
+  // tiles -- provided the runtime confirms that two such workgroups are
+  // resident on a CU and the kernel has no scratch (words2_resident).
+  // Otherwise, and when option 5 forces a lookahead the shape is not built
+  // with: one 1024-lane workgroup per CU, two words in flight if N <= 101,
+  // else one.  Measured on CVRP-100, K = 8, 16 Mi tours, alternating
+  // repetitions (DESIGN.md §4.1 "residency", profiles/words2_shapes_*):
+  //   bench.py ms per step, 5 repetitions    tools/words_ab.py ms, 6 rounds
+  //   1024 x 1, LA2 (before)  0.4515-0.4572    0.4276-0.4408
+  //   1024 x 1, LA1                            0.4220-0.4331
+  //    768 x 2, LA1           0.4368-0.4440    0.4203-0.4292
+  //    768 x 2, LA1, waves    0.4347-0.4389    0.4143-0.4192
+  //   (a later session, before against waves: 0.4301-0.4370, 0.4191-0.4225)
+  //    768 x 2, LA2 (16 B scratch at R = 5)    0.4249-0.4354
+  //   1024 x 2, LA1 (8 wavefronts, 36 B scratch: 64 VGPRs do not hold
+  //                  the kernel)               0.4335-0.4425
+  // One candidate per lane stays behind (ILP1/LA1 0.4199-0.4539, LA2
+  // 0.4365-0.4414).  At N = 111 every shape runs the 1024-lane kernel.
   const bool two_wg = 2 * lds <= ctx->max_lds;
-  const int ilp = ctx->opt_words_ilp ? ctx->opt_words_ilp : 2;  // 1: A/B builds only
-  const int la = ctx->opt_words_lookahead ? ctx->opt_words_lookahead : (two_wg ? 2 : 1);
-  // ILP >= 2 needs > 64 VGPRs: one 1024-lane workgroup per CU; ILP1 fits two
-  const int per_cu = ilp >= 2 ? 1 : (two_wg ? 2 : 1);
-  const int64_t blocks = (w.C + 1024 * ilp - 1) / (1024 * ilp);
-  const int grid = (int)std::min<int64_t>(blocks, (int64_t)ctx->num_cus * per_cu);
-  auto go = [&](auto kern) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    kern<<<grid, 1024, lds, s>>>(w);
-  };
+  int ilp = ctx->opt_words_ilp ? ctx->opt_words_ilp : 2;  // 1, 3..6: A/B builds only
+  int shape = VRPMS_WORDS_SHAPE;
+#ifdef VRPMS_AB
+  if (ilp >= 3) {
+    shape = ilp - 3;
+    ilp = 2;
+  }
+#endif
   // every customer demand >= 1: the fit test rides in the add's carry
   const bool cy = w.f.carry && ctx->opt_split_mode != 3;
-  auto pick2 = [&](auto ilp_c, auto la_c, auto cy_c) {
-    constexpr int I = decltype(ilp_c)::value, L = decltype(la_c)::value;
-    constexpr bool C = decltype(cy_c)::value;
-    switch (R) {
-      case 4: go(eval_cvrp_words2<4, I, L, C>); break;
-      case 5: go(eval_cvrp_words2<5, I, L, C>); break;
-      case 6: go(eval_cvrp_words2<6, I, L, C>); break;
-      case 7: go(eval_cvrp_words2<7, I, L, C>); break;
-      default: go(eval_cvrp_words2<8, I, L, C>); break;
+  auto allow_lds = [&](Words2Kern kern) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  };
+  auto go = [&](Words2Kern kern, int tpb, int per_cu) {
+    const int64_t span = (int64_t)tpb * ilp;
+    const int64_t blocks = (w.C + span - 1) / span;
+    const int grid = (int)std::min<int64_t>(blocks, (int64_t)ctx->num_cus * per_cu);
+    kern<<<grid, tpb, lds, s>>>(w);
+  };
+  if (ilp == 2 && shape != 0 && two_wg) {
+    // a forced lookahead the shape was not built with, or a second workgroup
+    // that does not fit beside the first: the 1024-lane shape below
+    const int la = ctx->opt_words_lookahead ? ctx->opt_words_lookahead : VRPMS_WORDS_SHAPE_LA;
+    const int tpb = shape == 2 ? 1024 : 768;
+    const Words2Kern kern = words2_shape_kern(shape, la, R, cy);
+    if (kern) {
+      allow_lds(kern);
+      if (words2_resident(kern, tpb, lds) >= 2) {
+        go(kern, tpb, 2);
+        VRPMS_HIP(hipGetLastError());
+        return VRPMS_OK;
+      }
     }
-  };
-  auto pick = [&](auto ilp_c, auto la_c) {
-    if (cy) pick2(ilp_c, la_c, std::true_type{});
-    else pick2(ilp_c, la_c, std::false_type{});
-  };
-  using one = std::integral_constant<int, 1>;
-  using two = std::integral_constant<int, 2>;
-  const bool la2 = la == 2;
+  }
+  const bool la2 = (ctx->opt_words_lookahead ? ctx->opt_words_lookahead : (two_wg ? 2 : 1)) == 2;
 #ifdef VRPMS_AB
   // one candidate per lane: measured slower, built only for A/B runs
-  // (VRPMS_OPT_WORDS_ILP = 1 is refused by the shipped library)
+  // (VRPMS_OPT_WORDS_ILP = 1 is refused by the shipped library); it fits two
+  // workgroups per CU
   if (ilp == 1) {
-    la2 ? pick(one{}, two{}) : pick(one{}, one{});
+    const Words2Kern k1 = la2 ? words2_kern<1, 2, 1024, 4>(R, cy) : words2_kern<1, 1, 1024, 4>(R, cy);
+    allow_lds(k1);
+    go(k1, 1024, two_wg ? 2 : 1);
     VRPMS_HIP(hipGetLastError());
     return VRPMS_OK;
   }
 #endif
-  la2 ? pick(two{}, two{}) : pick(two{}, one{});
+  const Words2Kern k = la2 ? words2_kern<2, 2, 1024, 4>(R, cy) : words2_kern<2, 1, 1024, 4>(R, cy);
+  allow_lds(k);
+  go(k, 1024, 1);
   VRPMS_HIP(hipGetLastError());
   return VRPMS_OK;
 }
