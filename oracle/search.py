@@ -195,34 +195,48 @@ def ox1(A, B, lo, hi):
     return out
 
 
-def ga_generation(score: Scorer, pops, keys, seed: int, gen: int, pmut: int):
-    """vrpms_ga_generation for one generation; pops[island][i] tours."""
+def ga_children(score: Scorer, P, K, island: int, seed: int, gen: int, pmut: int):
+    """The children that island `island` (tours P, keys K) breeds in
+    generation `gen`, and their keys."""
     skey = spec.seed_key(seed)
+    pop = len(P)
+    children = []
+    for child in range(pop):
+        cid = island * pop + child
+        r = spec.philox4x32_10((gen & M32, gen >> 32, cid, 0), skey)
+        r2 = spec.philox4x32_10((gen & M32, gen >> 32, cid, 1), skey)
+        pa, pb = _tourney(K, pop, r[0], r[1]), _tourney(K, pop, r[2], r[3])
+        A, B = list(P[pa]), list(P[pb])
+        n = len(A)
+        if n < 2:
+            children.append(A)
+            continue
+        lo, hi = r2[0] % n, r2[1] % n
+        if lo > hi:
+            lo, hi = hi, lo
+        out = ox1(A, B, lo, hi)
+        if r2[2] < pmut:
+            m = spec.decode_move(r2[3], r[0] ^ r2[0], r[1] ^ r2[1], n)
+            out = spec.apply_move(out, *m)
+        children.append(out)
+    return children, [score(t) for t in children]
+
+
+def survivor_order(K, ck):
+    """(mu + lambda): the (key, index) pairs of the pop parents (index i) and
+    their children (index pop + i), ascending; the first pop survive."""
+    pop = len(K)
+    return sorted([(int(K[i]), i) for i in range(pop)] + [(int(ck[i]), pop + i) for i in range(pop)])
+
+
+def ga_generation(score: Scorer, pops, keys, seed: int, gen: int, pmut: int, order=survivor_order):
+    """vrpms_ga_generation for one generation; pops[island][i] tours.  `order`
+    is the survivor rule (the tests of the tests swap in wrong ones)."""
     new_pops, new_keys = [], []
     for island, (P, K) in enumerate(zip(pops, keys)):
         pop = len(P)
-        children = []
-        for child in range(pop):
-            cid = island * pop + child
-            r = spec.philox4x32_10((gen & M32, gen >> 32, cid, 0), skey)
-            r2 = spec.philox4x32_10((gen & M32, gen >> 32, cid, 1), skey)
-            pa, pb = _tourney(K, pop, r[0], r[1]), _tourney(K, pop, r[2], r[3])
-            A, B = list(P[pa]), list(P[pb])
-            n = len(A)
-            if n < 2:
-                children.append(A)
-                continue
-            lo, hi = r2[0] % n, r2[1] % n
-            if lo > hi:
-                lo, hi = hi, lo
-            out = ox1(A, B, lo, hi)
-            if r2[2] < pmut:
-                m = spec.decode_move(r2[3], r[0] ^ r2[0], r[1] ^ r2[1], n)
-                out = spec.apply_move(out, *m)
-            children.append(out)
-        ck = [score(t) for t in children]
-        merged = sorted([(int(K[i]), i) for i in range(pop)] + [(ck[i], pop + i) for i in range(pop)])
-        sel = merged[:pop]
+        children, ck = ga_children(score, P, K, island, seed, gen, pmut)
+        sel = order(K, ck)[:pop]
         new_pops.append([list(P[i]) if i < pop else children[i - pop] for _, i in sel])
         new_keys.append([k for k, _ in sel])
     return new_pops, new_keys

@@ -5,6 +5,7 @@ exchange; ACO's device-side colony-best tracking."""
 import numpy as np
 import pytest
 
+import selection_cases as sc
 from oracle import pool as opool
 from oracle import search
 from vrpms_amd import synth
@@ -140,3 +141,197 @@ def test_aco_colony_best_tracking_on_device(ctx):
     assert u64(bk) == ref_k and bt.cpu().tolist() == ref_t
     sc = search.Scorer(inst.durations, inst.demand, inst.capacities, inst.start_times, "cvrp")
     assert all(sc(t) == k for t, k in zip(ref_t, ref_k))
+
+
+# --- selection at its level, chunk, tie and size edges (tests/selection_cases.py;
+# --- the premises of every input are proved in test_selection_cases_cpu.py) ----
+
+def dev16(ctx, rows):
+    return torch_().tensor(np.asarray(rows), dtype=torch_().int16, device=ctx.dev)
+
+
+def vrpms_error():
+    from vrpms_amd._lib import VrpmsError
+    return VrpmsError
+
+
+@pytest.mark.parametrize("count,E", sc.ELITE_CASES)
+def test_pool_elites_levels_and_ties_match_oracle(ctx, count, E):
+    """topk over 1 to 7 levels of 2048 -> E (3 at (6145, 1024); 5 at (20481,
+    1024), where the result lands in the second buffer; 7 at (70000, 1000)), E
+    up to the limit 1024 and E == count, with a run of E + 9 equal keys across
+    the E-th place and across the first chunk boundary, beside 0 and 2^64 - 1."""
+    n = sc.POOL_N
+    keys = sc.pool_keys(count, E, seed=count + E)
+    rows = sc.pool_rows(count, n, count)
+    t, k = ctx.pool_elites(dev16(ctx, rows), i64(keys).to(ctx.dev), E)
+    rt, rk = opool.pool_elites(rows.tolist(), keys, E)
+    assert u64(k) == rk and t.cpu().tolist() == rt
+
+
+def test_pool_elites_outside_the_limits_raise(ctx):
+    rows = dev16(ctx, sc.pool_rows(3000, 5, 1))
+    keys = i64(sc.pool_keys(3000, 1024, seed=1)).to(ctx.dev)
+    with pytest.raises(vrpms_error()):
+        ctx.pool_elites(rows, keys, 1025)
+    with pytest.raises(vrpms_error()):
+        ctx.pool_elites(rows[:600], keys[:600], 601)
+
+
+@pytest.mark.parametrize("count,E", sc.WORST_CASES)
+def test_pool_inject_worst_multi_chunk_matches_oracle(ctx, count, E):
+    """INJECT_WORST over several chunks and levels (inverted keys): the E worst
+    by (key descending, index ascending), with a run of equal keys across the
+    E-th worst place and key 0 -- whose inverted value equals the pad key -- as
+    the one real entry of the last chunk."""
+    n = sc.POOL_N
+    keys = sc.pool_keys(count, E, seed=count + E, worst=True)
+    rows = sc.pool_rows(count, n, count)
+    mt, mk = sc.migrants(E, n, count)
+    dt, dk = dev16(ctx, rows), i64(keys).to(ctx.dev)
+    ctx.pool_inject(dt, dk, opool.INJECT_WORST, dev16(ctx, mt), i64(mk).to(ctx.dev))
+    rt, rk = opool.pool_inject(rows.tolist(), keys, opool.INJECT_WORST, mt.tolist(), mk)
+    assert u64(dk) == rk and dt.cpu().tolist() == rt
+
+
+@pytest.mark.parametrize("groups,P,E", sc.SORTED_CASES)
+def test_pool_inject_sorted_sizes_match_oracle(ctx, groups, P, E):
+    """INJECT_SORTED at P = 1, a power of two, P above the 1024 threads,
+    P = 4096 (LDS exactly 65536 bytes), more migrants than slots (the surplus
+    is dropped) and fewer migrants than islands; migrants tie with the rows
+    they are sorted among."""
+    rows, keys, mt, mk = sc.sorted_islands(groups, P, E, seed=P)
+    dt, dk = dev16(ctx, rows), i64(keys).to(ctx.dev)
+    ctx.pool_inject(dt, dk, opool.INJECT_SORTED, dev16(ctx, mt), i64(mk).to(ctx.dev), groups)
+    rt, rk = opool.pool_inject(rows.tolist(), keys, opool.INJECT_SORTED, mt.tolist(), mk, groups)
+    assert u64(dk) == rk and dt.cpu().tolist() == rt
+
+
+def test_pool_inject_sorted_outside_the_limits_raises(ctx):
+    rows, keys, mt, mk = sc.sorted_islands(1, 4097, 4, seed=3)
+    dt, dk = dev16(ctx, rows), i64(keys).to(ctx.dev)
+    m = (dev16(ctx, mt), i64(mk).to(ctx.dev))
+    with pytest.raises(vrpms_error()):          # M = 8192: too large for the LDS sort
+        ctx.pool_inject(dt, dk, opool.INJECT_SORTED, *m, 1)
+    with pytest.raises(vrpms_error()):          # 4097 = 17 * 241
+        ctx.pool_inject(dt, dk, opool.INJECT_SORTED, *m, 16)
+    assert u64(dk) == keys and dt.cpu().tolist() == rows.tolist()
+
+
+def test_pool_inject_better_more_migrants_than_rows_and_equal_keys(ctx):
+    """INJECT_BETTER with E > count (the migrants past the last row are
+    ignored), and a migrant whose key equals the row's does not replace it."""
+    n, count, E = 7, 5, 9
+    rows = sc.pool_rows(count, n, 1)
+    mt = sc.pool_rows(E, n, 2)
+    keys = [50, 0, 70, sc.M64, 90]
+    mk = [50, 0, 69, sc.M64, 91, 1, 2, 3, 4]       # equal, equal, better, equal, worse
+    dt, dk = dev16(ctx, rows), i64(keys).to(ctx.dev)
+    ctx.pool_inject(dt, dk, opool.INJECT_BETTER, dev16(ctx, mt), i64(mk).to(ctx.dev))
+    rt, rk = opool.pool_inject(rows.tolist(), keys, opool.INJECT_BETTER, mt.tolist(), mk)
+    assert rk == [50, 0, 69, sc.M64, 90] and rt[0] == rows[0].tolist() and rt[2] == mt[2].tolist()
+    assert u64(dk) == rk and dt.cpu().tolist() == rt
+
+
+def _pack(ctx, tours, keys, E, n):
+    """island_pack; with n == 0 through the C entry point, since an empty
+    tensor has no address to hand over (the rows are never read)."""
+    torch = torch_()
+    dk = i64(keys).to(ctx.dev)
+    if n:
+        return ctx.island_pack(dev16(ctx, tours), dk, E)
+    import ctypes
+
+    from vrpms_amd import _lib
+    hold = torch.zeros(8, dtype=torch.int16, device=ctx.dev)
+    msg = torch.empty(ctx.island_msg_bytes(E, 0), dtype=torch.uint8, device=ctx.dev)
+    p = _lib.Pool(hold.data_ptr(), dk.data_ptr(), len(keys), 0, 1)
+    _lib.check(ctx.lib.vrpms_island_pack(ctx.handle, ctypes.byref(p), E, msg.data_ptr(),
+                                         ctx.stream()))
+    torch.cuda.synchronize()
+    return msg
+
+
+def _merge(ctx, msgs, world, E, n):
+    torch = torch_()
+    if n:
+        t, k = ctx.island_merge(msgs, world, E, n)
+        return t.cpu().tolist(), u64(k)
+    from vrpms_amd import _lib
+    hold = torch.zeros(8, dtype=torch.int16, device=ctx.dev)
+    k = torch.empty(E, dtype=torch.int64, device=ctx.dev)
+    _lib.check(ctx.lib.vrpms_island_merge(ctx.handle, msgs.data_ptr(), world, E, 0,
+                                          hold.data_ptr(), k.data_ptr(), ctx.stream()))
+    assert (hold == 0).all()
+    return [[] for _ in range(E)], u64(k)
+
+
+@pytest.mark.parametrize("world,E,n,identical", sc.MERGE_CASES)
+def test_island_merge_levels_ties_and_empty_rows_match_oracle(ctx, world, E, n, identical):
+    """island_pack byte for byte and island_merge by (key, rank, position):
+    3 x 1024 and 9 x 1024 candidates (2 and 4 levels), identical messages from
+    every rank (the state after one exchange), and messages without rows."""
+    torch = torch_()
+    pools = sc.merge_pools(world, E, n, identical)
+    msgs = []
+    for tours, keys in pools:
+        m = _pack(ctx, tours, keys, E, n)
+        assert bytes(m.cpu().numpy().tobytes()) == opool.island_pack(tours.tolist(), keys, E, n)
+        msgs.append(m)
+    assert ctx.island_msg_bytes(E, n) == opool.msg_bytes(E, n) == msgs[0].numel()
+    allm = torch.cat(msgs)
+    rt, rk = opool.island_merge(bytes(allm.cpu().numpy().tobytes()), world, E, n)
+    assert _merge(ctx, allm, world, E, n) == (rt, rk)
+
+
+def test_local_exchange_all_modes_growing_scratch(ctx):
+    """island_exchange without a communicator == pack -> merge -> inject of
+    the oracle, in all three modes on one context with E, n and the pools
+    growing from call to call: the message sizes (none a multiple of 16 before
+    padding) put the work area at another offset each time, and the last call
+    needs more scratch than any pool test before it, so the scratch is
+    reallocated between calls (every time on a fresh context)."""
+    assert ctx.island_world() == 0
+    calls = [(opool.INJECT_WORST, 1, 70, 64, 3, 5), (opool.INJECT_BETTER, 1, 300, 4, 5, 7),
+             (opool.INJECT_SORTED, 4, 3000, 4 * 2048, 7, 9),
+             (opool.INJECT_WORST, 1, 5000, 90000, 1001, 11)]
+    for mode, groups, src_count, dst_count, E, n in calls:
+        assert (E * 8 + E * n * 2) % 16 and n % 2
+        if mode == opool.INJECT_SORTED:
+            dst_t, dst_k, _, _ = sc.sorted_islands(groups, dst_count // groups, E, seed=n, n=n)
+        else:
+            dst_t, dst_k = sc.pool_rows(dst_count, n, n), sc.pool_keys(max(dst_count, 12), E, n,
+                                                                         worst=True)[:dst_count]
+        src_t, src_k = sc.pool_rows(src_count, n, n + 1), sc.pool_keys(src_count, E, seed=n + 1)
+        s = (dev16(ctx, src_t), i64(src_k).to(ctx.dev))
+        d = (dev16(ctx, dst_t), i64(dst_k).to(ctx.dev))
+        ctx.island_exchange(s, d, mode, E, groups)
+        msg = opool.island_pack(src_t.tolist(), src_k, E, n)
+        mt, mk = opool.island_merge(msg, 1, E, n)
+        rt, rk = opool.pool_inject(dst_t.tolist(), dst_k, mode, mt, mk, groups)
+        assert u64(d[1]) == rk and d[0].cpu().tolist() == rt, (mode, E, n)
+        assert u64(s[1]) == src_k and s[0].cpu().tolist() == src_t.tolist()
+
+
+@pytest.mark.parametrize("n,n_sep,dt,count,ld", [
+    (1280, 0, "i16", 65, 1280),     # the last row length shuffled in LDS (64 rows x 2560 B = 160 KiB)
+    (1281, 0, "i16", 65, 1284),     # the first one shuffled in place in HBM
+    (1275, 6, "i16", 65, 1281),     # ... with separators
+    (250, 5, "u8", 64, 255), (250, 5, "u8", 65, 255),       # the last uint8 token
+])
+def test_random_tours_size_edges_match_oracle(ctx, n, n_sep, dt, count, ld):
+    torch = torch_()
+    dtype = torch.uint8 if dt == "u8" else torch.int16
+    T = ctx.random_tours(count, n, seed=2**41 + 9, stream_id=5, ld=ld, dtype=dtype, n_sep=n_sep)
+    T = T.cpu().numpy().astype(np.int64) & (0xFF if dt == "u8" else 0xFFFF)
+    L = n + n_sep
+    assert (64 * L * 2 <= sc.LDS_BYTES) == (L <= 1280)
+    for r in range(count):          # every row: one lane each, 64 to a block, one row in the second block
+        assert T[r, :L].tolist() == opool.philox_tour(n, 2**41 + 9, r, 5, n_sep), r
+    assert (T[:, L:] == 0).all()
+
+
+def test_random_tours_token_past_uint8_raises(ctx):
+    torch = torch_()
+    with pytest.raises(vrpms_error()):
+        ctx.random_tours(4, 250, seed=1, dtype=torch.uint8, n_sep=6)
