@@ -621,6 +621,62 @@ int vrpms_vrp_batch_ga(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_d
                        uint32_t pmut, uint64_t seed, uint16_t* d_tours, uint64_t* d_keys,
                        int32_t* d_durs, int8_t* d_veh, void* stream);
 
+/* Throughput mode of the VRP ant colony: R independent CVRP
+ * requests of one node count N >= 2 (n = N - 1 customers, node 0 the depot),
+ * one fleet size K, 1 <= K <= 64, one hour count H (1 or 24), one objective,
+ * one ant count A, 1 <= A <= 256, one iteration count I >= 1, one seed and one
+ * set of pheromone parameters (tau0, tau_min, tau_max, evap_shift,
+ * bsf_period), each with its own int32 [H][N][N] matrix (d_mats [R][H][N][N]),
+ * demands (d_demand [R][N], entry 0 ignored), capacities (d_cap [R][K], in
+ * vehicle order; they may differ or be 0) and start times (d_start [R][K],
+ * minutes).  ONE WORKGROUP AND ONE COLONY PER REQUEST: the request's whole
+ * instance is staged into LDS once -- the matrix as uint16 with wide = 0, as
+ * int32 with wide = 1 -- next to tau and eta (uint32 [N][N] each), A tours of
+ * n customers (no separators; the greedy split A5-A7 prices them) and the
+ * best-so-far tour.  tau starts at tau0 everywhere and eta is vrpms_aco_init's,
+ * floor(2^24 / (1 + D)^2) of the hour-0 slice; iteration it = 0..I-1 is
+ * vrpms_aco_iteration's on colony 0 of one: ant a, step s draws Philox block
+ * (it, 0, a, s), words 0 and 1; the roulette over w_j = (tau[cur][j] >> 8) *
+ * eta[cur][j] of the unvisited j picks the first j with w_j > 0 whose prefix
+ * sum exceeds (r1 << 32 | r0) % tot, or the first unvisited node when tot = 0;
+ * the least (key, ant) is the iteration best and replaces the best-so-far
+ * when strictly better; every cell becomes min(tau_max, max(tau_min, tau -
+ * (tau >> evap_shift))); then floor(2^30 / (1 + primary)), primary = bits
+ * 28..55 of the key, is added on the n + 1 edges depot -> tour -> depot of the
+ * iteration best, or of the best-so-far when bsf_period > 0 and (it + 1) %
+ * bsf_period == 0.  tau_max <= 2^30 and one deposit per cell per iteration
+ * keep tau + deposit at or below 2^31: it never wraps.  With the Python
+ * ACORunner's values (tau0 = 2^24, tau_min = 2^12, tau_max = 2^30, evap_shift =
+ * 3, bsf_period = 5) a request's row is the best-so-far of a single-colony
+ * vrpms_aco_init + I vrpms_aco_iteration calls on the same instance.  The
+ * counters carry no request row, so a request's answer depends on the
+ * request, A, I, the pheromone parameters, seed and objective alone: not on
+ * the launch it rode in nor on its row in it.  vrpms_vrp_batch_aco_lds gives
+ * the launch's dynamic-LDS bytes for (N, K, H, wide, A) (host only, no
+ * context); a launch that needs more than the device has is refused with that
+ * byte count in the message.  (N + K + 1) * max(D) + max(start) < 2^31 and cap
+ * + demand < 2^31 (A9) are the caller's promise.  Out, per request, the
+ * best-so-far after the last iteration: d_tours [R][n], d_keys [R] (its A8
+ * key), d_durs [R][K] (the K route durations of that tour, unclamped, 0 for an
+ * empty route) and d_veh [R][n] (the vehicle of every customer of the tour, -1
+ * for an unvisited one).  A request whose matrix has a negative entry, or with
+ * wide = 0 one above 65535, gets UINT64_MAX, an all-zero tour, zero durations
+ * and vehicles of -1, walks no ant and touches nothing else.  No instance and
+ * no workspace needed; asynchronous on `stream`.  R = 0 launches nothing.
+ * VRPMS_EINVAL, with nothing launched and nothing written, for a NULL ctx,
+ * R < 0, N outside 2..65535, K outside 1..64, H other than 1 or 24, an unknown
+ * wide or objective, A outside 1..256, I < 1, evap_shift outside 1..31,
+ * bsf_period < 0, anything but 0 < tau_min <= tau0 <= tau_max <= 2^30, a NULL
+ * buffer with R > 0, or an LDS need above the device's. */
+int vrpms_vrp_batch_aco_lds(int32_t N, int32_t K, int32_t H, int32_t wide, int32_t A,
+                            uint64_t* bytes);
+int vrpms_vrp_batch_aco(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_demand,
+                        const int32_t* d_cap, const int32_t* d_start, int32_t R, int32_t N,
+                        int32_t K, int32_t H, int32_t objective, int32_t wide, int32_t A, int32_t I,
+                        uint32_t tau0, uint32_t tau_min, uint32_t tau_max, int32_t evap_shift,
+                        int32_t bsf_period, uint64_t seed, uint16_t* d_tours, uint64_t* d_keys,
+                        int32_t* d_durs, int8_t* d_veh, void* stream);
+
 /* ------------------------------------------------------------------------
  * Populations and the island model.  A pool is a set of
  * tours with their A8 keys: SA chains, a GA population ([islands][pop],

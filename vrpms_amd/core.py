@@ -94,6 +94,17 @@ def vrp_batch_ga_lds(N: int, K: int, H: int, wide, P: int) -> int:
     return int(nbytes.value)
 
 
+def vrp_batch_aco_lds(N: int, K: int, H: int, wide, A: int) -> int:
+    """vrpms_vrp_batch_aco_lds: the dynamic-LDS bytes of a vrp_batch_aco launch
+    for N nodes, K vehicles, H hour slices (1 or 24), a uint16 (`wide` false)
+    or int32 (`wide` true) matrix and A ants.  Host only: needs the library,
+    no GPU."""
+    nbytes = ctypes.c_uint64()
+    check(_lib.load().vrpms_vrp_batch_aco_lds(int(N), int(K), int(H), int(wide), int(A),
+                                              ctypes.byref(nbytes)))
+    return int(nbytes.value)
+
+
 def tdp_words(start: int, horizon: int) -> int:
     """Hour words of one A16 row: the words from the start's hour to the one
     of start + horizon."""
@@ -731,6 +742,56 @@ class Context:
                                           int(seed) & (2**64 - 1), tours.data_ptr(),
                                           keys.data_ptr(), durs.data_ptr(), veh.data_ptr(),
                                           self.stream()))
+        return tours, keys, durs, veh
+
+    def vrp_batch_aco(self, mats, demand, caps, starts, objective: int, ants: int, iters: int,
+                      seed: int, wide=None, tau0: int = 1 << 24, tau_min: int = 1 << 12,
+                      tau_max: int = 1 << 30, evap_shift: int = 3, bsf_period: int = 5):
+        """An ant colony per request, one workgroup per request, one launch
+        for all (spec A24; all requests of one N, K, H and objective): mats
+        int32 [R][H][N][N] (H = 1 or 24; [R][N][N] is taken as H = 1), demand
+        int32 [R][N] (entry 0 ignored), caps and starts int32 [R][K] on the
+        device -> (tours int16 [R][n], keys int64 [R], durs int32 [R][K], veh
+        int8 [R][n]) with n = N - 1: per request the best-so-far tour of one
+        colony of `ants` (1..256) ants after `iters` (>= 1) iterations, its A8
+        key, its K route durations (unclamped, 0 for an empty route) and the
+        vehicle of every customer of the tour (-1 unvisited).  The pheromone
+        parameters default to ACORunner's, and with them the row is the
+        best-so-far of ACORunner(ctx, n, colonies=1, ants=ants, seed=seed)
+        stepped `iters` times on the same instance.  A request's row depends
+        on the request, `ants`, `iters`, the pheromone parameters, `seed` and
+        `objective` alone, not on the batch.  `wide`: False stages the
+        matrices as uint16 (a request with an entry above 65535 then gets an
+        all-ones key, a zero tour, zero durations and veh = -1), True as
+        int32; None -- the default -- asks the device for the batch's largest
+        entry, which synchronises.  The A9 guard and non-negative demands and
+        capacities are the caller's promise.  Asynchronous on the current
+        stream."""
+        torch = _torch()
+        mats = self._batch_mats(torch, mats, 4)
+        R, H, N, _ = mats.shape
+        self._batch_rows(torch, demand, caps, R, N)
+        K = caps.shape[1]
+        if starts.device != self.dev or starts.shape != caps.shape or starts.dtype != torch.int32 \
+                or not starts.is_contiguous():
+            raise ValueError(f"starts must be a contiguous int32 [R][K] tensor on {self.dev}")
+        for name, v in (("tau0", tau0), ("tau_min", tau_min), ("tau_max", tau_max)):
+            if not 0 <= int(v) < 2**32:
+                raise ValueError(f"{name} must be a uint32")
+        if wide is None:
+            wide = bool(R) and int(mats.max().item()) > 65535
+        n = N - 1
+        tours = torch.empty((R, max(n, 1)), dtype=torch.int16, device=self.dev)
+        keys = torch.empty(R, dtype=torch.int64, device=self.dev)
+        durs = torch.empty((R, max(K, 1)), dtype=torch.int32, device=self.dev)
+        veh = torch.empty((R, max(n, 1)), dtype=torch.int8, device=self.dev)
+        check(self.lib.vrpms_vrp_batch_aco(self._ctx, mats.data_ptr(), demand.data_ptr(),
+                                           caps.data_ptr(), starts.data_ptr(), R, N, K, H,
+                                           int(objective), int(bool(wide)), int(ants), int(iters),
+                                           int(tau0), int(tau_min), int(tau_max), int(evap_shift),
+                                           int(bsf_period), int(seed) & (2**64 - 1),
+                                           tours.data_ptr(), keys.data_ptr(), durs.data_ptr(),
+                                           veh.data_ptr(), self.stream()))
         return tours, keys, durs, veh
 
     def set_batch_dp_team(self, T: int):

@@ -25,6 +25,7 @@
 #include <climits>
 #include <vector>
 
+#include "aco.hpp"
 #include "common.hpp"
 #include "ctx.hpp"
 #include "split.hpp"
@@ -1849,58 +1850,17 @@ __global__ __launch_bounds__(1024) void aco_construct_lds_kernel(AcoArgs a, int 
     for (int q = n + lane; q < 256; q += 64) tb[q] = 0;
   }
   uint16_t* out = a.tours + gid * n;
-  // Lane l owns the CH consecutive nodes CH l .. CH l + CH - 1, so the
-  // roulette's prefix sums in node order are the lanes' prefix (ONE 64-bit
-  // wave scan of each lane's sum, not one per 64-node chunk) followed by the
-  // lane's own running sum: the first lane whose inclusive prefix passes r
-  // holds the pick, the first of its nodes whose running sum passes r.  (The
-  // first node j with prefix P_j > r has w_j > 0, the register path's rule.)
-  uint32_t vm = lane == 0 ? 1u : 0u;  // bit c: node CH lane + c visited (or past N); depot
-#pragma unroll
-  for (int c = 0; c < CH; ++c)
-    if (CH * lane + c >= N) vm |= 1u << c;
-  constexpr uint32_t kAll = (1u << CH) - 1u;
+  // lane l owns the CH consecutive nodes CH l .. CH l + CH - 1 (aco.hpp)
+  uint32_t vm = aco_owned_start<CH>(lane, N);
   uint32_t cur = 0;
-  uint32_t rx = 0, ry = 0;  // lane l: Philox block (iter, gid, s0 + l), words x / y
+  AcoDraws draws;  // lane l: Philox block (iter, gid, s0 + l), words x / y
   for (int s = 0; s < n; ++s) {
-    if ((s & 63) == 0) {  // the next 64 steps' draws, one per lane, in VALU
-      const u32x4 r = philox((uint32_t)a.iter, (uint32_t)(a.iter >> 32), (uint32_t)gid,
-                             (uint32_t)(s + lane), a.seed_lo, a.seed_hi);
-      rx = r.x;
-      ry = r.y;
-    }
-    const uint32_t r_x = (uint32_t)__builtin_amdgcn_readlane((int)rx, s & 63);
-    const uint32_t r_y = (uint32_t)__builtin_amdgcn_readlane((int)ry, s & 63);
+    draws.step(a.iter, (uint32_t)gid, s, lane, a.seed_lo, a.seed_hi);
     const uint64_t* Wr = Wt + cur * (uint32_t)NS + CH * lane;
-    uint64_t w[CH], sum = 0;
+    uint64_t w[CH];
 #pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      w[c] = !((vm >> c) & 1u) ? Wr[c] : 0ull;
-      sum += w[c];
-    }
-    uint64_t incl = sum;
-    const uint64_t tot = wave_scan_add_u64(incl);
-    uint32_t mine, L;  // this lane's candidate node, the lane that holds the pick
-    if (tot != 0) {
-      const uint64_t rr = umod64(((uint64_t)r_y << 32) | r_x, tot);
-      L = (uint32_t)__ffsll((long long)__ballot(incl > rr)) - 1u;  // exists: the last lane's is tot
-      uint64_t run = incl - sum;
-      uint32_t cc = CH - 1;
-      bool found = false;
-#pragma unroll
-      for (int c = 0; c < CH; ++c) {
-        run += w[c];
-        if (!found && run > rr) {
-          cc = (uint32_t)c;
-          found = true;
-        }
-      }
-      mine = CH * (uint32_t)lane + cc;
-    } else {  // every free weight is 0: the first free node
-      L = (uint32_t)__ffsll((long long)__ballot(vm != kAll)) - 1u;
-      mine = CH * (uint32_t)lane + (uint32_t)__builtin_ctz((~vm & kAll) | (1u << CH));
-    }
-    const uint32_t pick = (uint32_t)__builtin_amdgcn_readlane((int)mine, (int)L);
+    for (int c = 0; c < CH; ++c) w[c] = !((vm >> c) & 1u) ? Wr[c] : 0ull;
+    const uint32_t pick = aco_roulette_owned<CH>(w, vm, draws.at(s), lane);
     if (lane == 0) {
       out[s] = (uint16_t)pick;
       if constexpr (WORDS) tb[s] = (uint8_t)pick;
@@ -1989,11 +1949,10 @@ __global__ __launch_bounds__(1024) void aco_update_fused_kernel(AcoUpdateArgs a,
     for (int u = 0; u < 8; ++u) v[u] = base + u * B < NN ? T[base + u * B] : 0u;
 #pragma unroll
     for (int u = 0; u < 8; ++u)
-      if (base + u * B < NN) T[base + u * B] = min(a.tau_max, max(a.tau_min, v[u] - (v[u] >> a.evap_shift)));
+      if (base + u * B < NN) T[base + u * B] = aco_evaporated(v[u], a.evap_shift, a.tau_min, a.tau_max);
   }
   __syncthreads();
-  const uint32_t primary = (uint32_t)((k >> 28) & ((1u << 28) - 1u));
-  const uint32_t dep = (uint32_t)((1u << 30) / (1ull + primary));
+  const uint32_t dep = aco_deposit_of(k);
   for (int q = threadIdx.x; q <= a.n; q += blockDim.x) {
     const uint32_t from = q == 0 ? 0u : t[q - 1];
     const uint32_t to = q == a.n ? 0u : t[q];
@@ -2005,8 +1964,7 @@ __global__ void aco_evaporate_kernel(AcoUpdateArgs a) {
   const int64_t total = (int64_t)a.colonies * a.N * a.N;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
        i += (int64_t)gridDim.x * blockDim.x) {
-    const uint32_t t = a.tau[i];
-    a.tau[i] = min(a.tau_max, max(a.tau_min, t - (t >> a.evap_shift)));
+    a.tau[i] = aco_evaporated(a.tau[i], a.evap_shift, a.tau_min, a.tau_max);
   }
 }
 
@@ -2019,8 +1977,7 @@ __global__ void aco_deposit_kernel(AcoUpdateArgs a, const uint16_t* best_tours,
   const bool bsf = a.bsf && best_tours && best_keys;
   const uint64_t key = bsf ? best_keys[colony] : a.ib[2 * colony];
   const int ant = (int)a.ib[2 * colony + 1];
-  const uint32_t primary = (uint32_t)((key >> 28) & ((1u << 28) - 1u));
-  const uint32_t dep = (uint32_t)((1u << 30) / (1ull + primary));
+  const uint32_t dep = aco_deposit_of(key);
   const uint16_t* t = bsf ? best_tours + (int64_t)colony * a.n
                           : a.tours + ((int64_t)colony * a.ants + ant) * a.n;
   uint32_t* T = a.tau + (int64_t)colony * a.N * a.N;
@@ -2809,8 +2766,7 @@ __global__ void aco_init_kernel(const int32_t* __restrict__ D, int N, int coloni
        i += (int64_t)gridDim.x * blockDim.x) {
     tau[i] = tau0;
     if (i < NN) {
-      const uint64_t d1 = 1ull + (uint64_t)(uint32_t)D[i];  // static slice (hour 0)
-      eta[i] = (uint32_t)((1ull << 24) / (d1 * d1));
+      eta[i] = aco_eta_cell((uint32_t)D[i]);  // static slice (hour 0)
     }
   }
 }

@@ -543,6 +543,46 @@ class VrpGaBatcher(VrpSaBatcher):
         return tours, list(zip(veh, durs))
 
 
+class VrpAcoBatcher(VrpSaBatcher):
+    """Coalesces concurrent /api/vrp/aco and /solve/vrp/aco requests into one
+    `vrp_batch_aco` launch per (node count, fleet size, hour count, cell
+    width, objective) (spec A24: one workgroup per request, its whole
+    instance and one colony in LDS).  Every launch runs `ants` ants for
+    `iters` iterations, the batcher's own (the endpoint has no knob for
+    either).  The queue, the window, the device round-robin and the error
+    fan-out are TspBatcher's.  A batched answer does not depend on the batch:
+    it is solver.solve_vrp_aco_batch([request], ants=, iters=, seed=the
+    app's, objective=)'s.  It is NOT the unbatched endpoint's answer, which
+    runs 4 colonies."""
+
+    def __init__(self, app, window_s: float = 0.005, iters: int = 100, ants: int = 64,
+                 max_batch: int = 16384, launch=None):
+        from . import solver
+        if not 1 <= int(ants) <= solver.BATCH_ACO_MAX_ANTS:
+            raise ValueError(f"ants must be in 1..{solver.BATCH_ACO_MAX_ANTS} ({ants} given)")
+        if not 1 <= int(iters) <= solver.BATCH_ACO_MAX_ITERATIONS:
+            raise ValueError(f"iters must be in 1..{solver.BATCH_ACO_MAX_ITERATIONS} "
+                             f"({iters} given)")
+        self.ants, self.iters = int(ants), int(iters)
+        super().__init__(app, window_s, steps=0, max_batch=max_batch, launch=launch)
+
+    def accepts(self, ci) -> bool:
+        """Requests inside A24's domain (LDS at the batcher's ants) that pass
+        the int32 guards vrpms_set_instance applies on the unbatched path;
+        anything else takes the unbatched path."""
+        from . import solver
+        return solver.batch_aco_fits(ci, self.ants, self.iters) and \
+            solver.batch_guard_message(ci) is None
+
+    def _gpu_launch(self, key, cis, device=None):
+        from . import solver
+        dev = self.devices[0] if device is None else device
+        with self.app.locks[dev]:
+            tours, veh, durs = solver.batch_aco_launch(solver.context(dev), cis, self.ants,
+                                                       self.iters, self.app.seed, key[-1])
+        return tours, list(zip(veh, durs))
+
+
 # ---------------------------------------------------------------------------
 # the endpoint logic
 # ---------------------------------------------------------------------------
@@ -567,7 +607,9 @@ class App:
                  batch_exact_vrp_launch=None, batch_exact_tdp_launch=None,
                  batch_exact_tdsp: bool = False, batch_exact_tdsp_launch=None,
                  batch_vrp_sa: bool = False, batch_vrp_sa_launch=None,
-                 batch_vrp_ga: bool = False, batch_vrp_ga_launch=None):
+                 batch_vrp_ga: bool = False, batch_vrp_ga_launch=None,
+                 batch_vrp_aco: bool = False, batch_vrp_aco_launch=None,
+                 batch_aco_iterations: int = 100, batch_aco_ants: int = 64):
         self.store = store
         self.devices = list(devices) if devices else [device]
         self.device = self.devices[0]
@@ -607,6 +649,11 @@ class App:
         # default: the batched answer is not the unbatched endpoint's)
         self.vrp_ga_batcher = VrpGaBatcher(self, batch_window_s, launch=batch_vrp_ga_launch) \
             if batch_vrp_ga else None
+        # small-fleet VRP ACO requests share vrp_batch_aco launches (off by
+        # default: the batched answer is not the unbatched endpoint's)
+        self.vrp_aco_batcher = VrpAcoBatcher(self, batch_window_s, batch_aco_iterations,
+                                             batch_aco_ants, launch=batch_vrp_aco_launch) \
+            if batch_vrp_aco else None
 
     def _scheduled(self, problem, algorithm, params, knobs, locations, durations):
         """Run the solve on a device: all of them (in order, as an island
@@ -682,9 +729,21 @@ class App:
                                 params["ignored_customers"], params["completed_customers"])
         return (ci, pop, gens) if self.vrp_ga_batcher.accepts(ci, pop, gens) else None
 
+    def _batched_vrp_aco(self, problem, algorithm, params, knobs, locations, durations):
+        """The compact instance when this request rides the VRP ACO batcher,
+        else None: the flag is on, the route is vrp / aco, the request names
+        no inline knob of its own and it is inside the batcher's domain."""
+        if self.vrp_aco_batcher is None or (problem, algorithm) != ("vrp", "aco") or \
+                knobs.get("inline"):
+            return None
+        from . import solver
+        ci = solver.compact_vrp(durations, locations, params["capacities"], params["start_times"],
+                                params["ignored_customers"], params["completed_customers"])
+        return ci if self.vrp_aco_batcher.accepts(ci) else None
+
     def _batched_vrp(self, problem, algorithm, params, knobs, locations, durations):
-        """A thunk that solves this request on the VRP SA or GA batcher, else
-        None."""
+        """A thunk that solves this request on the VRP SA, GA or ACO batcher,
+        else None."""
         objective = knobs.get("objective", "sum")
         vci = self._batched_vrp_sa(problem, algorithm, params, knobs, locations, durations)
         if vci is not None:
@@ -692,6 +751,9 @@ class App:
         gci = self._batched_vrp_ga(problem, algorithm, params, knobs, locations, durations)
         if gci is not None:
             return lambda: self.vrp_ga_batcher.solve(gci[0], objective, gci[1], gci[2])
+        aci = self._batched_vrp_aco(problem, algorithm, params, knobs, locations, durations)
+        if aci is not None:
+            return lambda: self.vrp_aco_batcher.solve(aci, objective)
         return None
 
     def _exact_batcher(self, problem, algorithm):
@@ -964,7 +1026,18 @@ def serve(app: App, host: str = "127.0.0.1", port: int = 8000) -> ThreadingHTTPS
     return ThreadingHTTPServer((host, port), router(app))
 
 
+def _int_in(lo: int, hi: int):
+    """An argparse type: an integer in lo..hi (anything else is an error, not a clamp)."""
+    def parse(text):
+        v = int(text)
+        if not lo <= v <= hi:
+            raise argparse.ArgumentTypeError(f"must be in {lo}..{hi} ({v} given)")
+        return v
+    return parse
+
+
 def main(argv=None):
+    from . import solver
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=8000)
@@ -1008,6 +1081,18 @@ def main(argv=None):
                          "population per request, so the answer differs from the unbatched "
                          "endpoint's; it depends on the request alone, not on the batch it "
                          "rode in")
+    ap.add_argument("--batch-vrp-aco", action="store_true",
+                    help="coalesce concurrent small-fleet VRP ACO requests (/api/vrp/aco and "
+                         "/solve/vrp/aco, static or hour-indexed matrix, 1..64 vehicles, an "
+                         "instance and colony that fit the LDS) into vrp_batch_aco launches of "
+                         "--batch-aco-ants ants and --batch-aco-iterations iterations: one colony "
+                         "per request, so the answer differs from the unbatched endpoint's; it "
+                         "depends on the request alone, not on the batch it rode in")
+    ap.add_argument("--batch-aco-iterations", type=_int_in(1, solver.BATCH_ACO_MAX_ITERATIONS), default=100,
+                    help="iterations of a vrp_batch_aco launch, 1..1000 "
+                         "(solver.BATCH_ACO_MAX_ITERATIONS)")
+    ap.add_argument("--batch-aco-ants", type=_int_in(1, solver.BATCH_ACO_MAX_ANTS), default=64,
+                    help="ants of a vrp_batch_aco launch, 1..256 (solver.BATCH_ACO_MAX_ANTS)")
     ap.add_argument("--batch-window-ms", type=float, default=5.0)
     ap.add_argument("--batch-steps", type=int, default=2000)
     ap.add_argument("--workers", type=int, default=0,
@@ -1047,7 +1132,8 @@ def main(argv=None):
               batch_tsp=args.batch_tsp, batch_window_s=args.batch_window_ms * 1e-3,
               batch_steps=args.batch_steps, devices=devices, batch_exact=args.batch_exact,
               batch_exact_tdsp=args.batch_exact_tdsp, batch_vrp_sa=args.batch_vrp_sa,
-              batch_vrp_ga=args.batch_vrp_ga)
+              batch_vrp_ga=args.batch_vrp_ga, batch_vrp_aco=args.batch_vrp_aco,
+              batch_aco_iterations=args.batch_aco_iterations, batch_aco_ants=args.batch_aco_ants)
     srv = serve(app, args.host, args.port)
     print(f"vrpms_amd service on http://{args.host}:{args.port}/api", flush=True)
     try:

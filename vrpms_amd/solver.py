@@ -125,6 +125,15 @@ BATCH_SA_LDS_BYTES = 160 * 1024
 BATCH_GA_MAX_POP = 256
 BATCH_GA_MAX_GENERATIONS = 2000
 BATCH_GA_LDS_BYTES = BATCH_SA_LDS_BYTES
+# batched VRP ACO (A24): next to the instance, tau and eta (4 bytes a cell
+# each), `ants` tours and the best-so-far's have to fit the same budget
+# (vrpms_vrp_batch_aco_lds gives the bytes for (N, K, H, wide, ants)); DESIGN.md
+# §4.3o has the largest N per (H, wide, ants).  A launch has no time limit, so
+# a request of more iterations than BATCH_ACO_MAX_ITERATIONS -- ten times the
+# endpoint's default of 100 -- takes the unbatched path, which has one
+BATCH_ACO_MAX_ANTS = 256
+BATCH_ACO_MAX_ITERATIONS = 1000
+BATCH_ACO_LDS_BYTES = BATCH_SA_LDS_BYTES
 # SA on tours of more than SA_WINDOW_MIN_N customers samples A11 windowed
 # moves (second position within SA_WINDOW of the first)
 SA_WINDOW, SA_WINDOW_MIN_N = 32, 150
@@ -1239,6 +1248,120 @@ def solve_vrp_ga_batch(requests, *, pop: int = 256, gens: int = 400, pmut: float
         ctx = context(device)
         for xs in groups.values():
             rows = batch_ga_launch(ctx, [cis[x] for x in xs], pop, gens, pmut, seed, objective)
+            for x, tour, veh, durs in zip(xs, *rows):
+                out[x] = sa_result(cis[x], tour, veh, durs, with_unvisited)
+    return out
+
+
+# ---------------------------------------------------------------------------
+# batched VRP ACO (A24): small-fleet requests share launches
+# ---------------------------------------------------------------------------
+def batch_aco_key(ci: CompactInstance, ants: int, iters: int):
+    """What the instances of one vrp_batch_aco launch share (next to the
+    objective and the seed): (N, K, H, wide, ants, iters)."""
+    return batch_sa_key(ci) + (int(ants), int(iters))
+
+
+def batch_aco_fits(ci: CompactInstance, ants: int, iters: int) -> bool:
+    """A24's domain: a CVRP of at least one customer, 1..64 vehicles, a static
+    or 24-slice matrix, 1 <= ants <= BATCH_ACO_MAX_ANTS, 1 <= iters <=
+    BATCH_ACO_MAX_ITERATIONS, and an instance that fits BATCH_ACO_LDS_BYTES
+    together with its pheromone tables and ants + 1 tours
+    (vrpms_vrp_batch_aco_lds; uint16 cells unless an entry is above 65535).
+    Needs the library, no GPU."""
+    from .core import vrp_batch_aco_lds
+    if ci.problem != CVRP or ci.n < 1 or ci.N > 65535:
+        return False
+    if not 1 <= int(ants) <= BATCH_ACO_MAX_ANTS or not 1 <= int(iters) <= BATCH_ACO_MAX_ITERATIONS:
+        return False
+    N, K, H, wide = batch_sa_key(ci)
+    if not 1 <= K <= BATCH_SA_MAX_VEHICLES or H not in (1, 24):
+        return False
+    return vrp_batch_aco_lds(N, K, H, wide, int(ants)) <= BATCH_ACO_LDS_BYTES
+
+
+def batch_aco_launch(ctx: Context, cis, ants: int, iters: int, seed: int, objective: str = "sum"):
+    """One upload and one vrp_batch_aco launch for compact instances of one
+    batch_aco_key (each passed batch_guard_message and batch_aco_fits), with
+    ACORunner's pheromone parameters -> (tours, veh, durs): per instance the n
+    customers of the best-so-far tour, each one's vehicle (-1 unvisited) and
+    the K route durations."""
+    import torch
+    mats, demand, caps = _stage(ctx, cis, hours=True)
+    starts = torch.from_numpy(np.array([ci.start_times for ci in cis], dtype=np.int32)).to(ctx.dev)
+    tours, keys, durs, veh = ctx.vrp_batch_aco(mats, demand, caps, starts,
+                                               OBJ_MAX if objective == "max" else OBJ_SUM,
+                                               int(ants), int(iters), seed,
+                                               wide=batch_sa_wide(cis[0]))
+    if (keys == -1).any().item():
+        raise RuntimeError("vrp_batch_aco: a request was outside the launch's contract")
+    return tours.cpu().tolist(), veh.cpu().tolist(), durs.cpu().tolist()
+
+
+def solve_vrp_aco_batch(requests, *, ants: int = 64, iters: int = 100, seed: int = 0,
+                        objective: str = "sum", with_unvisited: bool = False,
+                        device: int = 0) -> list:
+    """An ant colony for many small-fleet VRP requests, the requests that fit
+    sharing launches (spec A24): one workgroup per request, its whole
+    instance, one colony's pheromone and `ants` separator-free tours in LDS,
+    `iters` iterations of roulette construction, evaporation and an
+    iteration-best (every fifth: best-so-far) deposit.  `requests`:
+    solve_vrp_batch's (durations, locations, capacities, start_times[,
+    ignored_customers, completed_customers]) tuples, or dicts with those keys
+    -> one solve_vrp slot dict per request.
+
+    This is NOT solve_vrp("aco")'s answer: one colony here (the trajectory of
+    ACORunner(colonies=1, ants=ants)), 4 colonies there.  It is deterministic
+    per request: the dict depends on the request, `ants`, `iters`, `seed` and
+    `objective` alone, not on the other requests of the call or on its place
+    among them.
+
+    Every request is compacted and passed through batch_guard_message on the
+    host before any device is touched; a bad one raises ValueError("request
+    {x}: ...").  With no local GPU each request goes to solve_vrp("aco") on
+    the GPU box.  Requests inside the domain (batch_aco_fits) are grouped by
+    (N, K, H, wide), one upload and one vrp_batch_aco launch per group, and
+    their dicts are built on the host from the tour, its vehicles and the
+    route durations; no customer has solve_vrp's trivial answer; a request
+    outside the domain (also every request when `ants` is above
+    BATCH_ACO_MAX_ANTS or `iters` above BATCH_ACO_MAX_ITERATIONS) takes
+    solve_vrp("aco", seed=seed, objective=objective, iteration_count=iters,
+    ants=ants), one by one."""
+    if objective not in ("sum", "max"):
+        raise ValueError("objective must be 'sum' or 'max'")
+    if int(ants) < 1:
+        raise ValueError("ants must be at least 1")
+    if int(iters) < 1:
+        raise ValueError("iters must be at least 1")
+    reqs, cis = [], []
+    for x, r in enumerate(requests):
+        try:
+            r, _ = _sp_request(r)
+            ci = compact_vrp(*r)
+            msg = batch_guard_message(ci)
+            if msg is not None:
+                raise ValueError(msg)
+        except ValueError as e:
+            raise ValueError(f"request {x}: {e}") from None
+        reqs.append(r)
+        cis.append(ci)
+    shared = dict(seed=seed, objective=objective, with_unvisited=with_unvisited,
+                  iteration_count=int(iters), ants=int(ants))
+    if _remote() is not None:      # no local GPU: the GPU box answers each request
+        return [solve_vrp("aco", *r, **shared) for r in reqs]
+    out = [None] * len(cis)
+    groups: dict = {}
+    for x, ci in enumerate(cis):
+        if ci.n == 0:
+            out[x] = sa_result(ci, [], [], [0] * len(ci.capacities), with_unvisited)
+        elif batch_aco_fits(ci, ants, iters):
+            groups.setdefault(batch_aco_key(ci, ants, iters), []).append(x)
+        else:
+            out[x] = solve_vrp("aco", *reqs[x], device=device, **shared)
+    if groups:
+        ctx = context(device)
+        for xs in groups.values():
+            rows = batch_aco_launch(ctx, [cis[x] for x in xs], ants, iters, seed, objective)
             for x, tour, veh, durs in zip(xs, *rows):
                 out[x] = sa_result(cis[x], tour, veh, durs, with_unvisited)
     return out
