@@ -105,6 +105,17 @@ def vrp_batch_aco_lds(N: int, K: int, H: int, wide, A: int) -> int:
     return int(nbytes.value)
 
 
+def vrp_batch_ls_lds(N: int, K: int, H: int, wide) -> int:
+    """vrpms_vrp_batch_ls_lds: the dynamic-LDS bytes of a vrp_batch_ls launch
+    for N nodes, K vehicles, H hour slices (1 or 24) and a uint16 (`wide`
+    false) or int32 (`wide` true) matrix; never more than vrp_batch_sa_lds of
+    the same shape.  Host only: needs the library, no GPU."""
+    nbytes = ctypes.c_uint64()
+    check(_lib.load().vrpms_vrp_batch_ls_lds(int(N), int(K), int(H), int(wide),
+                                             ctypes.byref(nbytes)))
+    return int(nbytes.value)
+
+
 def tdp_words(start: int, horizon: int) -> int:
     """Hour words of one A16 row: the words from the start's hour to the one
     of start + horizon."""
@@ -793,6 +804,52 @@ class Context:
                                            tours.data_ptr(), keys.data_ptr(), durs.data_ptr(),
                                            veh.data_ptr(), self.stream()))
         return tours, keys, durs, veh
+
+    def vrp_batch_ls(self, mats, demand, caps, starts, objective: int, nstarts: int, rounds: int,
+                     seed: int, wide=None):
+        """A multi-start local search per request, one workgroup per request,
+        one launch for all (spec A25; all requests of one N, K, H and
+        objective): mats int32 [R][H][N][N] (H = 1 or 24; [R][N][N] is taken as
+        H = 1), demand int32 [R][N] (entry 0 ignored), caps and starts int32
+        [R][K] on the device -> (tours int16 [R][n], keys int64 [R], durs
+        int32 [R][K], veh int8 [R][n], info int32 [R][2]) with n = N - 1: per
+        request the least (key, start) end tour of `nstarts` (1..65535)
+        steepest descents over swap, 2-opt and relocate from vrp_batch_ga's
+        random members 0..nstarts-1, each stopped at a local optimum or after
+        `rounds` (>= 0) applied moves; its A8 key, its K route durations
+        (unclamped, 0 for an empty route), the vehicle of every gene (-1
+        unvisited), and info = (the winning start, the number of descents the
+        round cap stopped unproven).  A request's row depends on the request,
+        `nstarts`, `rounds`, `seed` and `objective` alone, not on the batch.
+        `wide`: False stages the matrices as uint16 (a request with an entry
+        above 65535 then gets an all-ones key, a zero tour, zero durations,
+        veh = -1 and info = (-1, 0)), True as int32; None -- the default --
+        asks the device for the batch's largest entry, which synchronises.
+        The A9 guard and non-negative demands and capacities are the caller's
+        promise.  Asynchronous on the current stream."""
+        torch = _torch()
+        mats = self._batch_mats(torch, mats, 4)
+        R, H, N, _ = mats.shape
+        self._batch_rows(torch, demand, caps, R, N)
+        K = caps.shape[1]
+        if starts.device != self.dev or starts.shape != caps.shape or starts.dtype != torch.int32 \
+                or not starts.is_contiguous():
+            raise ValueError(f"starts must be a contiguous int32 [R][K] tensor on {self.dev}")
+        if wide is None:
+            wide = bool(R) and int(mats.max().item()) > 65535
+        n = N - 1
+        tours = torch.empty((R, max(n, 1)), dtype=torch.int16, device=self.dev)
+        keys = torch.empty(R, dtype=torch.int64, device=self.dev)
+        durs = torch.empty((R, max(K, 1)), dtype=torch.int32, device=self.dev)
+        veh = torch.empty((R, max(n, 1)), dtype=torch.int8, device=self.dev)
+        info = torch.empty((R, 2), dtype=torch.int32, device=self.dev)
+        check(self.lib.vrpms_vrp_batch_ls(self._ctx, mats.data_ptr(), demand.data_ptr(),
+                                          caps.data_ptr(), starts.data_ptr(), R, N, K, H,
+                                          int(objective), int(bool(wide)), int(nstarts), int(rounds),
+                                          int(seed) & (2**64 - 1), tours.data_ptr(),
+                                          keys.data_ptr(), durs.data_ptr(), veh.data_ptr(),
+                                          info.data_ptr(), self.stream()))
+        return tours, keys, durs, veh, info
 
     def set_batch_dp_team(self, T: int):
         """Threads per request of tsp_batch_dp: 0 = auto (the n -> T table),

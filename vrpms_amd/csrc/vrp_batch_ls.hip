@@ -1,0 +1,377 @@
+// Throughput mode of a multi-start local search for the VRP (DESIGN.md §2 A25,
+// §4.3p): R independent small-fleet CVRP requests of one (N, K, H, objective,
+// S, rounds) share one launch, ONE WORKGROUP PER REQUEST.  The workgroup stages
+// its request's whole instance into LDS exactly as vrp_batch_sa does
+// (batch_stage.hpp: the [H][N][N] matrix as uint16, or int32 when `wide`, the
+// demand, capacity and start-time rows; a negative entry, or one above 65535
+// under wide = 0, ends the request with an all-ones key).  Its four wavefronts
+// then work alone until the final selection; wavefront w descends the starts
+// w, w + 4, ... one after the other on tours of n = N - 1 customers (no
+// separators: the greedy split prices them):
+//
+//   start s  vrp_batch_ga's member s: the Philox Fisher-Yates shuffle of 1..n,
+//            counters (0xffffffff, 0xffffffff, s, q);
+//   round    every move (typ, i, j) -- swap and 2-opt with i < j, relocate with
+//            i != j, 2 n (n - 1) in all -- is priced by eval_tour<true> over
+//            map_src(move_map(m), q).  The moves are numbered in (typ, i, j)
+//            order and lane l takes the ids [l per, (l + 1) per), per =
+//            ceil(2 n (n - 1) / 64): it decodes its first move once a launch
+//            and steps to the next by increments, keeping its least (key, id).
+//            The (key, lane) minimum of the wave is then the least (key, typ,
+//            i, j).  A key below the tour's applies the move in place (lane
+//            0 swaps; lanes reverse a 2-opt window by pairs; a relocate shifts
+//            by chunks of 64) and the next round follows; otherwise the tour
+//            is a local optimum.  After `rounds` applied moves the descent
+//            stops unproven and counts as capped.  n < 2 has no moves;
+//   answer   the least (key, s) over the S end tours: each wave keeps its own,
+//            and after the kernel's one barrier past staging the wave that
+//            holds the least walks it once more and writes the K route
+//            durations, every gene's vehicle, s and the capped count.
+//
+// The counters carry no request row: an answer does not depend on the launch
+// the request rode in or on its row in it.  With rounds = 0 the answer is
+// vrp_batch_ga's at P = S, G = 0.
+//
+// LDS, every part as the kernel carves it (vrpms_vrp_batch_ls_lds), never more
+// than vrpms_vrp_batch_sa_lds of the same shape:
+//   align16(H N N (wide ? 4 : 2))            the matrix
+// + 4 align4(N) + 2 * 4 align4(K)            demand, capacities, start times (int32)
+// + 4 * 2 * 2 align8(n)                      4 waves x (current, best end) uint16 tours
+// + 4 * 16                                   the waves' best key, best s, capped count
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "batch_stage.hpp"
+#include "common.hpp"
+#include "ctx.hpp"
+#include "staging.hpp"
+#include "tour.hpp"
+
+namespace vrpms {
+
+constexpr int kBatchLsMaxK = 64;      // one lane per route in the final walk
+constexpr int kBatchLsMaxN = 65535;   // genes are uint16
+constexpr int kBatchLsMaxS = 65535;
+
+struct VrpBatchLsArgs {
+  const int32_t* mats;    // [R][H][N][N]
+  const int32_t* demand;  // [R][N]
+  const int32_t* cap;     // [R][K]
+  const int32_t* start;   // [R][K]
+  int R, N, K, H, objective, S, rounds;
+  uint32_t seed_lo, seed_hi;
+  uint16_t* tours;        // [R][n]
+  uint64_t* keys;         // [R]
+  int32_t* durs;          // [R][K]
+  int8_t* veh;            // [R][n]
+  int32_t* info;          // [R][2]: the answer's start, the capped descents
+};
+
+struct BatchLsLds {
+  size_t mat, dem, row, tour, total;   // bytes of the matrix, the demand row, one K row, one tour
+};
+
+inline BatchLsLds batch_ls_lds(int N, int K, int H, int wide) {
+  BatchLsLds l;
+  l.mat = ((size_t)H * N * N * (wide ? 4 : 2) + 15) & ~(size_t)15;
+  l.dem = (((size_t)N + 3) & ~(size_t)3) * 4;
+  l.row = (((size_t)K + 3) & ~(size_t)3) * 4;
+  l.tour = (((size_t)N - 1 + 7) & ~(size_t)7) * 2;
+  l.total = l.mat + l.dem + 2 * l.row + 4 * 2 * l.tour + 4 * 16;
+  return l;
+}
+
+struct BatchLsWave {   // 16 bytes
+  uint64_t key;
+  int32_t s, capped;
+};
+
+// the move after m in (typ, i, j) order; n >= 2
+VRPMS_DEV void batch_ls_next(Move& m, int n) {
+  if (m.typ != kMoveRelocate) {
+    if (++m.j == n) {
+      ++m.i;
+      m.j = m.i + 1;
+      if (m.j == n) {   // the triangle is done: 2-opt after swap, relocate after 2-opt
+        ++m.typ;
+        m.i = 0;
+        m.j = 1;
+      }
+    }
+  } else {
+    ++m.j;
+    if (m.j == m.i) ++m.j;
+    if (m.j >= n) {
+      ++m.i;
+      m.j = 0;
+    }
+  }
+}
+
+// move number id of the 2 n (n - 1), n >= 2
+VRPMS_DEV Move batch_ls_move(int id, int n) {
+  const int tri = n * (n - 1) / 2;
+  Move m;
+  if (id >= 2 * tri) {
+    const int r = id - 2 * tri, jp = r % (n - 1);
+    m.typ = kMoveRelocate;
+    m.i = r / (n - 1);
+    m.j = jp + (jp >= m.i ? 1 : 0);
+    return m;
+  }
+  m.typ = id >= tri ? kMove2Opt : kMoveSwap;
+  int r = id >= tri ? id - tri : id, i = 0;
+  while (r >= n - 1 - i) {   // row i holds j = i + 1 .. n - 1
+    r -= n - 1 - i;
+    ++i;
+  }
+  m.i = i;
+  m.j = i + 1 + r;
+  return m;
+}
+
+template <typename MatT, int HM>
+__global__ __launch_bounds__(256) void vrp_batch_ls_kernel(VrpBatchLsArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char batch_ls_lds_mem[];
+  const int N = a.N, n = N - 1, K = a.K;
+  const int64_t r = blockIdx.x;
+  const uint32_t cells = (uint32_t)HM * (uint32_t)N * (uint32_t)N;
+  const uint32_t mat_bytes = (cells * (uint32_t)sizeof(MatT) + 15u) & ~15u;
+  const uint32_t dem_words = ((uint32_t)N + 3u) & ~3u, row_words = ((uint32_t)K + 3u) & ~3u;
+  const uint32_t tpad = ((uint32_t)n + 7u) & ~7u;
+  MatT* M = reinterpret_cast<MatT*>(batch_ls_lds_mem);
+  int32_t* dem = reinterpret_cast<int32_t*>(batch_ls_lds_mem + mat_bytes);
+  int32_t* cap = dem + dem_words;
+  int32_t* start = cap + row_words;
+  uint16_t* tours = reinterpret_cast<uint16_t*>(start + row_words);          // [4][2][tpad]
+  BatchLsWave* wst = reinterpret_cast<BatchLsWave*>(tours + 4 * 2 * tpad);    // [4]
+
+  // stage and check the request (batch_stage.hpp); the verdict goes through
+  // a word of the waves' records, free until the descents end
+  uint16_t* gtour = a.tours + r * n;
+  int8_t* gveh = a.veh + r * n;
+  int32_t* gdurs = a.durs + r * K;
+  if (batch_stage_request(a.mats, a.demand, a.cap, a.start, r, cells, N, K, M, dem, cap, start,
+                          reinterpret_cast<uint32_t*>(wst))) {
+    batch_refuse(gtour, gveh, gdurs, a.keys + r, n, K);
+    if (threadIdx.x == 0) {
+      a.info[2 * r] = -1;
+      a.info[2 * r + 1] = 0;
+    }
+    return;
+  }
+
+  const int wave = (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = lane_id();
+  uint16_t* A = tours + wave * 2 * tpad;   // current tour
+  uint16_t* Best = A + tpad;               // the wave's best end tour
+  const MatView<MatT, HM> D{M, (uint32_t)N, (uint32_t)N * (uint32_t)N, HM};
+  const SplitParams sp{dem, cap, start, K, a.objective};
+
+  // the lane's share of a round: ids [id0, id0 + cnt) from move m0 on
+  const int total = 2 * n * (n - 1), per = (total + 63) >> 6;
+  const int id0 = lane * per;
+  const int cnt = max(0, min(per, total - id0));
+  Move m0{kMoveSwap, 0, 1};
+  if (cnt > 0) m0 = batch_ls_move(id0, n);
+
+  // the wave-uniform move mb on A, in place
+  auto apply = [&](const Move& mb) {
+    const int i = mb.i, j = mb.j;
+    if (mb.typ == kMoveSwap) {
+      if (lane == 0) {
+        const uint16_t t = A[i];
+        A[i] = A[j];
+        A[j] = t;
+      }
+    } else if (mb.typ == kMove2Opt) {   // disjoint pairs (i + t, j - t)
+      const int half = (j - i + 1) >> 1;
+      for (int t = lane; t < half; t += 64) {
+        const uint16_t x = A[i + t];
+        A[i + t] = A[j - t];
+        A[j - t] = x;
+      }
+    } else if (i < j) {   // A[i+1..j] moves down one place, 64 at a time from below
+      const uint16_t v = A[i];
+      wave_sync();
+      for (int base = i; base < j; base += 64) {
+        const int q = base + lane;
+        uint16_t x = 0;
+        if (q < j) x = A[q + 1];
+        wave_sync();
+        if (q < j) A[q] = x;
+        wave_sync();
+      }
+      if (lane == 0) A[j] = v;
+    } else {              // A[j..i-1] moves up one place, 64 at a time from above
+      const uint16_t v = A[i];
+      wave_sync();
+      for (int top = i; top > j; top -= 64) {
+        const int q = top - lane;
+        uint16_t x = 0;
+        if (q > j) x = A[q - 1];
+        wave_sync();
+        if (q > j) A[q] = x;
+        wave_sync();
+      }
+      if (lane == 0) A[j] = v;
+    }
+    wave_sync();
+  };
+
+  uint64_t bk = ~0ull;
+  int bs = 0x7fffffff, capped = 0;
+  for (int s = wave; s < a.S; s += 4) {
+    // Philox Fisher-Yates start as in vrp_batch_sa: lane l draws the block of
+    // q = 64 c + l for a chunk of 64 swaps at once, lane 0 swaps
+    for (int q = lane; q < n; q += 64) A[q] = (uint16_t)(q + 1);
+    wave_sync();
+    uint32_t jv = 0;
+    for (int i = n - 1; i >= 1; --i) {
+      if (i == n - 1 || (i & 63) == 63) {
+        const uint32_t il = (uint32_t)(i & ~63) + (uint32_t)lane;
+        const u32x4 x = philox(0xffffffffu, 0xffffffffu, (uint32_t)s, il, a.seed_lo, a.seed_hi);
+        jv = x.x % (il + 1u);
+      }
+      const int j = __builtin_amdgcn_readlane((int)jv, i & 63);
+      if (lane == 0) {
+        const uint16_t t = A[i];
+        A[i] = A[j];
+        A[j] = t;
+      }
+    }
+    wave_sync();
+    uint64_t ck = readlane_u64(eval_tour<true>(D, sp, [&](int q) { return (uint32_t)A[q]; }, n).key, 0);
+    if (n >= 2) {
+      for (int applied = 0;; ++applied) {
+        if (applied >= a.rounds) {   // stopped unproven
+          ++capped;
+          break;
+        }
+        Move m = m0, lm = m0;
+        uint64_t lk = ~0ull;
+        for (int c = 0; c < cnt; ++c) {
+          const MoveMap mm = move_map(m);
+          const uint64_t k =
+              eval_tour<true>(D, sp, [&](int q) { return (uint32_t)A[map_src(mm, q)]; }, n).key;
+          if (k < lk) {
+            lk = k;
+            lm = m;
+          }
+          batch_ls_next(m, n);
+        }
+        // the lanes hold ascending id ranges: the lowest lane among equal keys
+        // holds the least (typ, i, j)
+        int bl;
+        const uint64_t k = wave_argmin_lane(lk, bl);
+        if (!(k < ck)) break;   // a local optimum
+        Move mb;
+        mb.typ = (uint32_t)wave_bcast((int)lm.typ, bl);
+        mb.i = wave_bcast(lm.i, bl);
+        mb.j = wave_bcast(lm.j, bl);
+        apply(mb);
+        ck = k;
+      }
+    }
+    if (ck < bk) {   // s rises: the least s among equal keys stays
+      bk = ck;
+      bs = s;
+      for (int q = lane; q < n; q += 64) Best[q] = A[q];
+      wave_sync();
+    }
+  }
+  if (lane == 0) wst[wave] = BatchLsWave{bk, bs, capped};
+  __syncthreads();
+  int bw = 0, ncap = wst[0].capped;
+  for (int w = 1; w < 4; ++w) {
+    if (wst[w].key < wst[bw].key || (wst[w].key == wst[bw].key && wst[w].s < wst[bw].s)) bw = w;
+    ncap += wst[w].capped;
+  }
+  if (wave != bw) return;
+
+  // the winner's best end tour once more, as spec.eval_cvrp walks it: every
+  // lane walks alike, lane k keeps route k's duration, lane 0 notes the
+  // vehicles (as int16 in the wave's current tour, no longer needed)
+  int16_t* V = reinterpret_cast<int16_t*>(A);
+  const int mydur = batch_final_walk(D, dem, cap, start, K, n, Best, n, V, lane);
+  wave_sync();
+  for (int q = lane; q < n; q += 64) {
+    gtour[q] = Best[q];
+    gveh[q] = (int8_t)V[q];
+  }
+  if (lane < K) gdurs[lane] = mydur;
+  if (lane == 0) {
+    a.keys[r] = bk;
+    a.info[2 * r] = bs;
+    a.info[2 * r + 1] = ncap;
+  }
+}
+
+// the shape checks both entry points share; 0 or the refusal's code
+static int batch_ls_check(const char* who, int32_t N, int32_t K, int32_t H, int32_t wide) {
+  const std::string w(who);
+  if (N < 2 || N > kBatchLsMaxN)
+    return fail(VRPMS_EINVAL, w + ": needs 2 <= N <= 65535 (" + std::to_string(N) + " given)");
+  if (K < 1 || K > kBatchLsMaxK)
+    return fail(VRPMS_EINVAL, w + ": one lane per route needs 1 <= K <= 64 (" + std::to_string(K) + " given)");
+  if (H != 1 && H != 24)
+    return fail(VRPMS_EINVAL, w + ": H must be 1 or 24 (" + std::to_string(H) + " given)");
+  if (wide != 0 && wide != 1)
+    return fail(VRPMS_EINVAL, w + ": wide must be 0 (uint16 matrix) or 1 (int32) (" + std::to_string(wide) +
+                                  " given)");
+  return VRPMS_OK;
+}
+
+}  // namespace vrpms
+
+using namespace vrpms;
+
+extern "C" int vrpms_vrp_batch_ls_lds(int32_t N, int32_t K, int32_t H, int32_t wide, uint64_t* bytes) {
+  if (!bytes) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_ls_lds: bytes is NULL");
+  const int rc = batch_ls_check("vrpms_vrp_batch_ls_lds", N, K, H, wide);
+  if (rc) return rc;
+  *bytes = batch_ls_lds(N, K, H, wide).total;
+  return VRPMS_OK;
+}
+
+extern "C" int vrpms_vrp_batch_ls(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_demand,
+                                  const int32_t* d_cap, const int32_t* d_start, int32_t R, int32_t N,
+                                  int32_t K, int32_t H, int32_t objective, int32_t wide, int32_t S,
+                                  int32_t rounds, uint64_t seed, uint16_t* d_tours, uint64_t* d_keys,
+                                  int32_t* d_durs, int8_t* d_veh, int32_t* d_info, void* stream) {
+  if (!ctx) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_ls: ctx is NULL");
+  if (R < 0) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_ls: R must not be negative");
+  const int rc = batch_ls_check("vrpms_vrp_batch_ls", N, K, H, wide);
+  if (rc) return rc;
+  if (objective != VRPMS_OBJ_SUM && objective != VRPMS_OBJ_MAX)
+    return fail(VRPMS_EINVAL, "vrpms_vrp_batch_ls: objective must be VRPMS_OBJ_SUM or VRPMS_OBJ_MAX");
+  if (S < 1 || S > kBatchLsMaxS)
+    return fail(VRPMS_EINVAL, "vrpms_vrp_batch_ls: 1 <= S <= 65535 (" + std::to_string(S) + " given)");
+  if (rounds < 0)
+    return fail(VRPMS_EINVAL,
+                "vrpms_vrp_batch_ls: rounds must not be negative (" + std::to_string(rounds) + " given)");
+  if (R == 0) return VRPMS_OK;
+  if (!d_mats || !d_demand || !d_cap || !d_start || !d_tours || !d_keys || !d_durs || !d_veh || !d_info)
+    return fail(VRPMS_EINVAL,
+                "vrpms_vrp_batch_ls: NULL matrix/demand/capacity/start/tour/key/duration/vehicle/info buffer");
+  const size_t lds = batch_ls_lds(N, K, H, wide).total;
+  if (lds > ctx->max_lds)
+    return fail(VRPMS_EINVAL, "vrpms_vrp_batch_ls: a request of N = " + std::to_string(N) + ", K = " +
+                                  std::to_string(K) + ", H = " + std::to_string(H) +
+                                  (wide ? " (int32 matrix)" : " (uint16 matrix)") + " needs " +
+                                  std::to_string(lds) + " bytes of LDS (" + std::to_string(ctx->max_lds) +
+                                  " available)");
+  VRPMS_HIP(hipSetDevice(ctx->device));
+  const VrpBatchLsArgs a{d_mats, d_demand, d_cap,  d_start, R,      N,      K,      H,     objective,
+                         S,      rounds,   (uint32_t)seed, (uint32_t)(seed >> 32), d_tours, d_keys,
+                         d_durs, d_veh,    d_info};
+  void (*kernel)(VrpBatchLsArgs) =
+      wide ? (H == 24 ? vrp_batch_ls_kernel<int32_t, 24> : vrp_batch_ls_kernel<int32_t, 1>)
+           : (H == 24 ? vrp_batch_ls_kernel<uint16_t, 24> : vrp_batch_ls_kernel<uint16_t, 1>);
+  if (lds > 65536)
+    VRPMS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  kernel<<<(unsigned)R, 256, lds, (hipStream_t)stream>>>(a);
+  VRPMS_HIP(hipGetLastError());
+  return VRPMS_OK;
+}

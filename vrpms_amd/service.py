@@ -39,7 +39,7 @@ TITLES = {"bf": "Brute Force", "ga": "Genetic Algorithm", "sa": "Simulated Annea
 # matrices) for the TSP and "tdsp" (its fleet counterpart, per-vehicle start
 # times) for the VRP (they have no /api endpoint: the eight endpoints are
 # the reference's wire contract)
-INLINE_ALGORITHMS = {"tsp": tuple(TITLES) + ("dp", "tdp"), "vrp": tuple(TITLES) + ("tdsp", "sp")}
+INLINE_ALGORITHMS = {"tsp": tuple(TITLES) + ("dp", "tdp"), "vrp": tuple(TITLES) + ("ls", "tdsp", "sp")}
 
 # (body key, params key) in the order the reference checks them
 # (api/parameters.py:4-15 and 34-44); 'auth' is the only optional one
@@ -57,14 +57,14 @@ _COMMON = {
 # in its "knobs" object (vrpms_amd.remote forwards them): name -> type
 INLINE_KNOBS = {"steps": int, "separators": int, "window": int, "chains": int,
                 "window_types": int, "pop": int, "islands": int, "colonies": int, "ants": int,
-                "upper_bound": int}
+                "upper_bound": int, "starts": int, "rounds": int}
 # their accepted ranges (inclusive): a value from the network outside them is a
 # 400, never an allocation (islands = 10**6 or chains = 2**30 would
 # exhaust device memory while the request holds every device lock)
 KNOB_RANGES = {"steps": (1, 10**8), "separators": (0, 4096), "window": (0, 65535),
                "chains": (1, 1 << 16), "window_types": (0, 7), "pop": (2, 4096),
                "islands": (1, 4096), "colonies": (1, 4096), "ants": (1, 4096),
-               "upper_bound": (0, 2**31 - 1)}
+               "upper_bound": (0, 2**31 - 1), "starts": (1, 1024), "rounds": (0, 1000)}
 
 
 def check_knob(name, value):
@@ -583,6 +583,46 @@ class VrpAcoBatcher(VrpSaBatcher):
         return tours, list(zip(veh, durs))
 
 
+class VrpLsBatcher(VrpSaBatcher):
+    """Coalesces concurrent /solve/vrp/ls requests into one `vrp_batch_ls`
+    launch per (node count, fleet size, hour count, cell width, objective)
+    (spec A25: one workgroup per request, its whole instance in LDS, a
+    multi-start local search).  Every launch descends from `starts` starts
+    for at most `rounds` rounds each, the batcher's own; a request that names
+    either inline takes the unbatched path.  The queue, the window, the device
+    round-robin and the error fan-out are TspBatcher's.  A batched answer does
+    not depend on the batch: it is solver.solve_vrp_ls_batch([request],
+    starts=, rounds=, seed=the app's, objective=)'s, which is also the
+    unbatched route's at the same knobs and seed."""
+
+    def __init__(self, app, window_s: float = 0.005, rounds: int = 1000, starts: int = 64,
+                 max_batch: int = 16384, launch=None):
+        from . import solver
+        if not 1 <= int(starts) <= solver.BATCH_LS_MAX_STARTS:
+            raise ValueError(f"starts must be in 1..{solver.BATCH_LS_MAX_STARTS} ({starts} given)")
+        if not 0 <= int(rounds) <= solver.BATCH_LS_MAX_ROUNDS:
+            raise ValueError(f"rounds must be in 0..{solver.BATCH_LS_MAX_ROUNDS} "
+                             f"({rounds} given)")
+        self.starts, self.rounds = int(starts), int(rounds)
+        super().__init__(app, window_s, steps=0, max_batch=max_batch, launch=launch)
+
+    def accepts(self, ci) -> bool:
+        """Requests inside A25's domain (LDS) that pass the int32 guards;
+        anything else takes the unbatched path, which raises the domain's
+        message."""
+        from . import solver
+        return solver.batch_ls_fits(ci, self.starts, self.rounds) and \
+            solver.batch_guard_message(ci) is None
+
+    def _gpu_launch(self, key, cis, device=None):
+        from . import solver
+        dev = self.devices[0] if device is None else device
+        with self.app.locks[dev]:
+            tours, veh, durs = solver.batch_ls_launch(solver.context(dev), cis, self.starts,
+                                                      self.rounds, self.app.seed, key[-1])
+        return tours, list(zip(veh, durs))
+
+
 # ---------------------------------------------------------------------------
 # the endpoint logic
 # ---------------------------------------------------------------------------
@@ -609,7 +649,9 @@ class App:
                  batch_vrp_sa: bool = False, batch_vrp_sa_launch=None,
                  batch_vrp_ga: bool = False, batch_vrp_ga_launch=None,
                  batch_vrp_aco: bool = False, batch_vrp_aco_launch=None,
-                 batch_aco_iterations: int = 100, batch_aco_ants: int = 64):
+                 batch_aco_iterations: int = 100, batch_aco_ants: int = 64,
+                 batch_vrp_ls: bool = False, batch_vrp_ls_launch=None,
+                 batch_ls_starts: int = 64, batch_ls_rounds: int = 1000):
         self.store = store
         self.devices = list(devices) if devices else [device]
         self.device = self.devices[0]
@@ -654,6 +696,10 @@ class App:
         self.vrp_aco_batcher = VrpAcoBatcher(self, batch_window_s, batch_aco_iterations,
                                              batch_aco_ants, launch=batch_vrp_aco_launch) \
             if batch_vrp_aco else None
+        # small-fleet VRP local-search requests share vrp_batch_ls launches
+        self.vrp_ls_batcher = VrpLsBatcher(self, batch_window_s, batch_ls_rounds,
+                                           batch_ls_starts, launch=batch_vrp_ls_launch) \
+            if batch_vrp_ls else None
 
     def _scheduled(self, problem, algorithm, params, knobs, locations, durations):
         """Run the solve on a device: all of them (in order, as an island
@@ -741,9 +787,22 @@ class App:
                                 params["ignored_customers"], params["completed_customers"])
         return ci if self.vrp_aco_batcher.accepts(ci) else None
 
+    def _batched_vrp_ls(self, problem, algorithm, params, knobs, locations, durations):
+        """The compact instance when this request rides the VRP local-search
+        batcher, else None: the flag is on, the route is vrp / ls, the request
+        names no inline knob of its own and it is inside the batcher's domain
+        (outside it the unbatched path raises the domain's message)."""
+        if self.vrp_ls_batcher is None or (problem, algorithm) != ("vrp", "ls") or \
+                knobs.get("inline"):
+            return None
+        from . import solver
+        ci = solver.compact_vrp(durations, locations, params["capacities"], params["start_times"],
+                                params["ignored_customers"], params["completed_customers"])
+        return ci if self.vrp_ls_batcher.accepts(ci) else None
+
     def _batched_vrp(self, problem, algorithm, params, knobs, locations, durations):
-        """A thunk that solves this request on the VRP SA, GA or ACO batcher,
-        else None."""
+        """A thunk that solves this request on the VRP SA, GA, ACO or
+        local-search batcher, else None."""
         objective = knobs.get("objective", "sum")
         vci = self._batched_vrp_sa(problem, algorithm, params, knobs, locations, durations)
         if vci is not None:
@@ -754,6 +813,9 @@ class App:
         aci = self._batched_vrp_aco(problem, algorithm, params, knobs, locations, durations)
         if aci is not None:
             return lambda: self.vrp_aco_batcher.solve(aci, objective)
+        lci = self._batched_vrp_ls(problem, algorithm, params, knobs, locations, durations)
+        if lci is not None:
+            return lambda: self.vrp_ls_batcher.solve(lci, objective)
         return None
 
     def _exact_batcher(self, problem, algorithm):
@@ -1093,6 +1155,17 @@ def main(argv=None):
                          "(solver.BATCH_ACO_MAX_ITERATIONS)")
     ap.add_argument("--batch-aco-ants", type=_int_in(1, solver.BATCH_ACO_MAX_ANTS), default=64,
                     help="ants of a vrp_batch_aco launch, 1..256 (solver.BATCH_ACO_MAX_ANTS)")
+    ap.add_argument("--batch-vrp-ls", action="store_true",
+                    help="coalesce concurrent small-fleet VRP local-search requests "
+                         "(/solve/vrp/ls, static or hour-indexed matrix, 1..64 vehicles, an "
+                         "instance that fits the LDS) into vrp_batch_ls launches of "
+                         "--batch-ls-starts starts and at most --batch-ls-rounds rounds a descent; "
+                         "the answer depends on the request alone, not on the batch it rode in")
+    ap.add_argument("--batch-ls-starts", type=_int_in(1, solver.BATCH_LS_MAX_STARTS), default=64,
+                    help="starts of a vrp_batch_ls launch, 1..1024 (solver.BATCH_LS_MAX_STARTS)")
+    ap.add_argument("--batch-ls-rounds", type=_int_in(0, solver.BATCH_LS_MAX_ROUNDS), default=1000,
+                    help="applied moves a descent of a vrp_batch_ls launch may take, 0..1000 "
+                         "(solver.BATCH_LS_MAX_ROUNDS)")
     ap.add_argument("--batch-window-ms", type=float, default=5.0)
     ap.add_argument("--batch-steps", type=int, default=2000)
     ap.add_argument("--workers", type=int, default=0,
@@ -1133,7 +1206,9 @@ def main(argv=None):
               batch_steps=args.batch_steps, devices=devices, batch_exact=args.batch_exact,
               batch_exact_tdsp=args.batch_exact_tdsp, batch_vrp_sa=args.batch_vrp_sa,
               batch_vrp_ga=args.batch_vrp_ga, batch_vrp_aco=args.batch_vrp_aco,
-              batch_aco_iterations=args.batch_aco_iterations, batch_aco_ants=args.batch_aco_ants)
+              batch_aco_iterations=args.batch_aco_iterations, batch_aco_ants=args.batch_aco_ants,
+              batch_vrp_ls=args.batch_vrp_ls, batch_ls_starts=args.batch_ls_starts,
+              batch_ls_rounds=args.batch_ls_rounds)
     srv = serve(app, args.host, args.port)
     print(f"vrpms_amd service on http://{args.host}:{args.port}/api", flush=True)
     try:
