@@ -726,6 +726,54 @@ int vrpms_vrp_batch_ls(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_d
                        int32_t rounds, uint64_t seed, uint16_t* d_tours, uint64_t* d_keys,
                        int32_t* d_durs, int8_t* d_veh, int32_t* d_info, void* stream);
 
+/* Throughput mode of a multi-start local search over separator tours for the
+ * VRP: vrpms_vrp_batch_ls's descent on the tours
+ * vrpms_vrp_batch_sa anneals.  The requests, their buffers, N, K, H, wide,
+ * objective, S, rounds and seed are vrpms_vrp_batch_ls's; a tour has
+ * L = n + K - 1 tokens, the n = N - 1 customers and K - 1 separators (the
+ * token 0, A10), and L <= 65535.  ONE WORKGROUP PER REQUEST, the instance in
+ * LDS next to two tours of L tokens per wavefront.  Wavefront w descends the
+ * starts w, w + 4, ...: start s is vrpms_vrp_batch_ls's start s -- the Philox
+ * Fisher-Yates shuffle of 1..n with counters (0xffffffff, 0xffffffff, s, q) --
+ * packed first-fit into the K routes with a separator between them, as
+ * vrpms_vrp_batch_sa packs chain w's (each customer, in shuffle order, to the
+ * first route with room for it, to the last when none has).  A round prices
+ * every move (typ, i, j) on positions 0..L-1, separators moved like customers
+ * -- swap (typ 0) and 2-opt (typ 1) with i < j, relocate (typ 2) with i != j,
+ * each the A8 key of the moved tour -- and takes the least (key, typ, i, j): a
+ * key below the tour's applies the move and the next round follows, otherwise
+ * the descent has stopped at a local optimum.  A descent also stops once
+ * `rounds` moves are applied; it then counts as capped.  L < 2 has no moves
+ * and is never capped.  The answer is the least (key, s) over the S end tours.
+ * The counters carry no request row, so a request's answer depends on the
+ * request, S, rounds, seed and objective alone: not on the launch it rode in
+ * nor on its row in it.  With K = 1 it is vrpms_vrp_batch_ls's; with S = 4 and
+ * rounds = 0 it is vrpms_vrp_batch_sa's at steps = 0.
+ * vrpms_vrp_batch_lsr_lds gives the launch's dynamic-LDS bytes for (N, K, H,
+ * wide) (host only, no context), never more than vrpms_vrp_batch_sa_lds of the
+ * same shape; a launch that needs more than the device has is refused with
+ * that byte count in the message.  (N + K + 1) * max(D) + max(start) < 2^31
+ * and cap + demand < 2^31 (A9) are the caller's promise.  Out, per request:
+ * d_tours [R][L] (the answer), d_keys [R] (its A8 key), d_durs [R][K] (the K
+ * route durations of that tour, unclamped, 0 for an empty route), d_veh [R][L]
+ * (the vehicle of every token of the tour, -1 for an unvisited customer, -2
+ * for a separator) and d_info [R][2] (the answer's start s, and the number of
+ * capped descents among the S).  A request whose matrix has a negative entry,
+ * or with wide = 0 one above 65535, gets UINT64_MAX, an all-zero tour, zero
+ * durations, vehicles of -1 and d_info = (-1, 0), descends nothing and touches
+ * nothing else.  No instance and no workspace needed; asynchronous on
+ * `stream`.  R = 0 launches nothing.  VRPMS_EINVAL, with nothing launched and
+ * nothing written, for a NULL ctx, R < 0, N outside 2..65535, K outside 1..64,
+ * N + K - 2 above 65535, H other than 1 or 24, an unknown wide or objective, S
+ * outside 1..65535, rounds < 0, a NULL buffer with R > 0, or an LDS need above
+ * the device's. */
+int vrpms_vrp_batch_lsr_lds(int32_t N, int32_t K, int32_t H, int32_t wide, uint64_t* bytes);
+int vrpms_vrp_batch_lsr(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_demand,
+                        const int32_t* d_cap, const int32_t* d_start, int32_t R, int32_t N,
+                        int32_t K, int32_t H, int32_t objective, int32_t wide, int32_t S,
+                        int32_t rounds, uint64_t seed, uint16_t* d_tours, uint64_t* d_keys,
+                        int32_t* d_durs, int8_t* d_veh, int32_t* d_info, void* stream);
+
 /* ------------------------------------------------------------------------
  * Populations and the island model.  A pool is a set of
  * tours with their A8 keys: SA chains, a GA population ([islands][pop],

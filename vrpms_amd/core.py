@@ -116,6 +116,17 @@ def vrp_batch_ls_lds(N: int, K: int, H: int, wide) -> int:
     return int(nbytes.value)
 
 
+def vrp_batch_lsr_lds(N: int, K: int, H: int, wide) -> int:
+    """vrpms_vrp_batch_lsr_lds: the dynamic-LDS bytes of a vrp_batch_lsr launch
+    for N nodes, K vehicles, H hour slices (1 or 24) and a uint16 (`wide`
+    false) or int32 (`wide` true) matrix; never more than vrp_batch_sa_lds of
+    the same shape.  Host only: needs the library, no GPU."""
+    nbytes = ctypes.c_uint64()
+    check(_lib.load().vrpms_vrp_batch_lsr_lds(int(N), int(K), int(H), int(wide),
+                                              ctypes.byref(nbytes)))
+    return int(nbytes.value)
+
+
 def tdp_words(start: int, horizon: int) -> int:
     """Hour words of one A16 row: the words from the start's hour to the one
     of start + horizon."""
@@ -849,6 +860,53 @@ class Context:
                                           int(seed) & (2**64 - 1), tours.data_ptr(),
                                           keys.data_ptr(), durs.data_ptr(), veh.data_ptr(),
                                           info.data_ptr(), self.stream()))
+        return tours, keys, durs, veh, info
+
+    def vrp_batch_lsr(self, mats, demand, caps, starts, objective: int, nstarts: int, rounds: int,
+                      seed: int, wide=None):
+        """A multi-start local search over separator tours per request, one
+        workgroup per request, one launch for all (spec A26; all requests of
+        one N, K, H and objective): vrp_batch_ls's arguments -> (tours int16
+        [R][L], keys int64 [R], durs int32 [R][K], veh int8 [R][L], info int32
+        [R][2]) with L = N - 1 + K - 1 tokens, 0 a route separator: per
+        request the least (key, start) end tour of `nstarts` (1..65535)
+        steepest descents over swap, 2-opt and relocate on all L positions,
+        start s being vrp_batch_ls's start s packed first-fit into the K
+        routes as vrp_batch_sa packs its chains', each stopped at a local
+        optimum or after `rounds` (>= 0) applied moves; its A8 key, its K route
+        durations (unclamped, 0 for an empty route), the vehicle of every token
+        (-1 unvisited, -2 a separator), and info = (the winning start, the
+        number of descents the round cap stopped unproven).  A request's row
+        depends on the request, `nstarts`, `rounds`, `seed` and `objective`
+        alone, not on the batch.  `wide`: False stages the matrices as uint16
+        (a request with an entry above 65535 then gets an all-ones key, a zero
+        tour, zero durations, veh = -1 and info = (-1, 0)), True as int32;
+        None -- the default -- asks the device for the batch's largest entry,
+        which synchronises.  The A9 guard and non-negative demands and
+        capacities are the caller's promise.  Asynchronous on the current
+        stream."""
+        torch = _torch()
+        mats = self._batch_mats(torch, mats, 4)
+        R, H, N, _ = mats.shape
+        self._batch_rows(torch, demand, caps, R, N)
+        K = caps.shape[1]
+        if starts.device != self.dev or starts.shape != caps.shape or starts.dtype != torch.int32 \
+                or not starts.is_contiguous():
+            raise ValueError(f"starts must be a contiguous int32 [R][K] tensor on {self.dev}")
+        if wide is None:
+            wide = bool(R) and int(mats.max().item()) > 65535
+        L = N - 1 + K - 1
+        tours = torch.empty((R, max(L, 1)), dtype=torch.int16, device=self.dev)
+        keys = torch.empty(R, dtype=torch.int64, device=self.dev)
+        durs = torch.empty((R, max(K, 1)), dtype=torch.int32, device=self.dev)
+        veh = torch.empty((R, max(L, 1)), dtype=torch.int8, device=self.dev)
+        info = torch.empty((R, 2), dtype=torch.int32, device=self.dev)
+        check(self.lib.vrpms_vrp_batch_lsr(self._ctx, mats.data_ptr(), demand.data_ptr(),
+                                           caps.data_ptr(), starts.data_ptr(), R, N, K, H,
+                                           int(objective), int(bool(wide)), int(nstarts), int(rounds),
+                                           int(seed) & (2**64 - 1), tours.data_ptr(),
+                                           keys.data_ptr(), durs.data_ptr(), veh.data_ptr(),
+                                           info.data_ptr(), self.stream()))
         return tours, keys, durs, veh, info
 
     def set_batch_dp_team(self, T: int):

@@ -1,5 +1,5 @@
 // What the one-workgroup-per-request VRP kernels share (vrp_batch_sa.hip, A22;
-// vrp_batch_ga.hip, A23; vrp_batch_aco.hip, A24; vrp_batch_ls.hip, A25): staging a request's instance into LDS with the entry
+// vrp_batch_ga.hip, A23; vrp_batch_aco.hip, A24; vrp_batch_ls.hip, A25; vrp_batch_lsr.hip, A26): staging a request's instance into LDS with the entry
 // check on the way, the refusal row, and the final walk of the winning tour.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -30,7 +30,9 @@
 //
 // The counters carry no request row: an answer does not depend on the launch
 // the request rode in or on its row in it.  With rounds = 0 the answer is
-// vrp_batch_ga's at P = S, G = 0.
+// vrp_batch_ga's at P = S, G = 0.  The move order, the lane's share, the start
+// shuffle, the in-place move and the round loop are batch_ls.hpp's, shared with
+// vrp_batch_lsr.hip (A26).
 //
 // LDS, every part as the kernel carves it (vrpms_vrp_batch_ls_lds), never more
 // than vrpms_vrp_batch_sa_lds of the same shape:
@@ -42,6 +44,7 @@
 
 #include <string>
 
+#include "batch_ls.hpp"
 #include "batch_stage.hpp"
 #include "common.hpp"
 #include "ctx.hpp"
@@ -82,55 +85,6 @@ inline BatchLsLds batch_ls_lds(int N, int K, int H, int wide) {
   return l;
 }
 
-struct BatchLsWave {   // 16 bytes
-  uint64_t key;
-  int32_t s, capped;
-};
-
-// the move after m in (typ, i, j) order; n >= 2
-VRPMS_DEV void batch_ls_next(Move& m, int n) {
-  if (m.typ != kMoveRelocate) {
-    if (++m.j == n) {
-      ++m.i;
-      m.j = m.i + 1;
-      if (m.j == n) {   // the triangle is done: 2-opt after swap, relocate after 2-opt
-        ++m.typ;
-        m.i = 0;
-        m.j = 1;
-      }
-    }
-  } else {
-    ++m.j;
-    if (m.j == m.i) ++m.j;
-    if (m.j >= n) {
-      ++m.i;
-      m.j = 0;
-    }
-  }
-}
-
-// move number id of the 2 n (n - 1), n >= 2
-VRPMS_DEV Move batch_ls_move(int id, int n) {
-  const int tri = n * (n - 1) / 2;
-  Move m;
-  if (id >= 2 * tri) {
-    const int r = id - 2 * tri, jp = r % (n - 1);
-    m.typ = kMoveRelocate;
-    m.i = r / (n - 1);
-    m.j = jp + (jp >= m.i ? 1 : 0);
-    return m;
-  }
-  m.typ = id >= tri ? kMove2Opt : kMoveSwap;
-  int r = id >= tri ? id - tri : id, i = 0;
-  while (r >= n - 1 - i) {   // row i holds j = i + 1 .. n - 1
-    r -= n - 1 - i;
-    ++i;
-  }
-  m.i = i;
-  m.j = i + 1 + r;
-  return m;
-}
-
 template <typename MatT, int HM>
 __global__ __launch_bounds__(256) void vrp_batch_ls_kernel(VrpBatchLsArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char batch_ls_lds_mem[];
@@ -168,111 +122,14 @@ __global__ __launch_bounds__(256) void vrp_batch_ls_kernel(VrpBatchLsArgs a) {
   const MatView<MatT, HM> D{M, (uint32_t)N, (uint32_t)N * (uint32_t)N, HM};
   const SplitParams sp{dem, cap, start, K, a.objective};
 
-  // the lane's share of a round: ids [id0, id0 + cnt) from move m0 on
-  const int total = 2 * n * (n - 1), per = (total + 63) >> 6;
-  const int id0 = lane * per;
-  const int cnt = max(0, min(per, total - id0));
-  Move m0{kMoveSwap, 0, 1};
-  if (cnt > 0) m0 = batch_ls_move(id0, n);
-
-  // the wave-uniform move mb on A, in place
-  auto apply = [&](const Move& mb) {
-    const int i = mb.i, j = mb.j;
-    if (mb.typ == kMoveSwap) {
-      if (lane == 0) {
-        const uint16_t t = A[i];
-        A[i] = A[j];
-        A[j] = t;
-      }
-    } else if (mb.typ == kMove2Opt) {   // disjoint pairs (i + t, j - t)
-      const int half = (j - i + 1) >> 1;
-      for (int t = lane; t < half; t += 64) {
-        const uint16_t x = A[i + t];
-        A[i + t] = A[j - t];
-        A[j - t] = x;
-      }
-    } else if (i < j) {   // A[i+1..j] moves down one place, 64 at a time from below
-      const uint16_t v = A[i];
-      wave_sync();
-      for (int base = i; base < j; base += 64) {
-        const int q = base + lane;
-        uint16_t x = 0;
-        if (q < j) x = A[q + 1];
-        wave_sync();
-        if (q < j) A[q] = x;
-        wave_sync();
-      }
-      if (lane == 0) A[j] = v;
-    } else {              // A[j..i-1] moves up one place, 64 at a time from above
-      const uint16_t v = A[i];
-      wave_sync();
-      for (int top = i; top > j; top -= 64) {
-        const int q = top - lane;
-        uint16_t x = 0;
-        if (q > j) x = A[q - 1];
-        wave_sync();
-        if (q > j) A[q] = x;
-        wave_sync();
-      }
-      if (lane == 0) A[j] = v;
-    }
-    wave_sync();
-  };
+  const BatchLsShare sh = batch_ls_share(n, lane);   // the lane's share of a round
 
   uint64_t bk = ~0ull;
   int bs = 0x7fffffff, capped = 0;
   for (int s = wave; s < a.S; s += 4) {
-    // Philox Fisher-Yates start as in vrp_batch_sa: lane l draws the block of
-    // q = 64 c + l for a chunk of 64 swaps at once, lane 0 swaps
-    for (int q = lane; q < n; q += 64) A[q] = (uint16_t)(q + 1);
-    wave_sync();
-    uint32_t jv = 0;
-    for (int i = n - 1; i >= 1; --i) {
-      if (i == n - 1 || (i & 63) == 63) {
-        const uint32_t il = (uint32_t)(i & ~63) + (uint32_t)lane;
-        const u32x4 x = philox(0xffffffffu, 0xffffffffu, (uint32_t)s, il, a.seed_lo, a.seed_hi);
-        jv = x.x % (il + 1u);
-      }
-      const int j = __builtin_amdgcn_readlane((int)jv, i & 63);
-      if (lane == 0) {
-        const uint16_t t = A[i];
-        A[i] = A[j];
-        A[j] = t;
-      }
-    }
-    wave_sync();
+    batch_ls_shuffle(A, n, s, a.seed_lo, a.seed_hi, lane);
     uint64_t ck = readlane_u64(eval_tour<true>(D, sp, [&](int q) { return (uint32_t)A[q]; }, n).key, 0);
-    if (n >= 2) {
-      for (int applied = 0;; ++applied) {
-        if (applied >= a.rounds) {   // stopped unproven
-          ++capped;
-          break;
-        }
-        Move m = m0, lm = m0;
-        uint64_t lk = ~0ull;
-        for (int c = 0; c < cnt; ++c) {
-          const MoveMap mm = move_map(m);
-          const uint64_t k =
-              eval_tour<true>(D, sp, [&](int q) { return (uint32_t)A[map_src(mm, q)]; }, n).key;
-          if (k < lk) {
-            lk = k;
-            lm = m;
-          }
-          batch_ls_next(m, n);
-        }
-        // the lanes hold ascending id ranges: the lowest lane among equal keys
-        // holds the least (typ, i, j)
-        int bl;
-        const uint64_t k = wave_argmin_lane(lk, bl);
-        if (!(k < ck)) break;   // a local optimum
-        Move mb;
-        mb.typ = (uint32_t)wave_bcast((int)lm.typ, bl);
-        mb.i = wave_bcast(lm.i, bl);
-        mb.j = wave_bcast(lm.j, bl);
-        apply(mb);
-        ck = k;
-      }
-    }
+    if (n >= 2) ck = batch_ls_descend(D, sp, A, n, ck, a.rounds, sh, lane, capped);
     if (ck < bk) {   // s rises: the least s among equal keys stays
       bk = ck;
       bs = s;
@@ -282,11 +139,8 @@ __global__ __launch_bounds__(256) void vrp_batch_ls_kernel(VrpBatchLsArgs a) {
   }
   if (lane == 0) wst[wave] = BatchLsWave{bk, bs, capped};
   __syncthreads();
-  int bw = 0, ncap = wst[0].capped;
-  for (int w = 1; w < 4; ++w) {
-    if (wst[w].key < wst[bw].key || (wst[w].key == wst[bw].key && wst[w].s < wst[bw].s)) bw = w;
-    ncap += wst[w].capped;
-  }
+  int ncap;
+  const int bw = batch_ls_winner(wst, ncap);
   if (wave != bw) return;
 
   // the winner's best end tour once more, as spec.eval_cvrp walks it: every

@@ -1,0 +1,252 @@
+// Throughput mode of a multi-start local search over separator tours for the
+// VRP: vrp_batch_ls's descent (A25) on the tours
+// vrp_batch_sa anneals (A22).  R independent small-fleet CVRP requests of one
+// (N, K, H, objective, S, rounds) share one launch, ONE WORKGROUP PER REQUEST.
+// The workgroup stages its request's whole instance into LDS exactly as
+// vrp_batch_sa does (batch_stage.hpp).  Its four wavefronts then work alone
+// until the final selection; wavefront w descends the starts w, w + 4, ... one
+// after the other on tours of L = n + K - 1 tokens, n = N - 1 customers and
+// K - 1 separators (the token 0, A10):
+//
+//   start s  vrp_batch_ls's start s, the Philox Fisher-Yates shuffle of 1..n
+//            with counters (0xffffffff, 0xffffffff, s, q), then
+//            spec.pack_separators: first fit into K routes, one lane per route
+//            (the fitting routes by one ballot).  The wave has no third row
+//            for it, so the packing is in place: the row starts as K - 1
+//            separators followed by the shuffle, and customer q, at position
+//            K - 1 + q, is relocated to the end of its route -- the tokens of
+//            the later routes move up one place, by the descent's own relocate;
+//   round    vrp_batch_ls's (batch_ls.hpp) over the L positions: all
+//            2 L (L - 1) moves (typ, i, j), separators moved like customers,
+//            lane l pricing the ids [l per, (l + 1) per), the least (key, typ,
+//            i, j) applied in place while its key is below the tour's, at most
+//            `rounds` applied moves.  L < 2 has no moves;
+//   answer   the least (key, s) over the S end tours: each wave keeps its own,
+//            and after the kernel's one barrier past staging the wave that
+//            holds the least walks it once more and writes the K route
+//            durations, every token's vehicle, s and the capped count.
+//
+// The counters carry no request row: an answer does not depend on the launch
+// the request rode in or on its row in it.  With K = 1 the answer is
+// vrp_batch_ls's; with S = 4 and rounds = 0 it is vrp_batch_sa's at steps = 0.
+//
+// LDS, every part as the kernel carves it (vrpms_vrp_batch_lsr_lds), never more
+// than vrpms_vrp_batch_sa_lds of the same shape:
+//   align16(H N N (wide ? 4 : 2))            the matrix
+// + 4 align4(N) + 2 * 4 align4(K)            demand, capacities, start times (int32)
+// + 4 * 2 * 2 align8(L)                      4 waves x (current, best end) uint16 tours
+// + 4 * 16                                   the waves' best key, best s, capped count
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "batch_ls.hpp"
+#include "batch_stage.hpp"
+#include "common.hpp"
+#include "ctx.hpp"
+#include "staging.hpp"
+#include "tour.hpp"
+
+namespace vrpms {
+
+constexpr int kBatchLsrMaxK = 64;      // one lane per route in the first-fit start
+constexpr int kBatchLsrMaxN = 65535;   // tokens are uint16
+constexpr int kBatchLsrMaxL = 65535;   // positions too
+constexpr int kBatchLsrMaxS = 65535;
+
+struct VrpBatchLsrArgs {
+  const int32_t* mats;    // [R][H][N][N]
+  const int32_t* demand;  // [R][N]
+  const int32_t* cap;     // [R][K]
+  const int32_t* start;   // [R][K]
+  int R, N, K, H, objective, S, rounds;
+  uint32_t seed_lo, seed_hi;
+  uint16_t* tours;        // [R][L]
+  uint64_t* keys;         // [R]
+  int32_t* durs;          // [R][K]
+  int8_t* veh;            // [R][L]
+  int32_t* info;          // [R][2]: the answer's start, the capped descents
+};
+
+struct BatchLsrLds {
+  size_t mat, dem, row, tour, total;   // bytes of the matrix, the demand row, one K row, one tour
+};
+
+inline BatchLsrLds batch_lsr_lds(int N, int K, int H, int wide) {
+  BatchLsrLds l;
+  l.mat = ((size_t)H * N * N * (wide ? 4 : 2) + 15) & ~(size_t)15;
+  l.dem = (((size_t)N + 3) & ~(size_t)3) * 4;
+  l.row = (((size_t)K + 3) & ~(size_t)3) * 4;
+  l.tour = (((size_t)N - 1 + K - 1 + 7) & ~(size_t)7) * 2;
+  l.total = l.mat + l.dem + 2 * l.row + 4 * 2 * l.tour + 4 * 16;
+  return l;
+}
+
+template <typename MatT, int HM>
+__global__ __launch_bounds__(256) void vrp_batch_lsr_kernel(VrpBatchLsrArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char batch_lsr_lds_mem[];
+  const int N = a.N, n = N - 1, K = a.K, L = n + K - 1;
+  const int64_t r = blockIdx.x;
+  const uint32_t cells = (uint32_t)HM * (uint32_t)N * (uint32_t)N;
+  const uint32_t mat_bytes = (cells * (uint32_t)sizeof(MatT) + 15u) & ~15u;
+  const uint32_t dem_words = ((uint32_t)N + 3u) & ~3u, row_words = ((uint32_t)K + 3u) & ~3u;
+  const uint32_t tpad = ((uint32_t)L + 7u) & ~7u;
+  MatT* M = reinterpret_cast<MatT*>(batch_lsr_lds_mem);
+  int32_t* dem = reinterpret_cast<int32_t*>(batch_lsr_lds_mem + mat_bytes);
+  int32_t* cap = dem + dem_words;
+  int32_t* start = cap + row_words;
+  uint16_t* tours = reinterpret_cast<uint16_t*>(start + row_words);          // [4][2][tpad]
+  BatchLsWave* wst = reinterpret_cast<BatchLsWave*>(tours + 4 * 2 * tpad);    // [4]
+
+  // stage and check the request (batch_stage.hpp); the verdict goes through
+  // a word of the waves' records, free until the descents end
+  uint16_t* gtour = a.tours + r * L;
+  int8_t* gveh = a.veh + r * L;
+  int32_t* gdurs = a.durs + r * K;
+  if (batch_stage_request(a.mats, a.demand, a.cap, a.start, r, cells, N, K, M, dem, cap, start,
+                          reinterpret_cast<uint32_t*>(wst))) {
+    batch_refuse(gtour, gveh, gdurs, a.keys + r, L, K);
+    if (threadIdx.x == 0) {
+      a.info[2 * r] = -1;
+      a.info[2 * r + 1] = 0;
+    }
+    return;
+  }
+
+  const int wave = (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = lane_id();
+  uint16_t* A = tours + wave * 2 * tpad;   // current tour
+  uint16_t* Best = A + tpad;               // the wave's best end tour
+  const MatView<MatT, HM> D{M, (uint32_t)N, (uint32_t)N * (uint32_t)N, HM};
+  const SplitParams sp{dem, cap, start, K, a.objective};
+
+  const BatchLsShare sh = batch_ls_share(L, lane);   // the lane's share of a round
+
+  uint64_t bk = ~0ull;
+  int bs = 0x7fffffff, capped = 0;
+  for (int s = wave; s < a.S; s += 4) {
+    // K - 1 separators (K empty routes), then the shuffle of 1..n
+    for (int q = lane; q < K - 1; q += 64) A[q] = 0;
+    batch_ls_shuffle(A + (K - 1), n, s, a.seed_lo, a.seed_hi, lane);
+    // spec.pack_separators(perm, K - 1), in place: lane b holds route b's
+    // load, its room and `end`, the position just past its last customer (its
+    // separator's; for route K - 1 the next customer's own).  Customer q goes
+    // to the first route that has room for it, to the last one when none has.
+    {
+      const int64_t room = lane < K ? (int64_t)cap[lane] : -1;
+      int64_t load = 0;
+      int end = lane;
+      for (int q = 0; q < n; ++q) {
+        const int at = K - 1 + q;
+        const int64_t d = dem[A[at]];
+        const uint64_t fits = __builtin_amdgcn_ballot_w64(lane < K && load + d <= room);
+        const int b = fits ? (int)__builtin_ctzll(fits) : K - 1;
+        const int pos = __builtin_amdgcn_readlane(end, b);
+        if (lane == b) load += d;
+        if (lane >= b) ++end;
+        if (pos < at) batch_ls_apply(A, Move{kMoveRelocate, at, pos}, lane);
+      }
+    }
+    uint64_t ck = readlane_u64(eval_tour<true>(D, sp, [&](int q) { return (uint32_t)A[q]; }, L).key, 0);
+    if (L >= 2) ck = batch_ls_descend(D, sp, A, L, ck, a.rounds, sh, lane, capped);
+    if (ck < bk) {   // s rises: the least s among equal keys stays
+      bk = ck;
+      bs = s;
+      for (int q = lane; q < L; q += 64) Best[q] = A[q];
+      wave_sync();
+    }
+  }
+  if (lane == 0) wst[wave] = BatchLsWave{bk, bs, capped};
+  __syncthreads();
+  int ncap;
+  const int bw = batch_ls_winner(wst, ncap);
+  if (wave != bw) return;
+
+  // the winner's best end tour once more, as spec.eval_cvrp walks it: every
+  // lane walks alike, lane k keeps route k's duration, lane 0 notes the
+  // vehicles (as int16 in the wave's current tour, no longer needed)
+  int16_t* V = reinterpret_cast<int16_t*>(A);
+  const int mydur = batch_final_walk(D, dem, cap, start, K, n, Best, L, V, lane);
+  wave_sync();
+  for (int q = lane; q < L; q += 64) {
+    gtour[q] = Best[q];
+    gveh[q] = (int8_t)V[q];
+  }
+  if (lane < K) gdurs[lane] = mydur;
+  if (lane == 0) {
+    a.keys[r] = bk;
+    a.info[2 * r] = bs;
+    a.info[2 * r + 1] = ncap;
+  }
+}
+
+// the shape checks both entry points share; 0 or the refusal's code
+static int batch_lsr_check(const char* who, int32_t N, int32_t K, int32_t H, int32_t wide) {
+  const std::string w(who);
+  if (N < 2 || N > kBatchLsrMaxN)
+    return fail(VRPMS_EINVAL, w + ": needs 2 <= N <= 65535 (" + std::to_string(N) + " given)");
+  if (K < 1 || K > kBatchLsrMaxK)
+    return fail(VRPMS_EINVAL, w + ": one lane per route needs 1 <= K <= 64 (" + std::to_string(K) + " given)");
+  if (N - 1 + K - 1 > kBatchLsrMaxL)
+    return fail(VRPMS_EINVAL, w + ": positions are uint16: needs N + K - 2 <= 65535 (" +
+                                  std::to_string(N - 1 + K - 1) + " given)");
+  if (H != 1 && H != 24)
+    return fail(VRPMS_EINVAL, w + ": H must be 1 or 24 (" + std::to_string(H) + " given)");
+  if (wide != 0 && wide != 1)
+    return fail(VRPMS_EINVAL, w + ": wide must be 0 (uint16 matrix) or 1 (int32) (" + std::to_string(wide) +
+                                  " given)");
+  return VRPMS_OK;
+}
+
+}  // namespace vrpms
+
+using namespace vrpms;
+
+extern "C" int vrpms_vrp_batch_lsr_lds(int32_t N, int32_t K, int32_t H, int32_t wide, uint64_t* bytes) {
+  if (!bytes) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_lsr_lds: bytes is NULL");
+  const int rc = batch_lsr_check("vrpms_vrp_batch_lsr_lds", N, K, H, wide);
+  if (rc) return rc;
+  *bytes = batch_lsr_lds(N, K, H, wide).total;
+  return VRPMS_OK;
+}
+
+extern "C" int vrpms_vrp_batch_lsr(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_demand,
+                                   const int32_t* d_cap, const int32_t* d_start, int32_t R, int32_t N,
+                                   int32_t K, int32_t H, int32_t objective, int32_t wide, int32_t S,
+                                   int32_t rounds, uint64_t seed, uint16_t* d_tours, uint64_t* d_keys,
+                                   int32_t* d_durs, int8_t* d_veh, int32_t* d_info, void* stream) {
+  if (!ctx) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_lsr: ctx is NULL");
+  if (R < 0) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_lsr: R must not be negative");
+  const int rc = batch_lsr_check("vrpms_vrp_batch_lsr", N, K, H, wide);
+  if (rc) return rc;
+  if (objective != VRPMS_OBJ_SUM && objective != VRPMS_OBJ_MAX)
+    return fail(VRPMS_EINVAL, "vrpms_vrp_batch_lsr: objective must be VRPMS_OBJ_SUM or VRPMS_OBJ_MAX");
+  if (S < 1 || S > kBatchLsrMaxS)
+    return fail(VRPMS_EINVAL, "vrpms_vrp_batch_lsr: 1 <= S <= 65535 (" + std::to_string(S) + " given)");
+  if (rounds < 0)
+    return fail(VRPMS_EINVAL,
+                "vrpms_vrp_batch_lsr: rounds must not be negative (" + std::to_string(rounds) + " given)");
+  if (R == 0) return VRPMS_OK;
+  if (!d_mats || !d_demand || !d_cap || !d_start || !d_tours || !d_keys || !d_durs || !d_veh || !d_info)
+    return fail(VRPMS_EINVAL,
+                "vrpms_vrp_batch_lsr: NULL matrix/demand/capacity/start/tour/key/duration/vehicle/info buffer");
+  const size_t lds = batch_lsr_lds(N, K, H, wide).total;
+  if (lds > ctx->max_lds)
+    return fail(VRPMS_EINVAL, "vrpms_vrp_batch_lsr: a request of N = " + std::to_string(N) + ", K = " +
+                                  std::to_string(K) + ", H = " + std::to_string(H) +
+                                  (wide ? " (int32 matrix)" : " (uint16 matrix)") + " needs " +
+                                  std::to_string(lds) + " bytes of LDS (" + std::to_string(ctx->max_lds) +
+                                  " available)");
+  VRPMS_HIP(hipSetDevice(ctx->device));
+  const VrpBatchLsrArgs a{d_mats, d_demand, d_cap,  d_start, R,      N,      K,      H,     objective,
+                          S,      rounds,   (uint32_t)seed, (uint32_t)(seed >> 32), d_tours, d_keys,
+                          d_durs, d_veh,    d_info};
+  void (*kernel)(VrpBatchLsrArgs) =
+      wide ? (H == 24 ? vrp_batch_lsr_kernel<int32_t, 24> : vrp_batch_lsr_kernel<int32_t, 1>)
+           : (H == 24 ? vrp_batch_lsr_kernel<uint16_t, 24> : vrp_batch_lsr_kernel<uint16_t, 1>);
+  if (lds > 65536)
+    VRPMS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  kernel<<<(unsigned)R, 256, lds, (hipStream_t)stream>>>(a);
+  VRPMS_HIP(hipGetLastError());
+  return VRPMS_OK;
+}

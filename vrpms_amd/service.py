@@ -39,7 +39,8 @@ TITLES = {"bf": "Brute Force", "ga": "Genetic Algorithm", "sa": "Simulated Annea
 # matrices) for the TSP and "tdsp" (its fleet counterpart, per-vehicle start
 # times) for the VRP (they have no /api endpoint: the eight endpoints are
 # the reference's wire contract)
-INLINE_ALGORITHMS = {"tsp": tuple(TITLES) + ("dp", "tdp"), "vrp": tuple(TITLES) + ("ls", "tdsp", "sp")}
+INLINE_ALGORITHMS = {"tsp": tuple(TITLES) + ("dp", "tdp"),
+                     "vrp": tuple(TITLES) + ("ls", "lsr", "tdsp", "sp")}
 
 # (body key, params key) in the order the reference checks them
 # (api/parameters.py:4-15 and 34-44); 'auth' is the only optional one
@@ -623,6 +624,44 @@ class VrpLsBatcher(VrpSaBatcher):
         return tours, list(zip(veh, durs))
 
 
+class VrpLsrBatcher(VrpLsBatcher):
+    """Coalesces concurrent /solve/vrp/lsr requests into one `vrp_batch_lsr`
+    launch per (node count, fleet size, hour count, cell width, objective)
+    (spec A26: VrpLsBatcher's local search on giant tours with route
+    separators).  Every launch descends from `starts` starts for at most
+    `rounds` rounds each, the batcher's own; a request that names either
+    inline takes the unbatched path.  A batched answer does not depend on the
+    batch: it is solver.solve_vrp_lsr_batch([request], starts=, rounds=,
+    seed=the app's, objective=)'s, which is also the unbatched route's at the
+    same knobs and seed."""
+
+    def __init__(self, app, window_s: float = 0.005, rounds: int = 1000, starts: int = 64,
+                 max_batch: int = 16384, launch=None):
+        from . import solver
+        if not 1 <= int(starts) <= solver.BATCH_LSR_MAX_STARTS:
+            raise ValueError(f"starts must be in 1..{solver.BATCH_LSR_MAX_STARTS} ({starts} given)")
+        if not 0 <= int(rounds) <= solver.BATCH_LSR_MAX_ROUNDS:
+            raise ValueError(f"rounds must be in 0..{solver.BATCH_LSR_MAX_ROUNDS} "
+                             f"({rounds} given)")
+        super().__init__(app, window_s, rounds, starts, max_batch=max_batch, launch=launch)
+
+    def accepts(self, ci) -> bool:
+        """Requests inside A26's domain (LDS) that pass the int32 guards;
+        anything else takes the unbatched path, which raises the domain's
+        message."""
+        from . import solver
+        return solver.batch_lsr_fits(ci, self.starts, self.rounds) and \
+            solver.batch_guard_message(ci) is None
+
+    def _gpu_launch(self, key, cis, device=None):
+        from . import solver
+        dev = self.devices[0] if device is None else device
+        with self.app.locks[dev]:
+            tours, veh, durs = solver.batch_lsr_launch(solver.context(dev), cis, self.starts,
+                                                       self.rounds, self.app.seed, key[-1])
+        return tours, list(zip(veh, durs))
+
+
 # ---------------------------------------------------------------------------
 # the endpoint logic
 # ---------------------------------------------------------------------------
@@ -651,7 +690,9 @@ class App:
                  batch_vrp_aco: bool = False, batch_vrp_aco_launch=None,
                  batch_aco_iterations: int = 100, batch_aco_ants: int = 64,
                  batch_vrp_ls: bool = False, batch_vrp_ls_launch=None,
-                 batch_ls_starts: int = 64, batch_ls_rounds: int = 1000):
+                 batch_ls_starts: int = 64, batch_ls_rounds: int = 1000,
+                 batch_vrp_lsr: bool = False, batch_vrp_lsr_launch=None,
+                 batch_lsr_starts: int = 64, batch_lsr_rounds: int = 1000):
         self.store = store
         self.devices = list(devices) if devices else [device]
         self.device = self.devices[0]
@@ -700,6 +741,10 @@ class App:
         self.vrp_ls_batcher = VrpLsBatcher(self, batch_window_s, batch_ls_rounds,
                                            batch_ls_starts, launch=batch_vrp_ls_launch) \
             if batch_vrp_ls else None
+        # and those over separator tours vrp_batch_lsr launches
+        self.vrp_lsr_batcher = VrpLsrBatcher(self, batch_window_s, batch_lsr_rounds,
+                                             batch_lsr_starts, launch=batch_vrp_lsr_launch) \
+            if batch_vrp_lsr else None
 
     def _scheduled(self, problem, algorithm, params, knobs, locations, durations):
         """Run the solve on a device: all of them (in order, as an island
@@ -800,9 +845,23 @@ class App:
                                 params["ignored_customers"], params["completed_customers"])
         return ci if self.vrp_ls_batcher.accepts(ci) else None
 
+    def _batched_vrp_lsr(self, problem, algorithm, params, knobs, locations, durations):
+        """The compact instance when this request rides the batcher of the
+        local search over separator tours, else None: the flag is on, the
+        route is vrp / lsr, the request names no inline knob of its own and it
+        is inside the batcher's domain (outside it the unbatched path raises
+        the domain's message)."""
+        if self.vrp_lsr_batcher is None or (problem, algorithm) != ("vrp", "lsr") or \
+                knobs.get("inline"):
+            return None
+        from . import solver
+        ci = solver.compact_vrp(durations, locations, params["capacities"], params["start_times"],
+                                params["ignored_customers"], params["completed_customers"])
+        return ci if self.vrp_lsr_batcher.accepts(ci) else None
+
     def _batched_vrp(self, problem, algorithm, params, knobs, locations, durations):
-        """A thunk that solves this request on the VRP SA, GA, ACO or
-        local-search batcher, else None."""
+        """A thunk that solves this request on the VRP SA, GA, ACO or one of
+        the local-search batchers, else None."""
         objective = knobs.get("objective", "sum")
         vci = self._batched_vrp_sa(problem, algorithm, params, knobs, locations, durations)
         if vci is not None:
@@ -816,6 +875,9 @@ class App:
         lci = self._batched_vrp_ls(problem, algorithm, params, knobs, locations, durations)
         if lci is not None:
             return lambda: self.vrp_ls_batcher.solve(lci, objective)
+        rci = self._batched_vrp_lsr(problem, algorithm, params, knobs, locations, durations)
+        if rci is not None:
+            return lambda: self.vrp_lsr_batcher.solve(rci, objective)
         return None
 
     def _exact_batcher(self, problem, algorithm):
@@ -1166,6 +1228,19 @@ def main(argv=None):
     ap.add_argument("--batch-ls-rounds", type=_int_in(0, solver.BATCH_LS_MAX_ROUNDS), default=1000,
                     help="applied moves a descent of a vrp_batch_ls launch may take, 0..1000 "
                          "(solver.BATCH_LS_MAX_ROUNDS)")
+    ap.add_argument("--batch-vrp-lsr", action="store_true",
+                    help="coalesce concurrent small-fleet VRP requests of the local search over "
+                         "separator tours (/solve/vrp/lsr, static or hour-indexed matrix, 1..64 "
+                         "vehicles, an instance that fits the LDS) into vrp_batch_lsr launches of "
+                         "--batch-lsr-starts starts and at most --batch-lsr-rounds rounds a "
+                         "descent; the answer depends on the request alone, not on the batch it "
+                         "rode in")
+    ap.add_argument("--batch-lsr-starts", type=_int_in(1, solver.BATCH_LSR_MAX_STARTS), default=64,
+                    help="starts of a vrp_batch_lsr launch, 1..1024 (solver.BATCH_LSR_MAX_STARTS)")
+    ap.add_argument("--batch-lsr-rounds", type=_int_in(0, solver.BATCH_LSR_MAX_ROUNDS),
+                    default=1000,
+                    help="applied moves a descent of a vrp_batch_lsr launch may take, 0..1000 "
+                         "(solver.BATCH_LSR_MAX_ROUNDS)")
     ap.add_argument("--batch-window-ms", type=float, default=5.0)
     ap.add_argument("--batch-steps", type=int, default=2000)
     ap.add_argument("--workers", type=int, default=0,
@@ -1208,7 +1283,9 @@ def main(argv=None):
               batch_vrp_ga=args.batch_vrp_ga, batch_vrp_aco=args.batch_vrp_aco,
               batch_aco_iterations=args.batch_aco_iterations, batch_aco_ants=args.batch_aco_ants,
               batch_vrp_ls=args.batch_vrp_ls, batch_ls_starts=args.batch_ls_starts,
-              batch_ls_rounds=args.batch_ls_rounds)
+              batch_ls_rounds=args.batch_ls_rounds,
+              batch_vrp_lsr=args.batch_vrp_lsr, batch_lsr_starts=args.batch_lsr_starts,
+              batch_lsr_rounds=args.batch_lsr_rounds)
     srv = serve(app, args.host, args.port)
     print(f"vrpms_amd service on http://{args.host}:{args.port}/api", flush=True)
     try:

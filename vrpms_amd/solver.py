@@ -39,7 +39,7 @@ import numpy as np
 from . import runners
 from .core import CVRP, OBJ_MAX, OBJ_SUM, TSP, Context
 
-ALGORITHMS = ("bf", "ga", "sa", "aco", "dp", "sp", "tdp", "tdsp", "ls")
+ALGORITHMS = ("bf", "ga", "sa", "aco", "dp", "sp", "tdp", "tdsp", "ls", "lsr")
 # the exact algorithms with kernels of their own: one device, no island model
 # (the exhaustive "bf" shares that with them)
 EXACT_ALGORITHMS = ("dp", "sp", "tdp", "tdsp")
@@ -143,6 +143,15 @@ BATCH_ACO_LDS_BYTES = BATCH_SA_LDS_BYTES
 BATCH_LS_MAX_STARTS = 1024
 BATCH_LS_MAX_ROUNDS = 1000
 BATCH_LS_LDS_BYTES = BATCH_SA_LDS_BYTES
+# batched VRP multi-start local search over separator tours (A26): A25's descent
+# on A22's tours of n + K - 1 tokens, two per wavefront
+# (vrpms_vrp_batch_lsr_lds gives the bytes for (N, K, H, wide), never more than
+# A22's), so the domain contains A22's; DESIGN.md §4.3q has the largest N per
+# (H, wide).  As for A25, more than BATCH_LSR_MAX_STARTS starts or
+# BATCH_LSR_MAX_ROUNDS rounds is an error, not another path
+BATCH_LSR_MAX_STARTS = 1024
+BATCH_LSR_MAX_ROUNDS = 1000
+BATCH_LSR_LDS_BYTES = BATCH_SA_LDS_BYTES
 # SA on tours of more than SA_WINDOW_MIN_N customers samples A11 windowed
 # moves (second position within SA_WINDOW of the first)
 SA_WINDOW, SA_WINDOW_MIN_N = 32, 150
@@ -532,6 +541,10 @@ def solve_tsp(algorithm: str, durations, customers, start_node, start_time=0, *,
         raise ValueError('ls solves the VRP only (a multi-start local search over the greedy '
                          'split of a giant tour); use solve_vrp("ls") with one vehicle, or sa, '
                          'ga or aco for the TSP')
+    if algorithm == "lsr":
+        raise ValueError('lsr solves the VRP only (a multi-start local search over giant tours '
+                         'with route separators); use solve_vrp("lsr") with one vehicle, or sa, '
+                         'ga or aco for the TSP')
     if algorithm == "dp":
         ci = compact_tsp(durations, customers, start_node, start_time)
         _check_dp(ci)
@@ -573,7 +586,11 @@ def solve_vrp(algorithm: str, durations, locations, capacities, start_times,
     vrp_batch_ls launch on the first of `devices`: solve_vrp_ls_batch's answer
     for the request.  It ignores `time_limit`; its domain (the instance has to
     fit the LDS: batch_ls_message) is checked before any device or remote is
-    touched."""
+    touched.  "lsr" (spec A26: the same descent on giant tours with K - 1
+    route separators, started from first-fit packed tours; the same knobs,
+    limits BATCH_LSR_MAX_STARTS and BATCH_LSR_MAX_ROUNDS) answers likewise with
+    a one-request vrp_batch_lsr launch: solve_vrp_lsr_batch's answer for the
+    request, its domain batch_lsr_message's."""
     if algorithm == "dp":
         raise ValueError("dp solves the TSP only (the greedy split of a giant tour does not "
                          "decompose over subsets); use bf, sa, ga or aco for the VRP")
@@ -598,6 +615,14 @@ def solve_vrp(algorithm: str, durations, locations, capacities, start_times,
         ls_starts = 64 if knobs.get("starts") is None else int(knobs["starts"])
         ls_rounds = 1000 if knobs.get("rounds") is None else int(knobs["rounds"])
         _check_ls(ci, ls_starts, ls_rounds)
+    if algorithm == "lsr":
+        if objective not in ("sum", "max"):
+            raise ValueError("objective must be 'sum' or 'max'")
+        ci = compact_vrp(durations, locations, capacities, start_times, ignored_customers,
+                         completed_customers)
+        ls_starts = 64 if knobs.get("starts") is None else int(knobs["starts"])
+        ls_rounds = 1000 if knobs.get("rounds") is None else int(knobs["rounds"])
+        _check_lsr(ci, ls_starts, ls_rounds)
     rem = _remote()
     if rem is not None:
         out = rem.solve_vrp(algorithm, durations, locations, capacities, start_times,
@@ -614,6 +639,12 @@ def solve_vrp(algorithm: str, durations, locations, capacities, start_times,
             return sa_result(ci, [], [], [0] * len(ci.capacities), with_unvisited)
         rows = batch_ls_launch(context(devices[0] if devices else device), [ci], ls_starts,
                                ls_rounds, seed, objective)
+        return sa_result(ci, rows[0][0], rows[1][0], rows[2][0], with_unvisited)
+    if algorithm == "lsr":         # a one-request vrp_batch_lsr launch on one device
+        if ci.n == 0:
+            return sa_result(ci, [], [], [0] * len(ci.capacities), with_unvisited)
+        rows = batch_lsr_launch(context(devices[0] if devices else device), [ci], ls_starts,
+                                ls_rounds, seed, objective)
         return sa_result(ci, rows[0][0], rows[1][0], rows[2][0], with_unvisited)
     if ci is None:
         ci = compact_vrp(durations, locations, capacities, start_times, ignored_customers,
@@ -1536,6 +1567,155 @@ def solve_vrp_ls_batch(requests, *, starts: int = 64, rounds: int = 1000, seed: 
         ctx = context(device)
         for xs in groups.values():
             rows = batch_ls_launch(ctx, [cis[x] for x in xs], starts, rounds, seed, objective)
+            for x, tour, veh, durs in zip(xs, *rows):
+                out[x] = sa_result(cis[x], tour, veh, durs, with_unvisited)
+    return out
+
+
+# ---------------------------------------------------------------------------
+# batched VRP multi-start local search over separator tours (A26): small-fleet
+# requests share launches
+# ---------------------------------------------------------------------------
+def batch_lsr_key(ci: CompactInstance, starts: int, rounds: int):
+    """What the instances of one vrp_batch_lsr launch share (next to the
+    objective and the seed): (N, K, H, wide, starts, rounds)."""
+    return batch_sa_key(ci) + (int(starts), int(rounds))
+
+
+def batch_lsr_message(ci: CompactInstance, starts: int, rounds: int):
+    """The limit of A26's domain this request fails -> its message, or None:
+    a CVRP of at least one customer and at most 65534, 1..64 vehicles, a static
+    or 24-slice matrix, 1 <= starts <= BATCH_LSR_MAX_STARTS, 0 <= rounds <=
+    BATCH_LSR_MAX_ROUNDS, at most 65535 tokens (customers and K - 1 separators),
+    and an instance that fits BATCH_LSR_LDS_BYTES together with its eight tours
+    of tokens (vrpms_vrp_batch_lsr_lds; uint16 cells unless an entry is above
+    65535).  Needs the library, no GPU."""
+    from .core import vrp_batch_lsr_lds
+    if ci.problem != CVRP:
+        return 'lsr solves the VRP only'
+    if not 1 <= int(starts) <= BATCH_LSR_MAX_STARTS:
+        return f"lsr (local search) takes 1..{BATCH_LSR_MAX_STARTS} starts ({starts} given)"
+    if not 0 <= int(rounds) <= BATCH_LSR_MAX_ROUNDS:
+        return f"lsr (local search) takes 0..{BATCH_LSR_MAX_ROUNDS} rounds ({rounds} given)"
+    if ci.n < 1:
+        return "lsr (local search) needs at least one customer"
+    if ci.N > 65535:
+        return f"lsr (local search) supports at most 65534 customers ({ci.n} given)"
+    N, K, H, wide = batch_sa_key(ci)
+    if not 1 <= K <= BATCH_SA_MAX_VEHICLES:
+        return (f"lsr (local search) supports 1..{BATCH_SA_MAX_VEHICLES} vehicles "
+                f"({K} given)")
+    if H not in (1, 24):
+        return f"lsr (local search) needs a static or 24-slice duration matrix ({H} slices given)"
+    if N + K - 2 > 65535:
+        return f"lsr (local search) supports at most 65535 tokens ({N + K - 2} given)"
+    need = vrp_batch_lsr_lds(N, K, H, wide)
+    if need > BATCH_LSR_LDS_BYTES:
+        return (f"lsr (local search) keeps the instance in LDS: {ci.n} customers, {K} vehicles and "
+                f"{H} hour slice(s) of {'int32' if wide else 'uint16'} cells need {need} bytes; "
+                f"the limit is {BATCH_LSR_LDS_BYTES} bytes")
+    return None
+
+
+def batch_lsr_fits(ci: CompactInstance, starts: int, rounds: int) -> bool:
+    """The request is inside A26's domain (batch_lsr_message names no limit).
+    Needs the library, no GPU."""
+    return batch_lsr_message(ci, starts, rounds) is None
+
+
+def _check_lsr(ci: CompactInstance, starts, rounds):
+    """A26's domain and the int32 guards, checked on the host before any device
+    or remote is touched.  No customer is solve_vrp's trivial answer."""
+    if ci.problem == CVRP and ci.n == 0 and 1 <= int(starts) <= BATCH_LSR_MAX_STARTS and \
+            0 <= int(rounds) <= BATCH_LSR_MAX_ROUNDS:
+        return
+    msg = batch_lsr_message(ci, starts, rounds) or batch_guard_message(ci)
+    if msg is not None:
+        raise ValueError(msg)
+
+
+def batch_lsr_launch(ctx: Context, cis, starts: int, rounds: int, seed: int,
+                     objective: str = "sum"):
+    """One upload and one vrp_batch_lsr launch for compact instances of one
+    batch_lsr_key (each passed batch_guard_message and batch_lsr_fits) ->
+    (tours, veh, durs): per instance the n + K - 1 tokens of the best end tour
+    (0 a separator), each token's vehicle (-1 unvisited, -2 a separator) and
+    the K route durations."""
+    import torch
+    mats, demand, caps = _stage(ctx, cis, hours=True)
+    st = torch.from_numpy(np.array([ci.start_times for ci in cis], dtype=np.int32)).to(ctx.dev)
+    tours, keys, durs, veh, _ = ctx.vrp_batch_lsr(mats, demand, caps, st,
+                                                  OBJ_MAX if objective == "max" else OBJ_SUM,
+                                                  int(starts), int(rounds), seed,
+                                                  wide=batch_sa_wide(cis[0]))
+    if (keys == -1).any().item():
+        raise RuntimeError("vrp_batch_lsr: a request was outside the launch's contract")
+    return tours.cpu().tolist(), veh.cpu().tolist(), durs.cpu().tolist()
+
+
+def solve_vrp_lsr_batch(requests, *, starts: int = 64, rounds: int = 1000, seed: int = 0,
+                        objective: str = "sum", with_unvisited: bool = False,
+                        device: int = 0) -> list:
+    """A multi-start local search over separator tours for many small-fleet
+    VRP requests, the requests sharing launches (spec A26): one workgroup per
+    request, its whole instance in LDS, `starts` steepest descents over swap,
+    2-opt and relocate on giant tours with K - 1 route separators, from random
+    orders packed first-fit into the K routes, each stopped at a local optimum
+    or after `rounds` applied moves; the least (key, start) end tour is the
+    answer.
+    `requests`: solve_vrp_batch's (durations, locations, capacities,
+    start_times[, ignored_customers, completed_customers]) tuples, or dicts
+    with those keys -> one solve_vrp slot dict per request.
+
+    It is deterministic per request: the dict depends on the request,
+    `starts`, `rounds`, `seed` and `objective` alone, not on the other requests
+    of the call or on its place among them, and is solve_vrp("lsr", starts=,
+    rounds=)'s.
+
+    Every request is compacted and passed through batch_guard_message and the
+    domain (batch_lsr_message) on the host before any device is touched.  There
+    is no unbatched local search, so a request outside the domain raises
+    ValueError("request {x}: ...") naming the limit that failed, as a bad one
+    does.  With no local GPU each request goes to solve_vrp("lsr") on the GPU
+    box.  The requests are grouped by (N, K, H, wide), one upload and one
+    vrp_batch_lsr launch per group, and their dicts are built on the host from
+    the tokens, their vehicles and the route durations; no customer has
+    solve_vrp's trivial answer."""
+    if objective not in ("sum", "max"):
+        raise ValueError("objective must be 'sum' or 'max'")
+    if not 1 <= int(starts) <= BATCH_LSR_MAX_STARTS:
+        raise ValueError(f"starts must be in 1..{BATCH_LSR_MAX_STARTS} ({starts} given)")
+    if not 0 <= int(rounds) <= BATCH_LSR_MAX_ROUNDS:
+        raise ValueError(f"rounds must be in 0..{BATCH_LSR_MAX_ROUNDS} ({rounds} given)")
+    reqs, cis = [], []
+    for x, r in enumerate(requests):
+        try:
+            r, _ = _sp_request(r)
+            ci = compact_vrp(*r)
+            msg = batch_guard_message(ci)
+            if msg is None and ci.n:
+                msg = batch_lsr_message(ci, starts, rounds)
+            if msg is not None:
+                raise ValueError(msg)
+        except ValueError as e:
+            raise ValueError(f"request {x}: {e}") from None
+        reqs.append(r)
+        cis.append(ci)
+    shared = dict(seed=seed, objective=objective, with_unvisited=with_unvisited,
+                  starts=int(starts), rounds=int(rounds))
+    if _remote() is not None:      # no local GPU: the GPU box answers each request
+        return [solve_vrp("lsr", *r, **shared) for r in reqs]
+    out = [None] * len(cis)
+    groups: dict = {}
+    for x, ci in enumerate(cis):
+        if ci.n == 0:
+            out[x] = sa_result(ci, [], [], [0] * len(ci.capacities), with_unvisited)
+        else:
+            groups.setdefault(batch_lsr_key(ci, starts, rounds), []).append(x)
+    if groups:
+        ctx = context(device)
+        for xs in groups.values():
+            rows = batch_lsr_launch(ctx, [cis[x] for x in xs], starts, rounds, seed, objective)
             for x, tour, veh, durs in zip(xs, *rows):
                 out[x] = sa_result(cis[x], tour, veh, durs, with_unvisited)
     return out
