@@ -127,6 +127,29 @@ def vrp_batch_lsr_lds(N: int, K: int, H: int, wide) -> int:
     return int(nbytes.value)
 
 
+def vrp_batch_lsr_spread_lds(N: int, K: int, H: int, wide) -> int:
+    """vrpms_vrp_batch_lsr_spread_lds: the dynamic-LDS bytes of either launch
+    of vrp_batch_lsr_spread for N nodes, K vehicles, H hour slices (1 or 24)
+    and a uint16 (`wide` false) or int32 (`wide` true) matrix; never more than
+    vrp_batch_lsr_lds of the same shape.  Host only: needs the library, no
+    GPU."""
+    nbytes = ctypes.c_uint64()
+    check(_lib.load().vrpms_vrp_batch_lsr_spread_lds(int(N), int(K), int(H), int(wide),
+                                                     ctypes.byref(nbytes)))
+    return int(nbytes.value)
+
+
+def vrp_batch_lsr_spread_work(R: int, N: int, K: int, G: int) -> int:
+    """vrpms_vrp_batch_lsr_spread_work: the workspace bytes of a
+    vrp_batch_lsr_spread launch of R requests at G workgroups each,
+    R * G * (16 + 2 * align8(N + K - 2)).  Host only: needs the library, no
+    GPU."""
+    nbytes = ctypes.c_uint64()
+    check(_lib.load().vrpms_vrp_batch_lsr_spread_work(int(R), int(N), int(K), int(G),
+                                                      ctypes.byref(nbytes)))
+    return int(nbytes.value)
+
+
 def tdp_words(start: int, horizon: int) -> int:
     """Hour words of one A16 row: the words from the start's hour to the one
     of start + horizon."""
@@ -175,6 +198,11 @@ class Context:
 
     def stream(self):
         return ctypes.c_void_p(_torch().cuda.current_stream(self.dev).cuda_stream)
+
+    @property
+    def cus(self) -> int:
+        """The device's compute units."""
+        return int(_torch().cuda.get_device_properties(self.dev).multi_processor_count)
 
     # -- instance -----------------------------------------------------------
     def set_instance(self, problem: int, durations, demand=None, capacities=None,
@@ -907,6 +935,44 @@ class Context:
                                            int(seed) & (2**64 - 1), tours.data_ptr(),
                                            keys.data_ptr(), durs.data_ptr(), veh.data_ptr(),
                                            info.data_ptr(), self.stream()))
+        return tours, keys, durs, veh, info
+
+    def vrp_batch_lsr_spread(self, mats, demand, caps, starts, objective: int, nstarts: int,
+                             rounds: int, seed: int, groups: int, wide=None):
+        """vrp_batch_lsr by another mapping: the same
+        arguments and the identical five tensors, but a request's `nstarts`
+        starts are spread over min(`groups`, nstarts) workgroups (`groups` in
+        1..65535) whose 256 threads each price one round of one tour together,
+        and a second launch selects the least (key, start) per request.  For
+        few requests that occupies R * groups workgroups instead of R.  The
+        workspace (vrp_batch_lsr_spread_work) is allocated here, from torch's
+        caching allocator, which keeps it alive for the stream's queued work.
+        Asynchronous on the current stream."""
+        torch = _torch()
+        mats = self._batch_mats(torch, mats, 4)
+        R, H, N, _ = mats.shape
+        self._batch_rows(torch, demand, caps, R, N)
+        K = caps.shape[1]
+        if starts.device != self.dev or starts.shape != caps.shape or starts.dtype != torch.int32 \
+                or not starts.is_contiguous():
+            raise ValueError(f"starts must be a contiguous int32 [R][K] tensor on {self.dev}")
+        if wide is None:
+            wide = bool(R) and int(mats.max().item()) > 65535
+        L = N - 1 + K - 1
+        G = int(groups)
+        work_bytes = vrp_batch_lsr_spread_work(R, N, K, max(1, min(G, int(nstarts)))) \
+            if R and 1 <= G <= 65535 else 0
+        work = torch.empty(max(work_bytes // 8, 1), dtype=torch.int64, device=self.dev)
+        tours = torch.empty((R, max(L, 1)), dtype=torch.int16, device=self.dev)
+        keys = torch.empty(R, dtype=torch.int64, device=self.dev)
+        durs = torch.empty((R, max(K, 1)), dtype=torch.int32, device=self.dev)
+        veh = torch.empty((R, max(L, 1)), dtype=torch.int8, device=self.dev)
+        info = torch.empty((R, 2), dtype=torch.int32, device=self.dev)
+        check(self.lib.vrpms_vrp_batch_lsr_spread(
+            self._ctx, mats.data_ptr(), demand.data_ptr(), caps.data_ptr(), starts.data_ptr(), R, N,
+            K, H, int(objective), int(bool(wide)), int(nstarts), int(rounds),
+            int(seed) & (2**64 - 1), G, work.data_ptr(), work_bytes, tours.data_ptr(),
+            keys.data_ptr(), durs.data_ptr(), veh.data_ptr(), info.data_ptr(), self.stream()))
         return tours, keys, durs, veh, info
 
     def set_batch_dp_team(self, T: int):

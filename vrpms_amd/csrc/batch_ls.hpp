@@ -1,8 +1,10 @@
 // What the two batched local searches share (vrp_batch_ls.hip, A25, on tours of
 // n customers; vrp_batch_lsr.hip, A26, on tours of n + K - 1 tokens): the order
 // of a round's moves, a lane's share of them, the Philox Fisher-Yates start,
-// the in-place move, the descent's round loop and the waves' records.  `n`
-// below is the number of positions of the tour the descent works on.
+// the in-place move, the descent's round loop and the waves' records, and for
+// vrp_batch_lsr_spread.hip (A26 with 256 threads on one descent) the thread's
+// share and the workgroup's round loop.  `n` below is the number of positions
+// of the tour the descent works on.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -179,6 +181,81 @@ VRPMS_DEV uint64_t batch_ls_descend(const Mat& D, const SplitParams& sp, uint16_
     mb.typ = (uint32_t)wave_bcast((int)lm.typ, bl);
     mb.i = wave_bcast(lm.i, bl);
     mb.j = wave_bcast(lm.j, bl);
+    batch_ls_apply(A, mb, lane);
+    ck = k;
+  }
+  return ck;
+}
+
+// The 256-thread forms: one descent per workgroup at a time (vrp_batch_lsr_spread.hip).
+//
+// the thread's share of a round: the ids [t per, t per + cnt) from move m0 on,
+// per = ceil(2 n (n - 1) / 256), t = 64 wave + lane; n < 2 has no moves
+VRPMS_DEV BatchLsShare batch_ls_share_wg(int n, int t) {
+  const int total = 2 * n * (n - 1), per = (total + 255) >> 8;
+  const int id0 = t * per;
+  BatchLsShare sh{Move{kMoveSwap, 0, 1}, max(0, min(per, total - id0))};
+  if (sh.cnt > 0) sh.m0 = batch_ls_move(id0, n);
+  return sh;
+}
+
+// a wavefront's least (key, typ, i, j) of a round, as the four exchange it
+struct BatchLsRec {   // 16 bytes
+  uint64_t key;
+  uint32_t typ;
+  uint16_t i, j;      // positions are below 65535
+};
+
+// One steepest descent of the whole workgroup (four wavefronts, `sh` from
+// batch_ls_share_wg) on one tour, n >= 2 positions, key ck: batch_ls_descend's
+// rounds, the thread pricing its share.  Every wavefront holds its own copy A
+// of the tour -- the four are equal on entry and stay equal, since each applies
+// the same move -- so a round has one barrier: the wavefronts' records meet in
+// rec[parity][wave], and each wavefront takes the least (key, wave), which is
+// the least (key, typ, i, j) because the id ranges ascend with the thread.
+// `parity` alternates with every barrier of the kernel, over all its descents:
+// a wavefront writes rec[p] for the round after next only past the next
+// round's barrier, which the slowest reaches after it has read rec[p].  ck,
+// `rounds`, the records and so every branch here are the same in all four
+// wavefronts; all of them reach every barrier.  -> the end tour's key.
+template <typename Mat>
+VRPMS_DEV uint64_t batch_ls_descend_wg(const Mat& D, const SplitParams& sp, uint16_t* A, int n,
+                                       uint64_t ck, int rounds, const BatchLsShare& sh, int wave,
+                                       int lane, BatchLsRec* rec, int& parity, int& capped) {
+  for (int applied = 0;; ++applied) {
+    if (applied >= rounds) {   // stopped unproven
+      ++capped;
+      break;
+    }
+    Move m = sh.m0, lm = sh.m0;
+    uint64_t lk = ~0ull;
+    for (int c = 0; c < sh.cnt; ++c) {
+      const MoveMap mm = move_map(m);
+      const uint64_t k =
+          eval_tour<true>(D, sp, [&](int q) { return (uint32_t)A[map_src(mm, q)]; }, n).key;
+      if (k < lk) {
+        lk = k;
+        lm = m;
+      }
+      batch_ls_next(m, n);
+    }
+    int bl;
+    const uint64_t wk = wave_argmin_lane(lk, bl);
+    BatchLsRec* mine = rec + 4 * parity;
+    if (lane == bl)
+      mine[wave] = BatchLsRec{wk, lm.typ, (uint16_t)lm.i, (uint16_t)lm.j};
+    __syncthreads();
+    int bw = 0;
+    for (int w = 1; w < 4; ++w)
+      if (mine[w].key < mine[bw].key) bw = w;   // the lowest wavefront among equal keys
+    const BatchLsRec best = mine[bw];
+    parity ^= 1;
+    const uint64_t k = readlane_u64(best.key, 0);
+    if (!(k < ck)) break;   // a local optimum
+    Move mb;
+    mb.typ = (uint32_t)__builtin_amdgcn_readfirstlane((int)best.typ);
+    mb.i = __builtin_amdgcn_readfirstlane((int)best.i);
+    mb.j = __builtin_amdgcn_readfirstlane((int)best.j);
     batch_ls_apply(A, mb, lane);
     ck = k;
   }

@@ -1,0 +1,290 @@
+// A second mapping of the local search over separator tours (DESIGN.md §2 A26,
+// §4.3r): the starts, the rounds and the answer are vrp_batch_lsr.hip's, bit
+// for bit -- the descent of start s depends on (request, seed, s, rounds,
+// objective) alone and the answer is the least (key, s) over the end tours --
+// but a request's S starts are spread over G workgroups, and a workgroup's 256
+// threads price one round of ONE tour instead of four wavefronts descending
+// four starts.  For a lone request, or a few, that puts R G workgroups on the
+// device instead of R.
+//
+//   descents   vrp_batch_lsr_spread_kernel, grid R x G, 256 threads.  Workgroup
+//              g of request r stages the request into LDS (batch_stage.hpp) and
+//              descends the starts g, g + G, ... one after the other.  Every
+//              wavefront builds the start in its own row -- the shuffle and the
+//              in-place first fit are deterministic, so the four copies are
+//              equal with no barrier -- and batch_ls_descend_wg (batch_ls.hpp)
+//              runs the rounds: thread t prices the ids [t per, (t + 1) per),
+//              per = ceil(2 L (L - 1) / 256), the four wavefronts' least
+//              records meet in LDS behind the round's one barrier, and each
+//              wavefront applies the winning move to its own copy.  Whenever an
+//              end tour's key is below the workgroup's best, wavefront 0 writes
+//              it to the workgroup's record of the workspace; after the last
+//              start thread 0 writes (key, s, capped count) in front of it.
+//   selection  vrp_batch_lsr_select_kernel, the next launch on the stream, one
+//              workgroup per request: it stages the request again (the entry
+//              check with it: a refusal row is vrp_batch_lsr's), takes the
+//              least (key, s) of the G records and the sum of their capped
+//              counts, walks that tour once more (batch_final_walk) and writes
+//              tours, keys, durs, veh and info as vrp_batch_lsr_kernel does.
+//
+// The kernel boundary orders the records; there is no counter of arrived
+// workgroups and no hand-off inside a kernel.
+//
+// Workspace: R G records of 16 + 2 align8(L) bytes: uint64 key, int32 s, int32
+// capped count, L uint16 tokens (vrpms_vrp_batch_lsr_spread_work).
+//
+// LDS of either kernel (vrpms_vrp_batch_lsr_spread_lds), never more than
+// vrpms_vrp_batch_lsr_lds of the same shape, as a tour has at least 8 padded
+// tokens:
+//   align16(H N N (wide ? 4 : 2))            the matrix
+// + 4 align4(N) + 2 * 4 align4(K)            demand, capacities, start times (int32)
+// + 4 * 2 align8(L)                          4 wavefronts' copies of the current tour
+// + 2 * 4 * 16                               the wavefronts' round records, by barrier parity
+// (the best end tour lives in the workspace, not in LDS; the selection uses two
+// of the tour rows for the answer and its vehicles).
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "batch_ls.hpp"
+#include "batch_stage.hpp"
+#include "common.hpp"
+#include "ctx.hpp"
+#include "staging.hpp"
+#include "tour.hpp"
+#include "vrp_batch_lsr.hpp"
+
+namespace vrpms {
+
+constexpr int kBatchLsrMaxG = 65535;
+
+struct VrpBatchLsrSpreadArgs {
+  VrpBatchLsrArgs a;
+  int G;                  // workgroups per request, 1 <= G <= S
+  unsigned char* work;    // [R][G] records of rec_bytes
+  uint32_t rec_bytes;     // 16 + 2 align8(L)
+};
+
+inline size_t batch_lsr_spread_lds(int N, int K, int H, int wide) {
+  const BatchLsrLds l = batch_lsr_lds(N, K, H, wide);
+  return l.mat + l.dem + 2 * l.row + 4 * l.tour + 2 * 4 * sizeof(BatchLsRec);
+}
+
+inline uint64_t batch_lsr_spread_rec_bytes(int N, int K) {
+  return 16 + 2 * (((uint64_t)N - 1 + K - 1 + 7) & ~(uint64_t)7);
+}
+
+// the LDS carve both kernels share
+template <typename MatT, int HM>
+struct BatchLsrSpreadCarve {
+  MatT* M;
+  int32_t *dem, *cap, *start;
+  uint16_t* tours;    // [4][tpad]
+  BatchLsRec* rec;    // [2][4]
+  uint32_t cells, tpad;
+  VRPMS_DEV BatchLsrSpreadCarve(unsigned char* mem, int N, int K, int L) {
+    cells = (uint32_t)HM * (uint32_t)N * (uint32_t)N;
+    const uint32_t mat_bytes = (cells * (uint32_t)sizeof(MatT) + 15u) & ~15u;
+    const uint32_t dem_words = ((uint32_t)N + 3u) & ~3u, row_words = ((uint32_t)K + 3u) & ~3u;
+    tpad = ((uint32_t)L + 7u) & ~7u;
+    M = reinterpret_cast<MatT*>(mem);
+    dem = reinterpret_cast<int32_t*>(mem + mat_bytes);
+    cap = dem + dem_words;
+    start = cap + row_words;
+    tours = reinterpret_cast<uint16_t*>(start + row_words);
+    rec = reinterpret_cast<BatchLsRec*>(tours + 4 * tpad);
+  }
+};
+
+template <typename MatT, int HM>
+__global__ __launch_bounds__(256) void vrp_batch_lsr_spread_kernel(VrpBatchLsrSpreadArgs p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char batch_lsr_spread_lds_mem[];
+  const VrpBatchLsrArgs& a = p.a;
+  const int N = a.N, n = N - 1, K = a.K, L = n + K - 1, G = p.G;
+  const int64_t r = blockIdx.x / (uint32_t)G;
+  const int g = (int)(blockIdx.x % (uint32_t)G);
+  const BatchLsrSpreadCarve<MatT, HM> c(batch_lsr_spread_lds_mem, N, K, L);
+
+  // stage and check the request; the selection kernel writes the refusal row.
+  // The verdict goes through a word of the round records, free until then
+  if (batch_stage_request(a.mats, a.demand, a.cap, a.start, r, c.cells, N, K, c.M, c.dem, c.cap, c.start,
+                          reinterpret_cast<uint32_t*>(c.rec)))
+    return;
+
+  const int wave = (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = lane_id();
+  uint16_t* A = c.tours + wave * c.tpad;   // the wavefront's copy of the current tour
+  const MatView<MatT, HM> D{c.M, (uint32_t)N, (uint32_t)N * (uint32_t)N, HM};
+  const SplitParams sp{c.dem, c.cap, c.start, K, a.objective};
+  unsigned char* mine = p.work + (r * G + g) * (int64_t)p.rec_bytes;
+  uint16_t* wtour = reinterpret_cast<uint16_t*>(mine + 16);
+
+  const BatchLsShare sh = batch_ls_share_wg(L, (int)threadIdx.x);   // the thread's share of a round
+
+  uint64_t bk = ~0ull;
+  int bs = 0x7fffffff, capped = 0, parity = 0;
+  for (int s = g; s < a.S; s += G) {
+    batch_lsr_start(A, c.dem, c.cap, n, K, s, a.seed_lo, a.seed_hi, lane);
+    uint64_t ck = readlane_u64(eval_tour<true>(D, sp, [&](int q) { return (uint32_t)A[q]; }, L).key, 0);
+    if (L >= 2)
+      ck = batch_ls_descend_wg(D, sp, A, L, ck, a.rounds, sh, wave, lane, c.rec, parity, capped);
+    if (ck < bk) {   // s rises: the least s among equal keys stays
+      bk = ck;
+      bs = s;
+      if (wave == 0)
+        for (int q = lane; q < L; q += 64) wtour[q] = A[q];
+    }
+  }
+  if (threadIdx.x == 0) *reinterpret_cast<BatchLsWave*>(mine) = BatchLsWave{bk, bs, capped};
+}
+
+template <typename MatT, int HM>
+__global__ __launch_bounds__(256) void vrp_batch_lsr_select_kernel(VrpBatchLsrSpreadArgs p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char batch_lsr_select_lds_mem[];
+  const VrpBatchLsrArgs& a = p.a;
+  const int N = a.N, n = N - 1, K = a.K, L = n + K - 1, G = p.G;
+  const int64_t r = blockIdx.x;
+  const BatchLsrSpreadCarve<MatT, HM> c(batch_lsr_select_lds_mem, N, K, L);
+
+  uint16_t* gtour = a.tours + r * L;
+  int8_t* gveh = a.veh + r * L;
+  int32_t* gdurs = a.durs + r * K;
+  if (batch_stage_request(a.mats, a.demand, a.cap, a.start, r, c.cells, N, K, c.M, c.dem, c.cap, c.start,
+                          reinterpret_cast<uint32_t*>(c.rec))) {
+    batch_refuse(gtour, gveh, gdurs, a.keys + r, L, K);
+    if (threadIdx.x == 0) {
+      a.info[2 * r] = -1;
+      a.info[2 * r + 1] = 0;
+    }
+    return;
+  }
+  if (threadIdx.x >= 64) return;   // one wavefront selects and walks
+
+  // the least (key, s) of the request's G records and the sum of their capped
+  // counts: lane l takes the records l, l + 64, ...
+  const int lane = lane_id();
+  const unsigned char* recs = p.work + r * G * (int64_t)p.rec_bytes;
+  uint64_t bk = ~0ull, bs = 0x7fffffffu;
+  int ncap = 0;
+  for (int g = lane; g < G; g += 64) {
+    const BatchLsWave w = *reinterpret_cast<const BatchLsWave*>(recs + (int64_t)g * p.rec_bytes);
+    if (w.key < bk || (w.key == bk && (uint64_t)(uint32_t)w.s < bs)) {
+      bk = w.key;
+      bs = (uint32_t)w.s;
+    }
+    ncap += w.capped;
+  }
+  wave_argmin(bk, bs);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) ncap += __shfl_xor(ncap, off, kWave);
+  bk = readlane_u64(bk, 0);
+  const int s = __builtin_amdgcn_readfirstlane((int)(uint32_t)bs);
+  const int bg = (int)((uint32_t)s % (uint32_t)G);   // workgroup g descended the starts g mod G
+
+  // its tour into LDS, then once more as spec.eval_cvrp walks it: every lane
+  // walks alike, lane k keeps route k's duration, lane 0 notes the vehicles
+  uint16_t* Best = c.tours;
+  int16_t* V = reinterpret_cast<int16_t*>(c.tours + c.tpad);
+  const uint16_t* wtour = reinterpret_cast<const uint16_t*>(recs + (int64_t)bg * p.rec_bytes + 16);
+  for (int q = lane; q < L; q += 64) Best[q] = wtour[q];
+  wave_sync();
+  const MatView<MatT, HM> D{c.M, (uint32_t)N, (uint32_t)N * (uint32_t)N, HM};
+  const int mydur = batch_final_walk(D, c.dem, c.cap, c.start, K, n, Best, L, V, lane);
+  wave_sync();
+  for (int q = lane; q < L; q += 64) {
+    gtour[q] = Best[q];
+    gveh[q] = (int8_t)V[q];
+  }
+  if (lane < K) gdurs[lane] = mydur;
+  if (lane == 0) {
+    a.keys[r] = bk;
+    a.info[2 * r] = s;
+    a.info[2 * r + 1] = ncap;
+  }
+}
+
+}  // namespace vrpms
+
+using namespace vrpms;
+
+extern "C" int vrpms_vrp_batch_lsr_spread_lds(int32_t N, int32_t K, int32_t H, int32_t wide,
+                                              uint64_t* bytes) {
+  if (!bytes) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_lsr_spread_lds: bytes is NULL");
+  const int rc = batch_lsr_check("vrpms_vrp_batch_lsr_spread_lds", N, K, H, wide);
+  if (rc) return rc;
+  *bytes = batch_lsr_spread_lds(N, K, H, wide);
+  return VRPMS_OK;
+}
+
+extern "C" int vrpms_vrp_batch_lsr_spread_work(int32_t R, int32_t N, int32_t K, int32_t G,
+                                               uint64_t* bytes) {
+  if (!bytes) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_lsr_spread_work: bytes is NULL");
+  if (R < 0) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_lsr_spread_work: R must not be negative");
+  const int rc = batch_lsr_check("vrpms_vrp_batch_lsr_spread_work", N, K, 1, 0);
+  if (rc) return rc;
+  if (G < 1 || G > kBatchLsrMaxG)
+    return fail(VRPMS_EINVAL,
+                "vrpms_vrp_batch_lsr_spread_work: 1 <= G <= 65535 (" + std::to_string(G) + " given)");
+  if ((uint64_t)R * (uint64_t)G > 0x7fffffffull)
+    return fail(VRPMS_EINVAL, "vrpms_vrp_batch_lsr_spread_work: R * G = " +
+                                  std::to_string((uint64_t)R * (uint64_t)G) + " records are above 2^31 - 1");
+  *bytes = (uint64_t)R * (uint64_t)G * batch_lsr_spread_rec_bytes(N, K);   // < 2^31 2^18
+  return VRPMS_OK;
+}
+
+extern "C" int vrpms_vrp_batch_lsr_spread(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_demand,
+                                          const int32_t* d_cap, const int32_t* d_start, int32_t R,
+                                          int32_t N, int32_t K, int32_t H, int32_t objective,
+                                          int32_t wide, int32_t S, int32_t rounds, uint64_t seed,
+                                          int32_t G, void* d_work, uint64_t work_bytes,
+                                          uint16_t* d_tours, uint64_t* d_keys, int32_t* d_durs,
+                                          int8_t* d_veh, int32_t* d_info, void* stream) {
+  const char* who = "vrpms_vrp_batch_lsr_spread";
+  const std::string w(who);
+  if (!ctx) return fail(VRPMS_EINVAL, w + ": ctx is NULL");
+  if (R < 0) return fail(VRPMS_EINVAL, w + ": R must not be negative");
+  const int rc = batch_lsr_check(who, N, K, H, wide);
+  if (rc) return rc;
+  const int rs = batch_lsr_check_search(who, objective, S, rounds);
+  if (rs) return rs;
+  if (G < 1 || G > kBatchLsrMaxG)
+    return fail(VRPMS_EINVAL, w + ": 1 <= G <= 65535 (" + std::to_string(G) + " given)");
+  if (R == 0) return VRPMS_OK;
+  if (!d_mats || !d_demand || !d_cap || !d_start || !d_tours || !d_keys || !d_durs || !d_veh || !d_info)
+    return fail(VRPMS_EINVAL,
+                w + ": NULL matrix/demand/capacity/start/tour/key/duration/vehicle/info buffer");
+  const int Gc = G < S ? G : S;   // a workgroup without a start cannot occur
+  if ((uint64_t)R * (uint64_t)Gc > 0x7fffffffull)
+    return fail(VRPMS_EINVAL, w + ": R * min(G, S) = " + std::to_string((uint64_t)R * (uint64_t)Gc) +
+                                  " workgroups are above 2^31 - 1");
+  const uint64_t rec = batch_lsr_spread_rec_bytes(N, K), need = (uint64_t)R * (uint64_t)Gc * rec;
+  if (!d_work) return fail(VRPMS_EINVAL, w + ": the workspace is NULL");
+  if ((uintptr_t)d_work & 7u) return fail(VRPMS_EINVAL, w + ": the workspace must be 8-byte aligned");
+  if (work_bytes < need)
+    return fail(VRPMS_EINVAL, w + ": the workspace has " + std::to_string(work_bytes) + " bytes, R = " +
+                                  std::to_string(R) + " requests of min(G, S) = " + std::to_string(Gc) +
+                                  " workgroups need " + std::to_string(need));
+  const size_t lds = batch_lsr_spread_lds(N, K, H, wide);
+  if (lds > ctx->max_lds) return batch_lsr_lds_refusal(who, N, K, H, wide, lds, ctx->max_lds);
+  VRPMS_HIP(hipSetDevice(ctx->device));
+  const VrpBatchLsrSpreadArgs p{
+      VrpBatchLsrArgs{d_mats, d_demand, d_cap, d_start, R, N, K, H, objective, S, rounds, (uint32_t)seed,
+                      (uint32_t)(seed >> 32), d_tours, d_keys, d_durs, d_veh, d_info},
+      Gc, static_cast<unsigned char*>(d_work), (uint32_t)rec};
+  void (*descend)(VrpBatchLsrSpreadArgs) =
+      wide ? (H == 24 ? vrp_batch_lsr_spread_kernel<int32_t, 24> : vrp_batch_lsr_spread_kernel<int32_t, 1>)
+           : (H == 24 ? vrp_batch_lsr_spread_kernel<uint16_t, 24> : vrp_batch_lsr_spread_kernel<uint16_t, 1>);
+  void (*select)(VrpBatchLsrSpreadArgs) =
+      wide ? (H == 24 ? vrp_batch_lsr_select_kernel<int32_t, 24> : vrp_batch_lsr_select_kernel<int32_t, 1>)
+           : (H == 24 ? vrp_batch_lsr_select_kernel<uint16_t, 24> : vrp_batch_lsr_select_kernel<uint16_t, 1>);
+  if (lds > 65536) {
+    VRPMS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(descend),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    VRPMS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(select),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  }
+  descend<<<(unsigned)((uint64_t)R * (uint64_t)Gc), 256, lds, (hipStream_t)stream>>>(p);
+  VRPMS_HIP(hipGetLastError());
+  select<<<(unsigned)R, 256, lds, (hipStream_t)stream>>>(p);
+  VRPMS_HIP(hipGetLastError());
+  return VRPMS_OK;
+}

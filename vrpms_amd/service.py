@@ -58,14 +58,15 @@ _COMMON = {
 # in its "knobs" object (vrpms_amd.remote forwards them): name -> type
 INLINE_KNOBS = {"steps": int, "separators": int, "window": int, "chains": int,
                 "window_types": int, "pop": int, "islands": int, "colonies": int, "ants": int,
-                "upper_bound": int, "starts": int, "rounds": int}
+                "upper_bound": int, "starts": int, "rounds": int, "spread": int}
 # their accepted ranges (inclusive): a value from the network outside them is a
 # 400, never an allocation (islands = 10**6 or chains = 2**30 would
 # exhaust device memory while the request holds every device lock)
 KNOB_RANGES = {"steps": (1, 10**8), "separators": (0, 4096), "window": (0, 65535),
                "chains": (1, 1 << 16), "window_types": (0, 7), "pop": (2, 4096),
                "islands": (1, 4096), "colonies": (1, 4096), "ants": (1, 4096),
-               "upper_bound": (0, 2**31 - 1), "starts": (1, 1024), "rounds": (0, 1000)}
+               "upper_bound": (0, 2**31 - 1), "starts": (1, 1024), "rounds": (0, 1000),
+               "spread": (1, 1024)}
 
 
 def check_knob(name, value):
@@ -633,11 +634,14 @@ class VrpLsrBatcher(VrpLsBatcher):
     inline takes the unbatched path.  A batched answer does not depend on the
     batch: it is solver.solve_vrp_lsr_batch([request], starts=, rounds=,
     seed=the app's, objective=)'s, which is also the unbatched route's at the
-    same knobs and seed."""
+    same knobs and seed.  `spread` (None, "auto" or 1..1024) is
+    solver.batch_lsr_launch's: how many workgroups a request's starts are
+    spread over, which changes a launch's time and no answer."""
 
     def __init__(self, app, window_s: float = 0.005, rounds: int = 1000, starts: int = 64,
-                 max_batch: int = 16384, launch=None):
+                 max_batch: int = 16384, launch=None, spread=None):
         from . import solver
+        self.spread = solver.check_lsr_spread(spread)
         if not 1 <= int(starts) <= solver.BATCH_LSR_MAX_STARTS:
             raise ValueError(f"starts must be in 1..{solver.BATCH_LSR_MAX_STARTS} ({starts} given)")
         if not 0 <= int(rounds) <= solver.BATCH_LSR_MAX_ROUNDS:
@@ -658,7 +662,8 @@ class VrpLsrBatcher(VrpLsBatcher):
         dev = self.devices[0] if device is None else device
         with self.app.locks[dev]:
             tours, veh, durs = solver.batch_lsr_launch(solver.context(dev), cis, self.starts,
-                                                       self.rounds, self.app.seed, key[-1])
+                                                       self.rounds, self.app.seed, key[-1],
+                                                       spread=self.spread)
         return tours, list(zip(veh, durs))
 
 
@@ -692,7 +697,8 @@ class App:
                  batch_vrp_ls: bool = False, batch_vrp_ls_launch=None,
                  batch_ls_starts: int = 64, batch_ls_rounds: int = 1000,
                  batch_vrp_lsr: bool = False, batch_vrp_lsr_launch=None,
-                 batch_lsr_starts: int = 64, batch_lsr_rounds: int = 1000):
+                 batch_lsr_starts: int = 64, batch_lsr_rounds: int = 1000,
+                 batch_lsr_spread=None):
         self.store = store
         self.devices = list(devices) if devices else [device]
         self.device = self.devices[0]
@@ -743,7 +749,8 @@ class App:
             if batch_vrp_ls else None
         # and those over separator tours vrp_batch_lsr launches
         self.vrp_lsr_batcher = VrpLsrBatcher(self, batch_window_s, batch_lsr_rounds,
-                                             batch_lsr_starts, launch=batch_vrp_lsr_launch) \
+                                             batch_lsr_starts, launch=batch_vrp_lsr_launch,
+                                             spread=batch_lsr_spread) \
             if batch_vrp_lsr else None
 
     def _scheduled(self, problem, algorithm, params, knobs, locations, durations):
@@ -1160,6 +1167,12 @@ def _int_in(lo: int, hi: int):
     return parse
 
 
+def _lsr_spread(text):
+    """An argparse type: "auto" or an integer in 1..1024 (solver.BATCH_LSR_MAX_SPREAD)."""
+    from . import solver
+    return text if text == "auto" else _int_in(1, solver.BATCH_LSR_MAX_SPREAD)(text)
+
+
 def main(argv=None):
     from . import solver
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
@@ -1241,6 +1254,11 @@ def main(argv=None):
                     default=1000,
                     help="applied moves a descent of a vrp_batch_lsr launch may take, 0..1000 "
                          "(solver.BATCH_LSR_MAX_ROUNDS)")
+    ap.add_argument("--batch-lsr-spread", type=_lsr_spread, default=None, metavar="{auto,N}",
+                    help="spread the starts of every request of a vrp_batch_lsr launch over N "
+                         "workgroups, 1..1024 (solver.BATCH_LSR_MAX_SPREAD), or over as many as "
+                         "keep the device busy (auto: solver.batch_lsr_spread); the answers are "
+                         "the same, a window that caught few requests answers sooner")
     ap.add_argument("--batch-window-ms", type=float, default=5.0)
     ap.add_argument("--batch-steps", type=int, default=2000)
     ap.add_argument("--workers", type=int, default=0,
@@ -1285,7 +1303,7 @@ def main(argv=None):
               batch_vrp_ls=args.batch_vrp_ls, batch_ls_starts=args.batch_ls_starts,
               batch_ls_rounds=args.batch_ls_rounds,
               batch_vrp_lsr=args.batch_vrp_lsr, batch_lsr_starts=args.batch_lsr_starts,
-              batch_lsr_rounds=args.batch_lsr_rounds)
+              batch_lsr_rounds=args.batch_lsr_rounds, batch_lsr_spread=args.batch_lsr_spread)
     srv = serve(app, args.host, args.port)
     print(f"vrpms_amd service on http://{args.host}:{args.port}/api", flush=True)
     try:

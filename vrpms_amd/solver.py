@@ -152,6 +152,9 @@ BATCH_LS_LDS_BYTES = BATCH_SA_LDS_BYTES
 BATCH_LSR_MAX_STARTS = 1024
 BATCH_LSR_MAX_ROUNDS = 1000
 BATCH_LSR_LDS_BYTES = BATCH_SA_LDS_BYTES
+# A26 by the other mapping (vrp_batch_lsr_spread): the workgroups
+# a request's starts may be spread over; the answers do not depend on it
+BATCH_LSR_MAX_SPREAD = 1024
 # SA on tours of more than SA_WINDOW_MIN_N customers samples A11 windowed
 # moves (second position within SA_WINDOW of the first)
 SA_WINDOW, SA_WINDOW_MIN_N = 32, 150
@@ -590,7 +593,9 @@ def solve_vrp(algorithm: str, durations, locations, capacities, start_times,
     route separators, started from first-fit packed tours; the same knobs,
     limits BATCH_LSR_MAX_STARTS and BATCH_LSR_MAX_ROUNDS) answers likewise with
     a one-request vrp_batch_lsr launch: solve_vrp_lsr_batch's answer for the
-    request, its domain batch_lsr_message's."""
+    request, its domain batch_lsr_message's.  Its knob `spread` (None, "auto"
+    or 1..BATCH_LSR_MAX_SPREAD; batch_lsr_launch) spreads the request's starts
+    over that many workgroups: the same answer, sooner for a lone request."""
     if algorithm == "dp":
         raise ValueError("dp solves the TSP only (the greedy split of a giant tour does not "
                          "decompose over subsets); use bf, sa, ga or aco for the VRP")
@@ -622,6 +627,11 @@ def solve_vrp(algorithm: str, durations, locations, capacities, start_times,
                          completed_customers)
         ls_starts = 64 if knobs.get("starts") is None else int(knobs["starts"])
         ls_rounds = 1000 if knobs.get("rounds") is None else int(knobs["rounds"])
+        ls_spread = check_lsr_spread(knobs.get("spread"))
+        if isinstance(ls_spread, int):   # only a number travels to a GPU box as a knob
+            knobs["spread"] = ls_spread
+        else:
+            knobs.pop("spread", None)
         _check_lsr(ci, ls_starts, ls_rounds)
     rem = _remote()
     if rem is not None:
@@ -644,7 +654,7 @@ def solve_vrp(algorithm: str, durations, locations, capacities, start_times,
         if ci.n == 0:
             return sa_result(ci, [], [], [0] * len(ci.capacities), with_unvisited)
         rows = batch_lsr_launch(context(devices[0] if devices else device), [ci], ls_starts,
-                                ls_rounds, seed, objective)
+                                ls_rounds, seed, objective, spread=ls_spread)
         return sa_result(ci, rows[0][0], rows[1][0], rows[2][0], with_unvisited)
     if ci is None:
         ci = compact_vrp(durations, locations, capacities, start_times, ignored_customers,
@@ -1634,20 +1644,54 @@ def _check_lsr(ci: CompactInstance, starts, rounds):
         raise ValueError(msg)
 
 
+def check_lsr_spread(spread):
+    """`spread` as batch_lsr_launch takes it -> None, "auto" or an int in
+    1..BATCH_LSR_MAX_SPREAD; anything else is a ValueError."""
+    if spread is None or (isinstance(spread, str) and spread == "auto"):
+        return spread
+    if isinstance(spread, (int, np.integer)) and not isinstance(spread, bool) and \
+            1 <= int(spread) <= BATCH_LSR_MAX_SPREAD:
+        return int(spread)
+    raise ValueError(f'spread must be None, "auto" or an integer in 1..{BATCH_LSR_MAX_SPREAD} '
+                     f"({spread!r} given)")
+
+
+def batch_lsr_spread(R: int, S: int, cus: int) -> int:
+    """The "auto" policy: the workgroups per request that vrp_batch_lsr_spread
+    gives a launch of R requests of S starts on a device of `cus` compute
+    units, min(S, max(1, 16 cus // R)): up to sixteen workgroups a CU while
+    the requests are few.  1 means vrp_batch_lsr itself, one workgroup per
+    request.  The factor is the largest of 1, 2, 4, 8 and 16 measured (DESIGN
+    §4.3r): at every launch size each step up was faster."""
+    return min(int(S), max(1, (16 * int(cus)) // max(int(R), 1)))
+
+
 def batch_lsr_launch(ctx: Context, cis, starts: int, rounds: int, seed: int,
-                     objective: str = "sum"):
+                     objective: str = "sum", spread=None):
     """One upload and one vrp_batch_lsr launch for compact instances of one
     batch_lsr_key (each passed batch_guard_message and batch_lsr_fits) ->
     (tours, veh, durs): per instance the n + K - 1 tokens of the best end tour
     (0 a separator), each token's vehicle (-1 unvisited, -2 a separator) and
-    the K route durations."""
+    the K route durations.  `spread`: None -- the default -- is that launch;
+    an int in 1..BATCH_LSR_MAX_SPREAD takes vrp_batch_lsr_spread at that many
+    workgroups per request (1: one workgroup per request, its 256 threads on
+    one descent at a time); "auto" takes batch_lsr_spread's for the launch's
+    size and the device, and vrp_batch_lsr when that is 1.  The rows are the
+    same whichever it is."""
     import torch
+    spread = check_lsr_spread(spread)
     mats, demand, caps = _stage(ctx, cis, hours=True)
     st = torch.from_numpy(np.array([ci.start_times for ci in cis], dtype=np.int32)).to(ctx.dev)
-    tours, keys, durs, veh, _ = ctx.vrp_batch_lsr(mats, demand, caps, st,
-                                                  OBJ_MAX if objective == "max" else OBJ_SUM,
-                                                  int(starts), int(rounds), seed,
-                                                  wide=batch_sa_wide(cis[0]))
+    if spread == "auto":
+        spread = batch_lsr_spread(len(cis), int(starts), ctx.cus)
+        spread = None if spread == 1 else min(spread, BATCH_LSR_MAX_SPREAD)
+    args = (mats, demand, caps, st, OBJ_MAX if objective == "max" else OBJ_SUM, int(starts),
+            int(rounds), seed)
+    if spread is None:
+        tours, keys, durs, veh, _ = ctx.vrp_batch_lsr(*args, wide=batch_sa_wide(cis[0]))
+    else:
+        tours, keys, durs, veh, _ = ctx.vrp_batch_lsr_spread(*args, spread,
+                                                             wide=batch_sa_wide(cis[0]))
     if (keys == -1).any().item():
         raise RuntimeError("vrp_batch_lsr: a request was outside the launch's contract")
     return tours.cpu().tolist(), veh.cpu().tolist(), durs.cpu().tolist()
@@ -1655,7 +1699,7 @@ def batch_lsr_launch(ctx: Context, cis, starts: int, rounds: int, seed: int,
 
 def solve_vrp_lsr_batch(requests, *, starts: int = 64, rounds: int = 1000, seed: int = 0,
                         objective: str = "sum", with_unvisited: bool = False,
-                        device: int = 0) -> list:
+                        device: int = 0, spread=None) -> list:
     """A multi-start local search over separator tours for many small-fleet
     VRP requests, the requests sharing launches (spec A26): one workgroup per
     request, its whole instance in LDS, `starts` steepest descents over swap,
@@ -1680,9 +1724,11 @@ def solve_vrp_lsr_batch(requests, *, starts: int = 64, rounds: int = 1000, seed:
     box.  The requests are grouped by (N, K, H, wide), one upload and one
     vrp_batch_lsr launch per group, and their dicts are built on the host from
     the tokens, their vehicles and the route durations; no customer has
-    solve_vrp's trivial answer."""
+    solve_vrp's trivial answer.  `spread` is batch_lsr_launch's, applied to
+    every group's launch: it changes which kernels run, never a dict."""
     if objective not in ("sum", "max"):
         raise ValueError("objective must be 'sum' or 'max'")
+    spread = check_lsr_spread(spread)
     if not 1 <= int(starts) <= BATCH_LSR_MAX_STARTS:
         raise ValueError(f"starts must be in 1..{BATCH_LSR_MAX_STARTS} ({starts} given)")
     if not 0 <= int(rounds) <= BATCH_LSR_MAX_ROUNDS:
@@ -1704,6 +1750,8 @@ def solve_vrp_lsr_batch(requests, *, starts: int = 64, rounds: int = 1000, seed:
     shared = dict(seed=seed, objective=objective, with_unvisited=with_unvisited,
                   starts=int(starts), rounds=int(rounds))
     if _remote() is not None:      # no local GPU: the GPU box answers each request
+        if isinstance(spread, int):   # "auto" is the GPU box's own to decide
+            shared["spread"] = spread
         return [solve_vrp("lsr", *r, **shared) for r in reqs]
     out = [None] * len(cis)
     groups: dict = {}
@@ -1715,7 +1763,8 @@ def solve_vrp_lsr_batch(requests, *, starts: int = 64, rounds: int = 1000, seed:
     if groups:
         ctx = context(device)
         for xs in groups.values():
-            rows = batch_lsr_launch(ctx, [cis[x] for x in xs], starts, rounds, seed, objective)
+            rows = batch_lsr_launch(ctx, [cis[x] for x in xs], starts, rounds, seed, objective,
+                                    spread=spread)
             for x, tour, veh, durs in zip(xs, *rows):
                 out[x] = sa_result(cis[x], tour, veh, durs, with_unvisited)
     return out
