@@ -808,6 +808,60 @@ int vrpms_vrp_batch_lsr_spread(vrpms_ctx* ctx, const int32_t* d_mats, const int3
                                uint64_t work_bytes, uint16_t* d_tours, uint64_t* d_keys,
                                int32_t* d_durs, int8_t* d_veh, int32_t* d_info, void* stream);
 
+/* Throughput mode of a multi-start local search for the TSP with Or-opt moves
+ * and delta pricing: R independent TSP requests of
+ * one node count N >= 2 (n = N - 1 customers, node 0 the start node), one hour
+ * count H (1 or 24), one start count S, 1 <= S <= 65535, one round cap `rounds`
+ * >= 0, one move mask `moves`, 1..31, and one seed, each with its own int32
+ * [H][N][N] matrix (d_mats [R][H][N][N]) and start time (d_start [R], minutes,
+ * >= 0).  A tour is a permutation of 1..n on positions 0..n-1, its duration
+ * spec.eval_tsp's (A4) from the start time, its key spec.tsp_key of it (A8:
+ * min(duration, 2^28 - 1) << 28); tours compare by key.  ONE WORKGROUP PER
+ * REQUEST: the matrix is staged into LDS once -- as uint16 with wide = 0, as
+ * int32 with wide = 1.  Wavefront w descends the starts w, w + 4, ...: start s
+ * is vrpms_vrp_batch_ls's start s, the Philox Fisher-Yates shuffle of 1..n with
+ * counters (0xffffffff, 0xffffffff, s, q).  A round prices the moves (typ, i,
+ * j) of every type whose bit `moves` has set (bit t: typ t) -- swap (typ 0) and
+ * 2-opt (typ 1) with i < j, relocate (typ 2) with i != j, and Or-opt of m = 2
+ * (typ 3) and m = 3 (typ 4) customers: with seg = p[i:i+m] and rest = p[:i] +
+ * p[i+m:] the moved tour is rest[:j] + seg + rest[j:], 0 <= i, j <= n - m,
+ * j != i (relocate is that formula at m = 1; a type has no moves when n <= m)
+ * -- and takes the least (key, typ, i, j): a key below the tour's applies the
+ * move and the next round follows, otherwise the descent has stopped at a
+ * local optimum.  A descent also stops once `rounds` moves are applied; it then
+ * counts as capped.  n < 2 has no moves and is never capped.  The answer is
+ * the least (key, s) over the S end tours.  No candidate is walked in full: on
+ * a static matrix its duration is the tour's plus an exact integer delta of a
+ * fixed number of edges and prefix sums, on an hour-indexed one the walk
+ * starts at the first changed position.  The counters carry no request row, so
+ * a request's answer depends on the request, S, rounds, moves and seed alone:
+ * not on the launch it rode in nor on its row in it.  With moves = 7 the tour,
+ * s and the capped count are vrpms_vrp_batch_ls's at K = 1, zero demands, any
+ * capacity >= 0, vehicle start = the start time and objective sum; only the
+ * key's secondary field differs (0 here, the duration there).
+ * vrpms_tsp_batch_lso_lds gives the launch's dynamic-LDS bytes for (N, H, wide)
+ * (host only, no context): align16(H N N (wide ? 4 : 2)) for the matrix, per
+ * wavefront (four of them) two int32 rows (H = 1) or one (H = 24) of
+ * align4(n + 2) words, a uint16 tour of align8(n + 2) and one of align8(n)
+ * genes, and 4 * 16 bytes of records; a launch that needs more than the device
+ * has is refused with that byte count in the message.  (N + 2) * max(D) +
+ * start < 2^31 (A9 with K = 1) is the caller's promise.  Out, per request:
+ * d_tours [R][n] (the answer), d_keys [R] (its key), d_durs [R] (its duration,
+ * unclamped) and d_info [R][2] (the answer's start s, and the number of capped
+ * descents among the S).  A request whose matrix has a negative entry, or with
+ * wide = 0 one above 65535, gets UINT64_MAX, an all-zero tour, duration 0 and
+ * d_info = (-1, 0), descends nothing and touches nothing else.  No instance
+ * and no workspace needed; asynchronous on `stream`.  R = 0 launches nothing.
+ * VRPMS_EINVAL, with nothing launched and nothing written, for a NULL ctx,
+ * R < 0, N outside 2..65535, H other than 1 or 24, an unknown wide, S outside
+ * 1..65535, rounds < 0, moves outside 1..31, a NULL buffer with R > 0, or an
+ * LDS need above the device's. */
+int vrpms_tsp_batch_lso_lds(int32_t N, int32_t H, int32_t wide, uint64_t* bytes);
+int vrpms_tsp_batch_lso(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_start, int32_t R,
+                        int32_t N, int32_t H, int32_t wide, int32_t S, int32_t rounds,
+                        int32_t moves, uint64_t seed, uint16_t* d_tours, uint64_t* d_keys,
+                        int32_t* d_durs, int32_t* d_info, void* stream);
+
 /* ------------------------------------------------------------------------
  * Populations and the island model.  A pool is a set of
  * tours with their A8 keys: SA chains, a GA population ([islands][pop],

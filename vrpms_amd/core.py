@@ -116,6 +116,15 @@ def vrp_batch_ls_lds(N: int, K: int, H: int, wide) -> int:
     return int(nbytes.value)
 
 
+def tsp_batch_lso_lds(N: int, H: int, wide) -> int:
+    """vrpms_tsp_batch_lso_lds: the dynamic-LDS bytes of a tsp_batch_lso launch
+    for N nodes, H hour slices (1 or 24) and a uint16 (`wide` false) or int32
+    (`wide` true) matrix.  Host only: needs the library, no GPU."""
+    nbytes = ctypes.c_uint64()
+    check(_lib.load().vrpms_tsp_batch_lso_lds(int(N), int(H), int(wide), ctypes.byref(nbytes)))
+    return int(nbytes.value)
+
+
 def vrp_batch_lsr_lds(N: int, K: int, H: int, wide) -> int:
     """vrpms_vrp_batch_lsr_lds: the dynamic-LDS bytes of a vrp_batch_lsr launch
     for N nodes, K vehicles, H hour slices (1 or 24) and a uint16 (`wide`
@@ -889,6 +898,48 @@ class Context:
                                           keys.data_ptr(), durs.data_ptr(), veh.data_ptr(),
                                           info.data_ptr(), self.stream()))
         return tours, keys, durs, veh, info
+
+    def tsp_batch_lso(self, mats, starts, nstarts: int, rounds: int, moves: int, seed: int,
+                      wide=None):
+        """A multi-start local search with Or-opt moves and delta pricing per
+        TSP request, one workgroup per request, one launch for all (spec A27;
+        all requests of one N and H): mats int32 [R][H][N][N] (H = 1 or 24;
+        [R][N][N] is taken as H = 1) and starts int32 [R] (the start times,
+        minutes) on the device -> (tours int16 [R][n], keys int64 [R], durs
+        int32 [R], info int32 [R][2]) with n = N - 1: per request the least
+        (key, start) end tour of `nstarts` (1..65535) steepest descents from
+        vrp_batch_ls's random starts 0..nstarts-1 over the move types `moves`
+        enables (1..31; bit 0 swap, 1 2-opt, 2 relocate, 3 and 4 Or-opt of two
+        and three customers), each stopped at a local optimum or after `rounds`
+        (>= 0) applied moves; its key (spec.tsp_key), its unclamped duration,
+        and info = (the winning start, the number of descents the round cap
+        stopped unproven).  A request's row depends on the request, `nstarts`,
+        `rounds`, `moves` and `seed` alone, not on the batch; with moves = 7
+        the tour and info are vrp_batch_ls's at K = 1 and zero demands.
+        `wide`: False stages the matrices as uint16 (a request with an entry
+        above 65535 then gets an all-ones key, a zero tour, duration 0 and
+        info = (-1, 0)), True as int32; None -- the default -- asks the device
+        for the batch's largest entry, which synchronises.  The A9 guard is
+        the caller's promise.  Asynchronous on the current stream."""
+        torch = _torch()
+        mats = self._batch_mats(torch, mats, 4)
+        R, H, N, _ = mats.shape
+        if starts.device != self.dev or starts.shape != (R,) or starts.dtype != torch.int32 \
+                or not starts.is_contiguous():
+            raise ValueError(f"starts must be a contiguous int32 [R] tensor on {self.dev}")
+        if wide is None:
+            wide = bool(R) and int(mats.max().item()) > 65535
+        n = N - 1
+        tours = torch.empty((R, max(n, 1)), dtype=torch.int16, device=self.dev)
+        keys = torch.empty(R, dtype=torch.int64, device=self.dev)
+        durs = torch.empty(R, dtype=torch.int32, device=self.dev)
+        info = torch.empty((R, 2), dtype=torch.int32, device=self.dev)
+        check(self.lib.vrpms_tsp_batch_lso(self._ctx, mats.data_ptr(), starts.data_ptr(), R, N, H,
+                                           int(bool(wide)), int(nstarts), int(rounds), int(moves),
+                                           int(seed) & (2**64 - 1), tours.data_ptr(),
+                                           keys.data_ptr(), durs.data_ptr(), info.data_ptr(),
+                                           self.stream()))
+        return tours, keys, durs, info
 
     def vrp_batch_lsr(self, mats, demand, caps, starts, objective: int, nstarts: int, rounds: int,
                       seed: int, wide=None):

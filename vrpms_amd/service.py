@@ -37,9 +37,10 @@ TITLES = {"bf": "Brute Force", "ga": "Genetic Algorithm", "sa": "Simulated Annea
 # and the exact solvers, "dp" (Held-Karp) for the TSP and "sp" (set
 # partitioning) for the VRP, and "tdp" (time-expanded subset DP, hour-indexed
 # matrices) for the TSP and "tdsp" (its fleet counterpart, per-vehicle start
-# times) for the VRP (they have no /api endpoint: the eight endpoints are
-# the reference's wire contract)
-INLINE_ALGORITHMS = {"tsp": tuple(TITLES) + ("dp", "tdp"),
+# times) for the VRP, and the local searches "ls" / "lsr" (VRP) and "lso" (TSP)
+# (they have no /api endpoint: the eight endpoints are the reference's wire
+# contract)
+INLINE_ALGORITHMS = {"tsp": tuple(TITLES) + ("dp", "tdp", "lso"),
                      "vrp": tuple(TITLES) + ("ls", "lsr", "tdsp", "sp")}
 
 # (body key, params key) in the order the reference checks them
@@ -58,7 +59,8 @@ _COMMON = {
 # in its "knobs" object (vrpms_amd.remote forwards them): name -> type
 INLINE_KNOBS = {"steps": int, "separators": int, "window": int, "chains": int,
                 "window_types": int, "pop": int, "islands": int, "colonies": int, "ants": int,
-                "upper_bound": int, "starts": int, "rounds": int, "spread": int}
+                "upper_bound": int, "starts": int, "rounds": int, "spread": int,
+                "moves": int}
 # their accepted ranges (inclusive): a value from the network outside them is a
 # 400, never an allocation (islands = 10**6 or chains = 2**30 would
 # exhaust device memory while the request holds every device lock)
@@ -66,7 +68,7 @@ KNOB_RANGES = {"steps": (1, 10**8), "separators": (0, 4096), "window": (0, 65535
                "chains": (1, 1 << 16), "window_types": (0, 7), "pop": (2, 4096),
                "islands": (1, 4096), "colonies": (1, 4096), "ants": (1, 4096),
                "upper_bound": (0, 2**31 - 1), "starts": (1, 1024), "rounds": (0, 1000),
-               "spread": (1, 1024)}
+               "spread": (1, 1024), "moves": (1, 31)}
 
 
 def check_knob(name, value):
@@ -995,7 +997,8 @@ class App:
         an endpoint name or, for tsp only, "dp" (exact Held-Karp, up to 24
         customers on a static matrix) or "tdp" (exact time-expanded DP, up to
         solver.TDP_MAX_CUSTOMERS customers, hour-indexed matrices too; knob
-        "upper_bound"), or, for vrp only, "sp" (exact set partitioning, up to solver.SP_MAX_CUSTOMERS customers and 64 vehicles
+        "upper_bound") or "lso" (multi-start local search with Or-opt, spec A27;
+        knobs "starts", "rounds", "moves"), or, for vrp only, "sp" (exact set partitioning, up to solver.SP_MAX_CUSTOMERS customers and 64 vehicles
         on a static matrix) or "tdsp" (exact time-expanded partition DP, up
         to solver.TDSP_MAX_CUSTOMERS customers and 64 vehicles, hour-indexed
         matrices and per-vehicle start times; knob "upper_bound":

@@ -39,7 +39,7 @@ import numpy as np
 from . import runners
 from .core import CVRP, OBJ_MAX, OBJ_SUM, TSP, Context
 
-ALGORITHMS = ("bf", "ga", "sa", "aco", "dp", "sp", "tdp", "tdsp", "ls", "lsr")
+ALGORITHMS = ("bf", "ga", "sa", "aco", "dp", "sp", "tdp", "tdsp", "ls", "lsr", "lso")
 # the exact algorithms with kernels of their own: one device, no island model
 # (the exhaustive "bf" shares that with them)
 EXACT_ALGORITHMS = ("dp", "sp", "tdp", "tdsp")
@@ -155,6 +155,15 @@ BATCH_LSR_LDS_BYTES = BATCH_SA_LDS_BYTES
 # A26 by the other mapping (vrp_batch_lsr_spread): the workgroups
 # a request's starts may be spread over; the answers do not depend on it
 BATCH_LSR_MAX_SPREAD = 1024
+# batched TSP multi-start local search with Or-opt and delta pricing (A27): next
+# to the matrix a wavefront keeps two tours and two int32 prefix rows (one on an
+# hour-indexed matrix); vrpms_tsp_batch_lso_lds gives the bytes for (N, H,
+# wide), DESIGN.md §4.3s has the largest N per (H, wide).  As for A25, more than
+# BATCH_LSO_MAX_STARTS starts or BATCH_LSO_MAX_ROUNDS rounds is an error, not
+# another path
+BATCH_LSO_MAX_STARTS = 1024
+BATCH_LSO_MAX_ROUNDS = 1000
+BATCH_LSO_LDS_BYTES = BATCH_SA_LDS_BYTES
 # SA on tours of more than SA_WINDOW_MIN_N customers samples A11 windowed
 # moves (second position within SA_WINDOW of the first)
 SA_WINDOW, SA_WINDOW_MIN_N = 32, 150
@@ -532,7 +541,15 @@ def solve_tsp(algorithm: str, durations, customers, start_node, start_time=0, *,
     (exact, at most TDP_MAX_CUSTOMERS customers, static or hour-indexed matrix)
     does the same; its knob `upper_bound` (minutes, default the
     nearest-neighbour tour's duration) bounds the tour duration, and the table
-    it implies must fit TDP_MAX_WORKSPACE."""
+    it implies must fit TDP_MAX_WORKSPACE.  "lso" (spec A27: a multi-start
+    local search with Or-opt moves and delta pricing on a static or
+    hour-indexed matrix; knobs `starts`, default 64, at most
+    BATCH_LSO_MAX_STARTS, `rounds`, default 1000, at most BATCH_LSO_MAX_ROUNDS,
+    and `moves`, the mask of enabled move types, default 31) answers with a
+    one-request tsp_batch_lso launch on the first of `devices`:
+    solve_tsp_lso_batch's answer for the request.  It ignores `time_limit`; its
+    domain (the matrix has to fit the LDS: batch_lso_message) is checked before
+    any device or remote is touched."""
     ci = None
     if algorithm == "sp":
         raise ValueError('sp solves the VRP only (set partitioning over a fleet); use "dp" for '
@@ -554,10 +571,21 @@ def solve_tsp(algorithm: str, durations, customers, start_node, start_time=0, *,
     if algorithm == "tdp":
         ci = compact_tsp(durations, customers, start_node, start_time)
         _check_tdp(ci, knobs.get("upper_bound"))
+    if algorithm == "lso":
+        ci = compact_tsp(durations, customers, start_node, start_time)
+        lso = (64 if knobs.get("starts") is None else int(knobs["starts"]),
+               1000 if knobs.get("rounds") is None else int(knobs["rounds"]),
+               31 if knobs.get("moves") is None else int(knobs["moves"]))
+        _check_lso(ci, *lso)
+        if ci.n == 0:              # no customer: answered on the host
+            return tsp_result(ci, [], _td_duration(ci, []))
     rem = _remote()
     if rem is not None:
         return rem.solve_tsp(algorithm, durations, customers, start_node, start_time, seed=seed,
                              time_limit=time_limit, **knobs)
+    if algorithm == "lso":         # a one-request tsp_batch_lso launch on one device
+        tours, durs = batch_lso_launch(context(devices[0] if devices else device), [ci], *lso, seed)
+        return tsp_result(ci, tours[0], durs[0])
     if ci is None:
         ci = compact_tsp(durations, customers, start_node, start_time)
     ctx, tour = _searched(ci, algorithm, seed, time_limit, device, devices, OBJ_SUM, knobs)
@@ -603,6 +631,9 @@ def solve_vrp(algorithm: str, durations, locations, capacities, start_times,
         raise ValueError("tdp solves the TSP only: per-vehicle start times (one table per "
                          "vehicle) and the capacity split are out of spec A16's scope; use bf, "
                          "sa, ga or aco for a time-dependent VRP, or tdsp for the exact one")
+    if algorithm == "lso":
+        raise ValueError('lso solves the TSP only (its delta pricing has no fleet and no capacity '
+                         'split); use "ls" or "lsr" for a local search on the VRP')
     ci = None
     if algorithm == "sp":
         ci = compact_vrp(durations, locations, capacities, start_times, ignored_customers,
@@ -1579,6 +1610,146 @@ def solve_vrp_ls_batch(requests, *, starts: int = 64, rounds: int = 1000, seed: 
             rows = batch_ls_launch(ctx, [cis[x] for x in xs], starts, rounds, seed, objective)
             for x, tour, veh, durs in zip(xs, *rows):
                 out[x] = sa_result(cis[x], tour, veh, durs, with_unvisited)
+    return out
+
+
+# ---------------------------------------------------------------------------
+# batched TSP multi-start local search with Or-opt and delta pricing (A27)
+# ---------------------------------------------------------------------------
+def batch_lso_key(ci: CompactInstance, starts: int, rounds: int, moves: int = 31):
+    """What the instances of one tsp_batch_lso launch share (next to the
+    seed): (N, H, wide, starts, rounds, moves)."""
+    return ci.N, ci.durations.shape[0], batch_sa_wide(ci), int(starts), int(rounds), int(moves)
+
+
+def batch_lso_message(ci: CompactInstance, starts: int, rounds: int, moves: int = 31):
+    """The limit of A27's domain this request fails -> its message, or None:
+    a TSP of at least one customer and at most 65534, a static or 24-slice
+    matrix, 1 <= starts <= BATCH_LSO_MAX_STARTS, 0 <= rounds <=
+    BATCH_LSO_MAX_ROUNDS, 1 <= moves <= 31, and a matrix that fits
+    BATCH_LSO_LDS_BYTES together with the wavefronts' tours and prefix rows
+    (vrpms_tsp_batch_lso_lds; uint16 cells unless an entry is above 65535).
+    Needs the library, no GPU."""
+    from .core import tsp_batch_lso_lds
+    if ci.problem != TSP:
+        return 'lso solves the TSP only'
+    if not 1 <= int(starts) <= BATCH_LSO_MAX_STARTS:
+        return f"lso (local search) takes 1..{BATCH_LSO_MAX_STARTS} starts ({starts} given)"
+    if not 0 <= int(rounds) <= BATCH_LSO_MAX_ROUNDS:
+        return f"lso (local search) takes 0..{BATCH_LSO_MAX_ROUNDS} rounds ({rounds} given)"
+    if not 1 <= int(moves) <= 31:
+        return f"lso (local search) takes a move mask of 1..31 ({moves} given)"
+    if ci.n < 1:
+        return "lso (local search) needs at least one customer"
+    if ci.N > 65535:
+        return f"lso (local search) supports at most 65534 customers ({ci.n} given)"
+    N, H, wide = batch_lso_key(ci, starts, rounds, moves)[:3]
+    if H not in (1, 24):
+        return f"lso (local search) needs a static or 24-slice duration matrix ({H} slices given)"
+    need = tsp_batch_lso_lds(N, H, wide)
+    if need > BATCH_LSO_LDS_BYTES:
+        return (f"lso (local search) keeps the matrix in LDS: {ci.n} customers and {H} hour "
+                f"slice(s) of {'int32' if wide else 'uint16'} cells need {need} bytes; the limit "
+                f"is {BATCH_LSO_LDS_BYTES} bytes")
+    return None
+
+
+def batch_lso_fits(ci: CompactInstance, starts: int, rounds: int, moves: int = 31) -> bool:
+    """The request is inside A27's domain (batch_lso_message names no limit).
+    Needs the library, no GPU."""
+    return batch_lso_message(ci, starts, rounds, moves) is None
+
+
+def _check_lso(ci: CompactInstance, starts, rounds, moves):
+    """A27's domain and the A9 guard, checked on the host before any device or
+    remote is touched.  No customer is answered on the host."""
+    if ci.problem == TSP and ci.n == 0 and 1 <= int(starts) <= BATCH_LSO_MAX_STARTS and \
+            0 <= int(rounds) <= BATCH_LSO_MAX_ROUNDS and 1 <= int(moves) <= 31:
+        msg = batch_guard_message(ci)
+    else:
+        msg = batch_lso_message(ci, starts, rounds, moves) or batch_guard_message(ci)
+    if msg is not None:
+        raise ValueError(msg)
+
+
+def batch_lso_launch(ctx: Context, cis, starts: int, rounds: int, moves: int, seed: int):
+    """One upload and one tsp_batch_lso launch for compact instances of one
+    batch_lso_key (each passed batch_guard_message and batch_lso_fits) ->
+    (tours, durs): per instance the n customers of the best end tour and its
+    duration."""
+    import torch
+    mats, = _stage(ctx, cis, hours=True)
+    st = torch.from_numpy(np.array([int(ci.start_times[0]) for ci in cis],
+                                   dtype=np.int32)).to(ctx.dev)
+    tours, keys, durs, _ = ctx.tsp_batch_lso(mats, st, int(starts), int(rounds), int(moves), seed,
+                                             wide=batch_sa_wide(cis[0]))
+    if (keys == -1).any().item():
+        raise RuntimeError("tsp_batch_lso: a request was outside the launch's contract")
+    return tours.cpu().tolist(), durs.cpu().tolist()
+
+
+def solve_tsp_lso_batch(requests, *, starts: int = 64, rounds: int = 1000, moves: int = 31,
+                        seed: int = 0, device: int = 0) -> list:
+    """A multi-start local search for many TSP requests, the requests sharing
+    launches (spec A27): one workgroup per request, its whole matrix (static
+    or hour-indexed) in LDS, `starts` steepest descents from random tours over
+    the move types `moves` enables (bit 0 swap, 1 2-opt, 2 relocate, 3 and 4
+    Or-opt of two and three customers), every candidate priced by a delta
+    instead of a tour walk, each descent stopped at a local optimum or after
+    `rounds` applied moves; the least (key, start) end tour is the answer.
+    `requests`: solve_tsp_batch's (durations, customers, start_node,
+    start_time) tuples, or dicts with those keys -> one solve_tsp slot dict per
+    request.
+
+    It is deterministic per request: the dict depends on the request,
+    `starts`, `rounds`, `moves` and `seed` alone, not on the other requests of
+    the call or on its place among them, and is solve_tsp("lso", starts=,
+    rounds=, moves=)'s.
+
+    Every request is compacted and passed through batch_guard_message and the
+    domain (batch_lso_message) on the host before any device is touched.  There
+    is no unbatched form, so a request outside the domain raises
+    ValueError("request {x}: ...") naming the limit that failed, as a bad one
+    does.  With no local GPU each request goes to solve_tsp("lso") on the GPU
+    box.  The requests are grouped by (N, H, wide, starts, rounds, moves), one
+    upload and one tsp_batch_lso launch per group; no customer is answered on
+    the host."""
+    if not 1 <= int(starts) <= BATCH_LSO_MAX_STARTS:
+        raise ValueError(f"starts must be in 1..{BATCH_LSO_MAX_STARTS} ({starts} given)")
+    if not 0 <= int(rounds) <= BATCH_LSO_MAX_ROUNDS:
+        raise ValueError(f"rounds must be in 0..{BATCH_LSO_MAX_ROUNDS} ({rounds} given)")
+    if not 1 <= int(moves) <= 31:
+        raise ValueError(f"moves must be in 1..31 ({moves} given)")
+    reqs, cis = [], []
+    for x, r in enumerate(requests):
+        try:
+            r, _ = _tsp_request(r)
+            ci = compact_tsp(*r)
+            msg = batch_guard_message(ci)
+            if msg is None and ci.n:
+                msg = batch_lso_message(ci, starts, rounds, moves)
+            if msg is not None:
+                raise ValueError(msg)
+        except ValueError as e:
+            raise ValueError(f"request {x}: {e}") from None
+        reqs.append(r)
+        cis.append(ci)
+    if _remote() is not None:      # no local GPU: the GPU box answers each request
+        return [solve_tsp("lso", *r, seed=seed, starts=int(starts), rounds=int(rounds),
+                          moves=int(moves)) for r in reqs]
+    out = [None] * len(cis)
+    groups: dict = {}
+    for x, ci in enumerate(cis):
+        if ci.n == 0:
+            out[x] = tsp_result(ci, [], _td_duration(ci, []))
+        else:
+            groups.setdefault(batch_lso_key(ci, starts, rounds, moves), []).append(x)
+    if groups:
+        ctx = context(device)
+        for xs in groups.values():
+            tours, durs = batch_lso_launch(ctx, [cis[x] for x in xs], starts, rounds, moves, seed)
+            for x, tour, dur in zip(xs, tours, durs):
+                out[x] = tsp_result(cis[x], tour, dur)
     return out
 
 
