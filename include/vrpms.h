@@ -862,6 +862,39 @@ int vrpms_tsp_batch_lso(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_
                         int32_t moves, uint64_t seed, uint16_t* d_tours, uint64_t* d_keys,
                         int32_t* d_durs, int32_t* d_info, void* stream);
 
+/* vrpms_tsp_batch_lso by another mapping: the same requests,
+ * the same arguments and, per request, the identical d_tours, d_keys, d_durs
+ * and d_info rows, refusal rows included -- but a request's S starts are
+ * spread over min(G, S) workgroups, workgroup g descending the starts g,
+ * g + G, ... one after the other with all 256 threads pricing one round of one
+ * tour (thread t the enabled move ids [t per, (t + 1) per), per = ceil(moves /
+ * 256)), and leaves its best (key, s, capped count, duration, tour) in the
+ * workspace; a second launch on the same stream, one workgroup per request,
+ * takes the least (key, s), sums the capped counts and writes the outputs.
+ * For few requests that occupies R * min(G, S) workgroups instead of R.
+ * vrpms_tsp_batch_lso_spread_lds gives the first launch's dynamic-LDS bytes
+ * for (N, H, wide) (host only, no context): the matrix, per wavefront the
+ * int32 rows and the uint16 tour of align8(n + 2) genes as above, and 2 * 4 *
+ * 16 bytes of round records; never more than vrpms_tsp_batch_lso_lds of the
+ * same shape, so A27's domain holds.  The second launch uses no LDS.
+ * vrpms_tsp_batch_lso_spread_work gives the workspace bytes of R requests at G
+ * workgroups each, R * G * (24 + 2 * align8(N - 1)) (host only; VRPMS_EINVAL
+ * for R < 0, N outside 2..65535, G outside 1..65535 or R * G above 2^31 - 1).
+ * d_work: work_bytes bytes of device memory, 8-byte aligned, at least
+ * vrpms_tsp_batch_lso_spread_work(R, N, min(G, S)); its contents before and
+ * after the call mean nothing.  Asynchronous on `stream`.  R = 0 launches
+ * nothing.  VRPMS_EINVAL, with nothing launched and nothing written, for
+ * everything vrpms_tsp_batch_lso refuses, G outside 1..65535, a NULL,
+ * misaligned or too small workspace with R > 0, or R * min(G, S) above
+ * 2^31 - 1. */
+int vrpms_tsp_batch_lso_spread_lds(int32_t N, int32_t H, int32_t wide, uint64_t* bytes);
+int vrpms_tsp_batch_lso_spread_work(int32_t R, int32_t N, int32_t G, uint64_t* bytes);
+int vrpms_tsp_batch_lso_spread(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_start,
+                               int32_t R, int32_t N, int32_t H, int32_t wide, int32_t S,
+                               int32_t rounds, int32_t moves, uint64_t seed, int32_t G, void* d_work,
+                               uint64_t work_bytes, uint16_t* d_tours, uint64_t* d_keys,
+                               int32_t* d_durs, int32_t* d_info, void* stream);
+
 /* ------------------------------------------------------------------------
  * Populations and the island model.  A pool is a set of
  * tours with their A8 keys: SA chains, a GA population ([islands][pop],

@@ -139,6 +139,10 @@ SIGNATURES = {
     "vrpms_tsp_batch_lso_lds": (_c.c_int, [_i32, _i32, _i32, _c.POINTER(_u64)]),
     "vrpms_tsp_batch_lso": (_c.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _u64,
                                        _vp, _vp, _vp, _vp, _vp]),
+    "vrpms_tsp_batch_lso_spread_lds": (_c.c_int, [_i32, _i32, _i32, _c.POINTER(_u64)]),
+    "vrpms_tsp_batch_lso_spread_work": (_c.c_int, [_i32, _i32, _i32, _c.POINTER(_u64)]),
+    "vrpms_tsp_batch_lso_spread": (_c.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                              _u64, _i32, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "vrpms_random_tours": (_c.c_int, [_vp, _i64, _i32, _i32, _i64, _i32, _u64, _c.c_uint32, _vp,
                                       _vp]),
     "vrpms_insert_separators": (_c.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),

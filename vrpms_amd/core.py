@@ -125,6 +125,27 @@ def tsp_batch_lso_lds(N: int, H: int, wide) -> int:
     return int(nbytes.value)
 
 
+def tsp_batch_lso_spread_lds(N: int, H: int, wide) -> int:
+    """vrpms_tsp_batch_lso_spread_lds: the dynamic-LDS bytes of the descents
+    launch of tsp_batch_lso_spread for N nodes, H hour slices (1 or 24) and a
+    uint16 (`wide` false) or int32 (`wide` true) matrix; never more than
+    tsp_batch_lso_lds of the same shape.  Host only: needs the library, no
+    GPU."""
+    nbytes = ctypes.c_uint64()
+    check(_lib.load().vrpms_tsp_batch_lso_spread_lds(int(N), int(H), int(wide),
+                                                     ctypes.byref(nbytes)))
+    return int(nbytes.value)
+
+
+def tsp_batch_lso_spread_work(R: int, N: int, G: int) -> int:
+    """vrpms_tsp_batch_lso_spread_work: the workspace bytes of a
+    tsp_batch_lso_spread launch of R requests at G workgroups each,
+    R * G * (24 + 2 * align8(N - 1)).  Host only: needs the library, no GPU."""
+    nbytes = ctypes.c_uint64()
+    check(_lib.load().vrpms_tsp_batch_lso_spread_work(int(R), int(N), int(G), ctypes.byref(nbytes)))
+    return int(nbytes.value)
+
+
 def vrp_batch_lsr_lds(N: int, K: int, H: int, wide) -> int:
     """vrpms_vrp_batch_lsr_lds: the dynamic-LDS bytes of a vrp_batch_lsr launch
     for N nodes, K vehicles, H hour slices (1 or 24) and a uint16 (`wide`
@@ -939,6 +960,40 @@ class Context:
                                            int(seed) & (2**64 - 1), tours.data_ptr(),
                                            keys.data_ptr(), durs.data_ptr(), info.data_ptr(),
                                            self.stream()))
+        return tours, keys, durs, info
+
+    def tsp_batch_lso_spread(self, mats, starts, nstarts: int, rounds: int, moves: int, seed: int,
+                             groups: int, wide=None):
+        """tsp_batch_lso by another mapping: the same
+        arguments and the identical four tensors, but a request's `nstarts`
+        starts are spread over min(`groups`, nstarts) workgroups (`groups` in
+        1..65535) whose 256 threads each price one round of one tour together,
+        and a second launch selects the least (key, start) per request.  For
+        few requests that occupies R * groups workgroups instead of R.  The
+        workspace (tsp_batch_lso_spread_work) is allocated here, from torch's
+        caching allocator, which keeps it alive for the stream's queued work.
+        Asynchronous on the current stream."""
+        torch = _torch()
+        mats = self._batch_mats(torch, mats, 4)
+        R, H, N, _ = mats.shape
+        if starts.device != self.dev or starts.shape != (R,) or starts.dtype != torch.int32 \
+                or not starts.is_contiguous():
+            raise ValueError(f"starts must be a contiguous int32 [R] tensor on {self.dev}")
+        if wide is None:
+            wide = bool(R) and int(mats.max().item()) > 65535
+        n = N - 1
+        G = int(groups)
+        work_bytes = tsp_batch_lso_spread_work(R, N, max(1, min(G, int(nstarts)))) \
+            if R and 1 <= G <= 65535 else 0
+        work = torch.empty(max(work_bytes // 8, 1), dtype=torch.int64, device=self.dev)
+        tours = torch.empty((R, max(n, 1)), dtype=torch.int16, device=self.dev)
+        keys = torch.empty(R, dtype=torch.int64, device=self.dev)
+        durs = torch.empty(R, dtype=torch.int32, device=self.dev)
+        info = torch.empty((R, 2), dtype=torch.int32, device=self.dev)
+        check(self.lib.vrpms_tsp_batch_lso_spread(
+            self._ctx, mats.data_ptr(), starts.data_ptr(), R, N, H, int(bool(wide)), int(nstarts),
+            int(rounds), int(moves), int(seed) & (2**64 - 1), G, work.data_ptr(), work_bytes,
+            tours.data_ptr(), keys.data_ptr(), durs.data_ptr(), info.data_ptr(), self.stream()))
         return tours, keys, durs, info
 
     def vrp_batch_lsr(self, mats, demand, caps, starts, objective: int, nstarts: int, rounds: int,

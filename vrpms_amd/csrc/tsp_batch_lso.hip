@@ -50,6 +50,8 @@
 // capped count are vrpms_vrp_batch_ls's at K = 1, zero demands, any capacity
 // >= 0, vehicle start = the start time and objective sum; only the key's
 // secondary field differs (0 here, the duration there).
+// tsp_batch_lso_spread.hip computes the same rows with G workgroups a request;
+// what the two share lives in tsp_batch_lso.hpp.
 //
 // LDS, every part as the kernel carves it (vrpms_tsp_batch_lso_lds):
 //   align16(H N N (wide ? 4 : 2))            the matrix
@@ -70,120 +72,6 @@
 
 namespace vrpms {
 
-constexpr int kBatchLsoMaxN = 65535;   // genes are uint16
-constexpr int kBatchLsoMaxS = 65535;
-
-struct TspBatchLsoArgs {
-  const int32_t* mats;    // [R][H][N][N]
-  const int32_t* start;   // [R]
-  int R, N, S, rounds;
-  uint32_t moves, seed_lo, seed_hi;
-  uint16_t* tours;        // [R][n]
-  uint64_t* keys;         // [R]
-  int32_t* durs;          // [R]
-  int32_t* info;          // [R][2]: the answer's start, the capped descents
-};
-
-struct BatchLsoLds {
-  size_t mat, row, cur, best, total;   // bytes of the matrix, one int32 row, one padded tour, one tour
-};
-
-inline BatchLsoLds batch_lso_lds(int N, int H, int wide) {
-  BatchLsoLds l;
-  const size_t n = (size_t)N - 1;
-  l.mat = ((size_t)H * N * N * (wide ? 4 : 2) + 15) & ~(size_t)15;
-  l.row = ((n + 2 + 3) & ~(size_t)3) * 4;
-  l.cur = ((n + 2 + 7) & ~(size_t)7) * 2;
-  l.best = ((n + 7) & ~(size_t)7) * 2;
-  l.total = l.mat + 4 * ((H == 1 ? 2 : 1) * l.row + l.cur + l.best) + 4 * 16;
-  return l;
-}
-
-// duration of the padded tour P (node 0 at P[0] and P[n + 1]) on a static
-// matrix, with the rows F and B filled on the way: 64 edges a step, the
-// forward edge in the low and the backward edge in the high half of one scan
-template <typename Mat>
-VRPMS_DEV int lso_rows_static(const Mat& D, const uint16_t* P, int n, int32_t* F, int32_t* B,
-                              int lane) {
-  uint32_t cf = 0, cb = 0;
-  if (lane == 0) {
-    F[0] = 0;
-    B[0] = 0;
-  }
-  for (int base = 1; base <= n + 1; base += 64) {
-    const int q = base + lane;
-    uint64_t v = 0;
-    if (q <= n + 1) {
-      const uint32_t x = P[q - 1], y = P[q];
-      v = ((uint64_t)(uint32_t)D(0, y, x) << 32) | (uint32_t)D(0, x, y);
-    }
-    const uint64_t tot = wave_scan_add_u64(v);
-    if (q <= n + 1) {
-      F[q] = (int32_t)(cf + (uint32_t)v);
-      B[q] = (int32_t)(cb + (uint32_t)(v >> 32));
-    }
-    cf += (uint32_t)tot;
-    cb += (uint32_t)(tot >> 32);
-  }
-  wave_sync();
-  return (int)cf;
-}
-
-// duration of the padded tour P from time t0 on the clock, with the arrival
-// row T filled on the way: every lane walks alike, lane 0 writes
-template <typename Mat>
-VRPMS_DEV int lso_row_clock(const Mat& D, const uint16_t* P, int n, int t0, int32_t* T, int lane) {
-  int t = t0;
-  uint32_t prev = 0;
-  if (lane == 0) T[0] = t;
-  for (int q = 1; q <= n + 1; ++q) {
-    const uint32_t c = P[q];
-    t += D(t, prev, c);
-    prev = c;
-    if (lane == 0) T[q] = t;
-  }
-  wave_sync();
-  return t - t0;
-}
-
-// exact duration change of the static closed tour under move m; P is the
-// padded tour (P[q + 1] = position q), F and B its prefix rows
-template <typename Mat>
-VRPMS_DEV int lso_delta_static(const Mat& D, const uint16_t* P, const int32_t* F, const int32_t* B,
-                               int n, const Move& m) {
-  auto d = [&](uint32_t a, uint32_t b) { return D(0, a, b); };
-  const int i = m.i, j = m.j;
-  if (m.typ == kMove2Opt) {
-    const uint32_t a = P[i], pi = P[i + 1], pj = P[j + 1], b = P[j + 2];
-    return d(a, pj) + d(pi, b) - d(a, pi) - d(pj, b) + (B[j + 1] - B[i + 1]) - (F[j + 1] - F[i + 1]);
-  }
-  if (m.typ <= kMoveRelocate)
-    return tsp_move_delta(d, [&](int q) { return (uint32_t)P[q + 1]; }, n, m, true);
-  const int sl = (int)m.typ - 1;
-  const uint32_t a = P[i], s0 = P[i + 1], s1 = P[i + sl], b = P[i + sl + 1];
-  // rest's padded position x is P[x] up to i and P[x + m] past it
-  const uint32_t pred = P[j <= i ? j : j + sl], succ = P[j + 1 <= i ? j + 1 : j + 1 + sl];
-  return d(a, b) + d(pred, s0) + d(s1, succ) - d(a, s0) - d(s1, b) - d(pred, succ);
-}
-
-// duration of the moved tour on the clock: the walk from the move's first
-// changed position with T's clock there
-template <typename Mat>
-VRPMS_DEV int lso_walk_clock(const Mat& D, const uint16_t* P, const int32_t* T, int n, const Move& m) {
-  const LsoMap mm = lso_map(m);
-  const int f = lso_first(m), l = lso_last(m);
-  int t = T[f];
-  uint32_t prev = P[f];
-  for (int q = f; q < n; ++q) {
-    const uint32_t c = P[lso_src(mm, q) + 1];
-    t += D(t, prev, c);
-    prev = c;
-    if (q > l && t == T[q + 1]) return T[n + 1] - T[0];   // the rest is the current tour's
-  }
-  t += D(t, prev, 0);
-  return t - T[0];
-}
-
 template <typename MatT, int HM>
 __global__ __launch_bounds__(256) void tsp_batch_lso_kernel(TspBatchLsoArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char batch_lso_lds_mem[];
@@ -203,31 +91,9 @@ __global__ __launch_bounds__(256) void tsp_batch_lso_kernel(TspBatchLsoArgs a) {
   // stage and check the matrix as batch_stage_request does; the verdict goes
   // through a word of the waves' records, free until the descents end
   uint16_t* gtour = a.tours + r * n;
-  {
-    uint32_t* flag = reinterpret_cast<uint32_t*>(wst);
-    const int32_t* src = a.mats + r * (int64_t)cells;
-    if (threadIdx.x == 0) *flag = 0;
-    __syncthreads();
-    bool bad = false;
-    for (uint32_t i = threadIdx.x; i < cells; i += 256) {
-      const int32_t v = src[i];
-      bad |= v < 0 || (sizeof(MatT) == 2 && v > 65535);
-      M[i] = (MatT)v;
-    }
-    if (bad) *flag = 1;
-    __syncthreads();
-    bad = *flag != 0;
-    __syncthreads();   // every wavefront has read the word before anything replaces it
-    if (bad) {         // the refusal row
-      for (int q = threadIdx.x; q < n; q += 256) gtour[q] = 0;
-      if (threadIdx.x == 0) {
-        a.keys[r] = ~0ull;
-        a.durs[r] = 0;
-        a.info[2 * r] = -1;
-        a.info[2 * r + 1] = 0;
-      }
-      return;
-    }
+  if (lso_stage(a.mats, r, cells, M, reinterpret_cast<uint32_t*>(wst))) {
+    lso_refuse(a, r, n);
+    return;
   }
 
   const int wave = (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = lane_id();
@@ -312,19 +178,6 @@ __global__ __launch_bounds__(256) void tsp_batch_lso_kernel(TspBatchLsoArgs a) {
   }
 }
 
-// the shape checks both entry points share; 0 or the refusal's code
-static int batch_lso_check(const char* who, int32_t N, int32_t H, int32_t wide) {
-  const std::string w(who);
-  if (N < 2 || N > kBatchLsoMaxN)
-    return fail(VRPMS_EINVAL, w + ": needs 2 <= N <= 65535 (" + std::to_string(N) + " given)");
-  if (H != 1 && H != 24)
-    return fail(VRPMS_EINVAL, w + ": H must be 1 or 24 (" + std::to_string(H) + " given)");
-  if (wide != 0 && wide != 1)
-    return fail(VRPMS_EINVAL, w + ": wide must be 0 (uint16 matrix) or 1 (int32) (" + std::to_string(wide) +
-                                  " given)");
-  return VRPMS_OK;
-}
-
 }  // namespace vrpms
 
 using namespace vrpms;
@@ -345,23 +198,14 @@ extern "C" int vrpms_tsp_batch_lso(vrpms_ctx* ctx, const int32_t* d_mats, const 
   if (R < 0) return fail(VRPMS_EINVAL, "vrpms_tsp_batch_lso: R must not be negative");
   const int rc = batch_lso_check("vrpms_tsp_batch_lso", N, H, wide);
   if (rc) return rc;
-  if (S < 1 || S > kBatchLsoMaxS)
-    return fail(VRPMS_EINVAL, "vrpms_tsp_batch_lso: 1 <= S <= 65535 (" + std::to_string(S) + " given)");
-  if (rounds < 0)
-    return fail(VRPMS_EINVAL,
-                "vrpms_tsp_batch_lso: rounds must not be negative (" + std::to_string(rounds) + " given)");
-  if (moves < 1 || moves > 31)
-    return fail(VRPMS_EINVAL, "vrpms_tsp_batch_lso: 1 <= moves <= 31, bit t enabling move type t (" +
-                                  std::to_string(moves) + " given)");
+  const int rs = batch_lso_check_search("vrpms_tsp_batch_lso", S, rounds, moves);
+  if (rs) return rs;
   if (R == 0) return VRPMS_OK;
   if (!d_mats || !d_start || !d_tours || !d_keys || !d_durs || !d_info)
     return fail(VRPMS_EINVAL, "vrpms_tsp_batch_lso: NULL matrix/start/tour/key/duration/info buffer");
   const size_t lds = batch_lso_lds(N, H, wide).total;
   if (lds > ctx->max_lds)
-    return fail(VRPMS_EINVAL, "vrpms_tsp_batch_lso: a request of N = " + std::to_string(N) + ", H = " +
-                                  std::to_string(H) + (wide ? " (int32 matrix)" : " (uint16 matrix)") +
-                                  " needs " + std::to_string(lds) + " bytes of LDS (" +
-                                  std::to_string(ctx->max_lds) + " available)");
+    return batch_lso_lds_refusal("vrpms_tsp_batch_lso", N, H, wide, lds, ctx->max_lds);
   VRPMS_HIP(hipSetDevice(ctx->device));
   const TspBatchLsoArgs a{d_mats, d_start, R, N, S, rounds, (uint32_t)moves, (uint32_t)seed,
                           (uint32_t)(seed >> 32), d_tours, d_keys, d_durs, d_info};

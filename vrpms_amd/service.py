@@ -998,7 +998,8 @@ class App:
         customers on a static matrix) or "tdp" (exact time-expanded DP, up to
         solver.TDP_MAX_CUSTOMERS customers, hour-indexed matrices too; knob
         "upper_bound") or "lso" (multi-start local search with Or-opt, spec A27;
-        knobs "starts", "rounds", "moves"), or, for vrp only, "sp" (exact set partitioning, up to solver.SP_MAX_CUSTOMERS customers and 64 vehicles
+        knobs "starts", "rounds", "moves" and "spread": the workgroups the
+        starts are spread over, the same body sooner), or, for vrp only, "sp" (exact set partitioning, up to solver.SP_MAX_CUSTOMERS customers and 64 vehicles
         on a static matrix) or "tdsp" (exact time-expanded partition DP, up
         to solver.TDSP_MAX_CUSTOMERS customers and 64 vehicles, hour-indexed
         matrices and per-vehicle start times; knob "upper_bound":

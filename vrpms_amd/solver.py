@@ -164,6 +164,9 @@ BATCH_LSR_MAX_SPREAD = 1024
 BATCH_LSO_MAX_STARTS = 1024
 BATCH_LSO_MAX_ROUNDS = 1000
 BATCH_LSO_LDS_BYTES = BATCH_SA_LDS_BYTES
+# A27 by the other mapping (tsp_batch_lso_spread): the workgroups
+# a request's starts may be spread over; the answers do not depend on it
+BATCH_LSO_MAX_SPREAD = 1024
 # SA on tours of more than SA_WINDOW_MIN_N customers samples A11 windowed
 # moves (second position within SA_WINDOW of the first)
 SA_WINDOW, SA_WINDOW_MIN_N = 32, 150
@@ -549,7 +552,9 @@ def solve_tsp(algorithm: str, durations, customers, start_node, start_time=0, *,
     one-request tsp_batch_lso launch on the first of `devices`:
     solve_tsp_lso_batch's answer for the request.  It ignores `time_limit`; its
     domain (the matrix has to fit the LDS: batch_lso_message) is checked before
-    any device or remote is touched."""
+    any device or remote is touched.  Its knob `spread` (None, "auto" or
+    1..BATCH_LSO_MAX_SPREAD; batch_lso_launch) spreads the request's starts
+    over that many workgroups: the same answer, sooner for a lone request."""
     ci = None
     if algorithm == "sp":
         raise ValueError('sp solves the VRP only (set partitioning over a fleet); use "dp" for '
@@ -576,6 +581,11 @@ def solve_tsp(algorithm: str, durations, customers, start_node, start_time=0, *,
         lso = (64 if knobs.get("starts") is None else int(knobs["starts"]),
                1000 if knobs.get("rounds") is None else int(knobs["rounds"]),
                31 if knobs.get("moves") is None else int(knobs["moves"]))
+        lso_spread = check_lso_spread(knobs.get("spread"))
+        if isinstance(lso_spread, int):   # only a number travels to a GPU box as a knob
+            knobs["spread"] = lso_spread
+        else:
+            knobs.pop("spread", None)
         _check_lso(ci, *lso)
         if ci.n == 0:              # no customer: answered on the host
             return tsp_result(ci, [], _td_duration(ci, []))
@@ -584,7 +594,8 @@ def solve_tsp(algorithm: str, durations, customers, start_node, start_time=0, *,
         return rem.solve_tsp(algorithm, durations, customers, start_node, start_time, seed=seed,
                              time_limit=time_limit, **knobs)
     if algorithm == "lso":         # a one-request tsp_batch_lso launch on one device
-        tours, durs = batch_lso_launch(context(devices[0] if devices else device), [ci], *lso, seed)
+        tours, durs = batch_lso_launch(context(devices[0] if devices else device), [ci], *lso, seed,
+                                       spread=lso_spread)
         return tsp_result(ci, tours[0], durs[0])
     if ci is None:
         ci = compact_tsp(durations, customers, start_node, start_time)
@@ -1672,24 +1683,59 @@ def _check_lso(ci: CompactInstance, starts, rounds, moves):
         raise ValueError(msg)
 
 
-def batch_lso_launch(ctx: Context, cis, starts: int, rounds: int, moves: int, seed: int):
+def check_lso_spread(spread):
+    """`spread` as batch_lso_launch takes it -> None, "auto" or an int in
+    1..BATCH_LSO_MAX_SPREAD; anything else is a ValueError."""
+    if spread is None or (isinstance(spread, str) and spread == "auto"):
+        return spread
+    if isinstance(spread, (int, np.integer)) and not isinstance(spread, bool) and \
+            1 <= int(spread) <= BATCH_LSO_MAX_SPREAD:
+        return int(spread)
+    raise ValueError(f'spread must be None, "auto" or an integer in 1..{BATCH_LSO_MAX_SPREAD} '
+                     f"({spread!r} given)")
+
+
+def batch_lso_spread(R: int, S: int, cus: int) -> int:
+    """The "auto" policy: the workgroups per request that tsp_batch_lso_spread
+    gives a launch of R requests of S starts on a device of `cus` compute
+    units, min(S, max(1, 16 cus // R)): up to sixteen workgroups a CU while
+    the requests are few.  1 means tsp_batch_lso itself, one workgroup per
+    request.  The factor is the largest of 1, 2, 4, 8 and 16 measured (DESIGN
+    §4.3t): at every launch size each step up was faster."""
+    return min(int(S), max(1, (16 * int(cus)) // max(int(R), 1)))
+
+
+def batch_lso_launch(ctx: Context, cis, starts: int, rounds: int, moves: int, seed: int,
+                     spread=None):
     """One upload and one tsp_batch_lso launch for compact instances of one
     batch_lso_key (each passed batch_guard_message and batch_lso_fits) ->
     (tours, durs): per instance the n customers of the best end tour and its
-    duration."""
+    duration.  `spread`: None -- the default -- is that launch; an int in
+    1..BATCH_LSO_MAX_SPREAD takes tsp_batch_lso_spread at that many workgroups
+    per request (1: one workgroup per request, its 256 threads on one descent
+    at a time); "auto" takes batch_lso_spread's for the launch's size and the
+    device, and tsp_batch_lso when that is 1.  The rows are the same whichever
+    it is."""
     import torch
+    spread = check_lso_spread(spread)
     mats, = _stage(ctx, cis, hours=True)
     st = torch.from_numpy(np.array([int(ci.start_times[0]) for ci in cis],
                                    dtype=np.int32)).to(ctx.dev)
-    tours, keys, durs, _ = ctx.tsp_batch_lso(mats, st, int(starts), int(rounds), int(moves), seed,
-                                             wide=batch_sa_wide(cis[0]))
+    if spread == "auto":
+        spread = batch_lso_spread(len(cis), int(starts), ctx.cus)
+        spread = None if spread == 1 else min(spread, BATCH_LSO_MAX_SPREAD)
+    args = (mats, st, int(starts), int(rounds), int(moves), seed)
+    if spread is None:
+        tours, keys, durs, _ = ctx.tsp_batch_lso(*args, wide=batch_sa_wide(cis[0]))
+    else:
+        tours, keys, durs, _ = ctx.tsp_batch_lso_spread(*args, spread, wide=batch_sa_wide(cis[0]))
     if (keys == -1).any().item():
         raise RuntimeError("tsp_batch_lso: a request was outside the launch's contract")
     return tours.cpu().tolist(), durs.cpu().tolist()
 
 
 def solve_tsp_lso_batch(requests, *, starts: int = 64, rounds: int = 1000, moves: int = 31,
-                        seed: int = 0, device: int = 0) -> list:
+                        seed: int = 0, device: int = 0, spread=None) -> list:
     """A multi-start local search for many TSP requests, the requests sharing
     launches (spec A27): one workgroup per request, its whole matrix (static
     or hour-indexed) in LDS, `starts` steepest descents from random tours over
@@ -1713,7 +1759,9 @@ def solve_tsp_lso_batch(requests, *, starts: int = 64, rounds: int = 1000, moves
     does.  With no local GPU each request goes to solve_tsp("lso") on the GPU
     box.  The requests are grouped by (N, H, wide, starts, rounds, moves), one
     upload and one tsp_batch_lso launch per group; no customer is answered on
-    the host."""
+    the host.  `spread` is batch_lso_launch's, applied to every group's launch:
+    it changes which kernels run, never a dict."""
+    spread = check_lso_spread(spread)
     if not 1 <= int(starts) <= BATCH_LSO_MAX_STARTS:
         raise ValueError(f"starts must be in 1..{BATCH_LSO_MAX_STARTS} ({starts} given)")
     if not 0 <= int(rounds) <= BATCH_LSO_MAX_ROUNDS:
@@ -1735,8 +1783,10 @@ def solve_tsp_lso_batch(requests, *, starts: int = 64, rounds: int = 1000, moves
         reqs.append(r)
         cis.append(ci)
     if _remote() is not None:      # no local GPU: the GPU box answers each request
-        return [solve_tsp("lso", *r, seed=seed, starts=int(starts), rounds=int(rounds),
-                          moves=int(moves)) for r in reqs]
+        shared = dict(seed=seed, starts=int(starts), rounds=int(rounds), moves=int(moves))
+        if isinstance(spread, int):   # "auto" is the GPU box's own to decide
+            shared["spread"] = spread
+        return [solve_tsp("lso", *r, **shared) for r in reqs]
     out = [None] * len(cis)
     groups: dict = {}
     for x, ci in enumerate(cis):
@@ -1747,7 +1797,8 @@ def solve_tsp_lso_batch(requests, *, starts: int = 64, rounds: int = 1000, moves
     if groups:
         ctx = context(device)
         for xs in groups.values():
-            tours, durs = batch_lso_launch(ctx, [cis[x] for x in xs], starts, rounds, moves, seed)
+            tours, durs = batch_lso_launch(ctx, [cis[x] for x in xs], starts, rounds, moves, seed,
+                                           spread=spread)
             for x, tour, dur in zip(xs, tours, durs):
                 out[x] = tsp_result(cis[x], tour, dur)
     return out
