@@ -41,13 +41,24 @@ def tour_dtype(N: int):
     return torch.uint8 if N <= 256 else torch.int16
 
 
+def _u64(seed) -> int:
+    """A seed as the uint64 the C entry points take."""
+    return int(seed) & (2**64 - 1)
+
+
+def _bytes(symbol: str, *ints) -> int:
+    """The library's size function `symbol` for those arguments: each takes
+    ints and a uint64 to write the bytes to.  Host only."""
+    nbytes = ctypes.c_uint64()
+    check(getattr(_lib.load(), symbol)(*map(int, ints), ctypes.byref(nbytes)))
+    return int(nbytes.value)
+
+
 def vrp_batch_sp_lds(n: int, K: int, team: int = 0) -> int:
     """vrpms_vrp_batch_sp_lds: the dynamic-LDS bytes of a vrp_batch_sp launch
     for n customers, K vehicles and `team` threads per request (0 = the auto
     team).  Host only: needs the library, no GPU."""
-    nbytes = ctypes.c_uint64()
-    check(_lib.load().vrpms_vrp_batch_sp_lds(int(n), int(K), int(team), ctypes.byref(nbytes)))
-    return int(nbytes.value)
+    return _bytes("vrpms_vrp_batch_sp_lds", n, K, team)
 
 
 def tsp_batch_tdp_lds(n: int, H: int, W: int, team: int = 0) -> int:
@@ -55,10 +66,7 @@ def tsp_batch_tdp_lds(n: int, H: int, W: int, team: int = 0) -> int:
     launch for n customers, H hour slices (1 or 24), rows of W hour words and
     `team` threads per request (0 = the auto team).  Host only: needs the
     library, no GPU."""
-    nbytes = ctypes.c_uint64()
-    check(_lib.load().vrpms_tsp_batch_tdp_lds(int(n), int(H), int(W), int(team),
-                                              ctypes.byref(nbytes)))
-    return int(nbytes.value)
+    return _bytes("vrpms_tsp_batch_tdp_lds", n, H, W, team)
 
 
 def vrp_batch_tdsp_lds(n: int, K: int, G: int, H: int, W: int, team: int = 0) -> int:
@@ -66,10 +74,7 @@ def vrp_batch_tdsp_lds(n: int, K: int, G: int, H: int, W: int, team: int = 0) ->
     launch for n customers, K vehicles, at most G distinct start times per
     request, H hour slices (1 or 24), rows of W hour words and `team` threads
     per request (0 = the auto team).  Host only: needs the library, no GPU."""
-    nbytes = ctypes.c_uint64()
-    check(_lib.load().vrpms_vrp_batch_tdsp_lds(int(n), int(K), int(G), int(H), int(W), int(team),
-                                               ctypes.byref(nbytes)))
-    return int(nbytes.value)
+    return _bytes("vrpms_vrp_batch_tdsp_lds", n, K, G, H, W, team)
 
 
 def vrp_batch_sa_lds(N: int, K: int, H: int, wide) -> int:
@@ -77,10 +82,7 @@ def vrp_batch_sa_lds(N: int, K: int, H: int, wide) -> int:
     for N nodes, K vehicles, H hour slices (1 or 24) and a uint16 (`wide`
     false) or int32 (`wide` true) matrix.  Host only: needs the library, no
     GPU."""
-    nbytes = ctypes.c_uint64()
-    check(_lib.load().vrpms_vrp_batch_sa_lds(int(N), int(K), int(H), int(wide),
-                                             ctypes.byref(nbytes)))
-    return int(nbytes.value)
+    return _bytes("vrpms_vrp_batch_sa_lds", N, K, H, wide)
 
 
 def vrp_batch_ga_lds(N: int, K: int, H: int, wide, P: int) -> int:
@@ -88,10 +90,7 @@ def vrp_batch_ga_lds(N: int, K: int, H: int, wide, P: int) -> int:
     for N nodes, K vehicles, H hour slices (1 or 24), a uint16 (`wide` false)
     or int32 (`wide` true) matrix and a population of P.  Host only: needs the
     library, no GPU."""
-    nbytes = ctypes.c_uint64()
-    check(_lib.load().vrpms_vrp_batch_ga_lds(int(N), int(K), int(H), int(wide), int(P),
-                                             ctypes.byref(nbytes)))
-    return int(nbytes.value)
+    return _bytes("vrpms_vrp_batch_ga_lds", N, K, H, wide, P)
 
 
 def vrp_batch_aco_lds(N: int, K: int, H: int, wide, A: int) -> int:
@@ -99,10 +98,7 @@ def vrp_batch_aco_lds(N: int, K: int, H: int, wide, A: int) -> int:
     for N nodes, K vehicles, H hour slices (1 or 24), a uint16 (`wide` false)
     or int32 (`wide` true) matrix and A ants.  Host only: needs the library,
     no GPU."""
-    nbytes = ctypes.c_uint64()
-    check(_lib.load().vrpms_vrp_batch_aco_lds(int(N), int(K), int(H), int(wide), int(A),
-                                              ctypes.byref(nbytes)))
-    return int(nbytes.value)
+    return _bytes("vrpms_vrp_batch_aco_lds", N, K, H, wide, A)
 
 
 def vrp_batch_ls_lds(N: int, K: int, H: int, wide) -> int:
@@ -110,19 +106,14 @@ def vrp_batch_ls_lds(N: int, K: int, H: int, wide) -> int:
     for N nodes, K vehicles, H hour slices (1 or 24) and a uint16 (`wide`
     false) or int32 (`wide` true) matrix; never more than vrp_batch_sa_lds of
     the same shape.  Host only: needs the library, no GPU."""
-    nbytes = ctypes.c_uint64()
-    check(_lib.load().vrpms_vrp_batch_ls_lds(int(N), int(K), int(H), int(wide),
-                                             ctypes.byref(nbytes)))
-    return int(nbytes.value)
+    return _bytes("vrpms_vrp_batch_ls_lds", N, K, H, wide)
 
 
 def tsp_batch_lso_lds(N: int, H: int, wide) -> int:
     """vrpms_tsp_batch_lso_lds: the dynamic-LDS bytes of a tsp_batch_lso launch
     for N nodes, H hour slices (1 or 24) and a uint16 (`wide` false) or int32
     (`wide` true) matrix.  Host only: needs the library, no GPU."""
-    nbytes = ctypes.c_uint64()
-    check(_lib.load().vrpms_tsp_batch_lso_lds(int(N), int(H), int(wide), ctypes.byref(nbytes)))
-    return int(nbytes.value)
+    return _bytes("vrpms_tsp_batch_lso_lds", N, H, wide)
 
 
 def tsp_batch_lso_spread_lds(N: int, H: int, wide) -> int:
@@ -131,19 +122,14 @@ def tsp_batch_lso_spread_lds(N: int, H: int, wide) -> int:
     uint16 (`wide` false) or int32 (`wide` true) matrix; never more than
     tsp_batch_lso_lds of the same shape.  Host only: needs the library, no
     GPU."""
-    nbytes = ctypes.c_uint64()
-    check(_lib.load().vrpms_tsp_batch_lso_spread_lds(int(N), int(H), int(wide),
-                                                     ctypes.byref(nbytes)))
-    return int(nbytes.value)
+    return _bytes("vrpms_tsp_batch_lso_spread_lds", N, H, wide)
 
 
 def tsp_batch_lso_spread_work(R: int, N: int, G: int) -> int:
     """vrpms_tsp_batch_lso_spread_work: the workspace bytes of a
     tsp_batch_lso_spread launch of R requests at G workgroups each,
     R * G * (24 + 2 * align8(N - 1)).  Host only: needs the library, no GPU."""
-    nbytes = ctypes.c_uint64()
-    check(_lib.load().vrpms_tsp_batch_lso_spread_work(int(R), int(N), int(G), ctypes.byref(nbytes)))
-    return int(nbytes.value)
+    return _bytes("vrpms_tsp_batch_lso_spread_work", R, N, G)
 
 
 def vrp_batch_lsr_lds(N: int, K: int, H: int, wide) -> int:
@@ -151,10 +137,7 @@ def vrp_batch_lsr_lds(N: int, K: int, H: int, wide) -> int:
     for N nodes, K vehicles, H hour slices (1 or 24) and a uint16 (`wide`
     false) or int32 (`wide` true) matrix; never more than vrp_batch_sa_lds of
     the same shape.  Host only: needs the library, no GPU."""
-    nbytes = ctypes.c_uint64()
-    check(_lib.load().vrpms_vrp_batch_lsr_lds(int(N), int(K), int(H), int(wide),
-                                              ctypes.byref(nbytes)))
-    return int(nbytes.value)
+    return _bytes("vrpms_vrp_batch_lsr_lds", N, K, H, wide)
 
 
 def vrp_batch_lsr_spread_lds(N: int, K: int, H: int, wide) -> int:
@@ -163,10 +146,7 @@ def vrp_batch_lsr_spread_lds(N: int, K: int, H: int, wide) -> int:
     and a uint16 (`wide` false) or int32 (`wide` true) matrix; never more than
     vrp_batch_lsr_lds of the same shape.  Host only: needs the library, no
     GPU."""
-    nbytes = ctypes.c_uint64()
-    check(_lib.load().vrpms_vrp_batch_lsr_spread_lds(int(N), int(K), int(H), int(wide),
-                                                     ctypes.byref(nbytes)))
-    return int(nbytes.value)
+    return _bytes("vrpms_vrp_batch_lsr_spread_lds", N, K, H, wide)
 
 
 def vrp_batch_lsr_spread_work(R: int, N: int, K: int, G: int) -> int:
@@ -174,10 +154,7 @@ def vrp_batch_lsr_spread_work(R: int, N: int, K: int, G: int) -> int:
     vrp_batch_lsr_spread launch of R requests at G workgroups each,
     R * G * (16 + 2 * align8(N + K - 2)).  Host only: needs the library, no
     GPU."""
-    nbytes = ctypes.c_uint64()
-    check(_lib.load().vrpms_vrp_batch_lsr_spread_work(int(R), int(N), int(K), int(G),
-                                                      ctypes.byref(nbytes)))
-    return int(nbytes.value)
+    return _bytes("vrpms_vrp_batch_lsr_spread_work", R, N, K, G)
 
 
 def tdp_words(start: int, horizon: int) -> int:
@@ -584,6 +561,59 @@ class Context:
                 raise ValueError(f"{name} must be a contiguous int32 [R][{'N' if cols else 'K'}] "
                                  f"tensor on {self.dev}")
 
+    def _vrp_batch_args(self, mats, demand, caps, starts, wide):
+        """The batched heuristics' VRP arguments, checked: mats of rank 4,
+        demand [R][N], caps and starts [R][K] -> (mats, R, H, N, K, wide), a
+        `wide` of None answered by the device (_wide)."""
+        torch = _torch()
+        mats = self._batch_mats(torch, mats, 4)
+        R, H, N, _ = mats.shape
+        self._batch_rows(torch, demand, caps, R, N)
+        if starts.device != self.dev or starts.shape != caps.shape or starts.dtype != torch.int32 \
+                or not starts.is_contiguous():
+            raise ValueError(f"starts must be a contiguous int32 [R][K] tensor on {self.dev}")
+        return mats, R, H, N, caps.shape[1], self._wide(mats, wide)
+
+    def _tsp_batch_args(self, mats, starts, wide):
+        """The TSP counterpart: mats of rank 4 and starts [R] -> (mats, R, H, N,
+        wide)."""
+        torch = _torch()
+        mats = self._batch_mats(torch, mats, 4)
+        R, H, N, _ = mats.shape
+        if starts.device != self.dev or starts.shape != (R,) or starts.dtype != torch.int32 \
+                or not starts.is_contiguous():
+            raise ValueError(f"starts must be a contiguous int32 [R] tensor on {self.dev}")
+        return mats, R, H, N, self._wide(mats, wide)
+
+    @staticmethod
+    def _wide(mats, wide):
+        """`wide` as given, or for None whether the batch's largest entry is
+        above 65535: a question to the device, which synchronises."""
+        return (bool(mats.shape[0]) and int(mats.max().item()) > 65535) if wide is None else wide
+
+    def _batch_out(self, R: int, ntok: int, K: int | None = None, info: bool = False) -> tuple:
+        """The batched heuristics' output tensors, in the entry points' order:
+        tours int16 [R][ntok], keys int64 [R], durs int32 [R][K] ([R] without
+        a K: a TSP's), with a K veh int8 [R][ntok], with `info` info int32
+        [R][2]."""
+        torch = _torch()
+        shapes = [((R, max(ntok, 1)), torch.int16), (R, torch.int64),
+                  (R if K is None else (R, max(K, 1)), torch.int32)]
+        if K is not None:
+            shapes.append(((R, max(ntok, 1)), torch.int8))
+        if info:
+            shapes.append(((R, 2), torch.int32))
+        return tuple(torch.empty(shape, dtype=dtype, device=self.dev) for shape, dtype in shapes)
+
+    def _spread_work(self, size, R: int, shape, groups: int, nstarts: int):
+        """The workspace of a spread launch of R requests of `shape` at
+        min(groups, nstarts) workgroups each, `size` its size function ->
+        (groups as an int, the workspace, its bytes); groups outside 1..65535
+        is left to the entry point to refuse."""
+        G = int(groups)
+        nbytes = size(R, *shape, max(1, min(G, int(nstarts)))) if R and 1 <= G <= 65535 else 0
+        return G, _torch().empty(max(nbytes // 8, 1), dtype=_torch().int64, device=self.dev), nbytes
+
     def _host_minutes(self, torch, starts, shape, horizons, R: int, explicit: bool):
         """starts (of `shape`) and horizons ([R]) as int64 host arrays for the
         caller to check and upload, or None when both are int32 tensors of
@@ -753,31 +783,16 @@ class Context:
         device for the batch's largest entry, which synchronises.  The A9
         guard and non-negative demands and capacities are the caller's
         promise.  Asynchronous on the current stream."""
-        torch = _torch()
-        mats = self._batch_mats(torch, mats, 4)
-        R, H, N, _ = mats.shape
-        self._batch_rows(torch, demand, caps, R, N)
-        K = caps.shape[1]
-        if starts.device != self.dev or starts.shape != caps.shape or starts.dtype != torch.int32 \
-                or not starts.is_contiguous():
-            raise ValueError(f"starts must be a contiguous int32 [R][K] tensor on {self.dev}")
-        if inv_t0.device != self.dev or inv_t0.shape != (R,) or inv_t0.dtype != torch.float32 or \
-                not inv_t0.is_contiguous():
+        mats, R, H, N, K, wide = self._vrp_batch_args(mats, demand, caps, starts, wide)
+        if inv_t0.device != self.dev or inv_t0.shape != (R,) or \
+                inv_t0.dtype != _torch().float32 or not inv_t0.is_contiguous():
             raise ValueError(f"inv_t0 must be a contiguous float32 [R] tensor on {self.dev}")
-        if wide is None:
-            wide = bool(R) and int(mats.max().item()) > 65535
-        ntok = N - 1 + K - 1
-        tours = torch.empty((R, max(ntok, 1)), dtype=torch.int16, device=self.dev)
-        keys = torch.empty(R, dtype=torch.int64, device=self.dev)
-        durs = torch.empty((R, max(K, 1)), dtype=torch.int32, device=self.dev)
-        veh = torch.empty((R, max(ntok, 1)), dtype=torch.int8, device=self.dev)
-        check(self.lib.vrpms_vrp_batch_sa(self._ctx, mats.data_ptr(), demand.data_ptr(),
-                                          caps.data_ptr(), starts.data_ptr(), inv_t0.data_ptr(), R,
-                                          N, K, H, int(objective), int(bool(wide)), int(steps),
-                                          float(inv_alpha), int(seed) & (2**64 - 1),
-                                          tours.data_ptr(), keys.data_ptr(), durs.data_ptr(),
-                                          veh.data_ptr(), self.stream()))
-        return tours, keys, durs, veh
+        out = self._batch_out(R, N - 1 + K - 1, K)
+        check(self.lib.vrpms_vrp_batch_sa(
+            self._ctx, mats.data_ptr(), demand.data_ptr(), caps.data_ptr(), starts.data_ptr(),
+            inv_t0.data_ptr(), R, N, K, H, int(objective), int(bool(wide)), int(steps),
+            float(inv_alpha), _u64(seed), *(t.data_ptr() for t in out), self.stream()))
+        return out
 
     def vrp_batch_ga(self, mats, demand, caps, starts, objective: int, pop: int, gens: int,
                      pmut: float, seed: int, wide=None):
@@ -800,29 +815,14 @@ class Context:
         entry, which synchronises.  The A9 guard and non-negative demands and
         capacities are the caller's promise.  Asynchronous on the current
         stream."""
-        torch = _torch()
-        mats = self._batch_mats(torch, mats, 4)
-        R, H, N, _ = mats.shape
-        self._batch_rows(torch, demand, caps, R, N)
-        K = caps.shape[1]
-        if starts.device != self.dev or starts.shape != caps.shape or starts.dtype != torch.int32 \
-                or not starts.is_contiguous():
-            raise ValueError(f"starts must be a contiguous int32 [R][K] tensor on {self.dev}")
-        if wide is None:
-            wide = bool(R) and int(mats.max().item()) > 65535
+        mats, R, H, N, K, wide = self._vrp_batch_args(mats, demand, caps, starts, wide)
         pm = min(int(round(float(pmut) * 2**32)), 2**32 - 1)
-        n = N - 1
-        tours = torch.empty((R, max(n, 1)), dtype=torch.int16, device=self.dev)
-        keys = torch.empty(R, dtype=torch.int64, device=self.dev)
-        durs = torch.empty((R, max(K, 1)), dtype=torch.int32, device=self.dev)
-        veh = torch.empty((R, max(n, 1)), dtype=torch.int8, device=self.dev)
-        check(self.lib.vrpms_vrp_batch_ga(self._ctx, mats.data_ptr(), demand.data_ptr(),
-                                          caps.data_ptr(), starts.data_ptr(), R, N, K, H,
-                                          int(objective), int(bool(wide)), int(pop), int(gens), pm,
-                                          int(seed) & (2**64 - 1), tours.data_ptr(),
-                                          keys.data_ptr(), durs.data_ptr(), veh.data_ptr(),
-                                          self.stream()))
-        return tours, keys, durs, veh
+        out = self._batch_out(R, N - 1, K)
+        check(self.lib.vrpms_vrp_batch_ga(
+            self._ctx, mats.data_ptr(), demand.data_ptr(), caps.data_ptr(), starts.data_ptr(), R, N,
+            K, H, int(objective), int(bool(wide)), int(pop), int(gens), pm, _u64(seed),
+            *(t.data_ptr() for t in out), self.stream()))
+        return out
 
     def vrp_batch_aco(self, mats, demand, caps, starts, objective: int, ants: int, iters: int,
                       seed: int, wide=None, tau0: int = 1 << 24, tau_min: int = 1 << 12,
@@ -847,32 +847,17 @@ class Context:
         entry, which synchronises.  The A9 guard and non-negative demands and
         capacities are the caller's promise.  Asynchronous on the current
         stream."""
-        torch = _torch()
-        mats = self._batch_mats(torch, mats, 4)
-        R, H, N, _ = mats.shape
-        self._batch_rows(torch, demand, caps, R, N)
-        K = caps.shape[1]
-        if starts.device != self.dev or starts.shape != caps.shape or starts.dtype != torch.int32 \
-                or not starts.is_contiguous():
-            raise ValueError(f"starts must be a contiguous int32 [R][K] tensor on {self.dev}")
+        mats, R, H, N, K, wide = self._vrp_batch_args(mats, demand, caps, starts, wide)
         for name, v in (("tau0", tau0), ("tau_min", tau_min), ("tau_max", tau_max)):
             if not 0 <= int(v) < 2**32:
                 raise ValueError(f"{name} must be a uint32")
-        if wide is None:
-            wide = bool(R) and int(mats.max().item()) > 65535
-        n = N - 1
-        tours = torch.empty((R, max(n, 1)), dtype=torch.int16, device=self.dev)
-        keys = torch.empty(R, dtype=torch.int64, device=self.dev)
-        durs = torch.empty((R, max(K, 1)), dtype=torch.int32, device=self.dev)
-        veh = torch.empty((R, max(n, 1)), dtype=torch.int8, device=self.dev)
-        check(self.lib.vrpms_vrp_batch_aco(self._ctx, mats.data_ptr(), demand.data_ptr(),
-                                           caps.data_ptr(), starts.data_ptr(), R, N, K, H,
-                                           int(objective), int(bool(wide)), int(ants), int(iters),
-                                           int(tau0), int(tau_min), int(tau_max), int(evap_shift),
-                                           int(bsf_period), int(seed) & (2**64 - 1),
-                                           tours.data_ptr(), keys.data_ptr(), durs.data_ptr(),
-                                           veh.data_ptr(), self.stream()))
-        return tours, keys, durs, veh
+        out = self._batch_out(R, N - 1, K)
+        check(self.lib.vrpms_vrp_batch_aco(
+            self._ctx, mats.data_ptr(), demand.data_ptr(), caps.data_ptr(), starts.data_ptr(), R, N,
+            K, H, int(objective), int(bool(wide)), int(ants), int(iters), int(tau0), int(tau_min),
+            int(tau_max), int(evap_shift), int(bsf_period), _u64(seed),
+            *(t.data_ptr() for t in out), self.stream()))
+        return out
 
     def vrp_batch_ls(self, mats, demand, caps, starts, objective: int, nstarts: int, rounds: int,
                      seed: int, wide=None):
@@ -896,29 +881,13 @@ class Context:
         asks the device for the batch's largest entry, which synchronises.
         The A9 guard and non-negative demands and capacities are the caller's
         promise.  Asynchronous on the current stream."""
-        torch = _torch()
-        mats = self._batch_mats(torch, mats, 4)
-        R, H, N, _ = mats.shape
-        self._batch_rows(torch, demand, caps, R, N)
-        K = caps.shape[1]
-        if starts.device != self.dev or starts.shape != caps.shape or starts.dtype != torch.int32 \
-                or not starts.is_contiguous():
-            raise ValueError(f"starts must be a contiguous int32 [R][K] tensor on {self.dev}")
-        if wide is None:
-            wide = bool(R) and int(mats.max().item()) > 65535
-        n = N - 1
-        tours = torch.empty((R, max(n, 1)), dtype=torch.int16, device=self.dev)
-        keys = torch.empty(R, dtype=torch.int64, device=self.dev)
-        durs = torch.empty((R, max(K, 1)), dtype=torch.int32, device=self.dev)
-        veh = torch.empty((R, max(n, 1)), dtype=torch.int8, device=self.dev)
-        info = torch.empty((R, 2), dtype=torch.int32, device=self.dev)
-        check(self.lib.vrpms_vrp_batch_ls(self._ctx, mats.data_ptr(), demand.data_ptr(),
-                                          caps.data_ptr(), starts.data_ptr(), R, N, K, H,
-                                          int(objective), int(bool(wide)), int(nstarts), int(rounds),
-                                          int(seed) & (2**64 - 1), tours.data_ptr(),
-                                          keys.data_ptr(), durs.data_ptr(), veh.data_ptr(),
-                                          info.data_ptr(), self.stream()))
-        return tours, keys, durs, veh, info
+        mats, R, H, N, K, wide = self._vrp_batch_args(mats, demand, caps, starts, wide)
+        out = self._batch_out(R, N - 1, K, info=True)
+        check(self.lib.vrpms_vrp_batch_ls(
+            self._ctx, mats.data_ptr(), demand.data_ptr(), caps.data_ptr(), starts.data_ptr(), R, N,
+            K, H, int(objective), int(bool(wide)), int(nstarts), int(rounds), _u64(seed),
+            *(t.data_ptr() for t in out), self.stream()))
+        return out
 
     def tsp_batch_lso(self, mats, starts, nstarts: int, rounds: int, moves: int, seed: int,
                       wide=None):
@@ -942,25 +911,12 @@ class Context:
         info = (-1, 0)), True as int32; None -- the default -- asks the device
         for the batch's largest entry, which synchronises.  The A9 guard is
         the caller's promise.  Asynchronous on the current stream."""
-        torch = _torch()
-        mats = self._batch_mats(torch, mats, 4)
-        R, H, N, _ = mats.shape
-        if starts.device != self.dev or starts.shape != (R,) or starts.dtype != torch.int32 \
-                or not starts.is_contiguous():
-            raise ValueError(f"starts must be a contiguous int32 [R] tensor on {self.dev}")
-        if wide is None:
-            wide = bool(R) and int(mats.max().item()) > 65535
-        n = N - 1
-        tours = torch.empty((R, max(n, 1)), dtype=torch.int16, device=self.dev)
-        keys = torch.empty(R, dtype=torch.int64, device=self.dev)
-        durs = torch.empty(R, dtype=torch.int32, device=self.dev)
-        info = torch.empty((R, 2), dtype=torch.int32, device=self.dev)
-        check(self.lib.vrpms_tsp_batch_lso(self._ctx, mats.data_ptr(), starts.data_ptr(), R, N, H,
-                                           int(bool(wide)), int(nstarts), int(rounds), int(moves),
-                                           int(seed) & (2**64 - 1), tours.data_ptr(),
-                                           keys.data_ptr(), durs.data_ptr(), info.data_ptr(),
-                                           self.stream()))
-        return tours, keys, durs, info
+        mats, R, H, N, wide = self._tsp_batch_args(mats, starts, wide)
+        out = self._batch_out(R, N - 1, info=True)
+        check(self.lib.vrpms_tsp_batch_lso(
+            self._ctx, mats.data_ptr(), starts.data_ptr(), R, N, H, int(bool(wide)), int(nstarts),
+            int(rounds), int(moves), _u64(seed), *(t.data_ptr() for t in out), self.stream()))
+        return out
 
     def tsp_batch_lso_spread(self, mats, starts, nstarts: int, rounds: int, moves: int, seed: int,
                              groups: int, wide=None):
@@ -973,28 +929,14 @@ class Context:
         workspace (tsp_batch_lso_spread_work) is allocated here, from torch's
         caching allocator, which keeps it alive for the stream's queued work.
         Asynchronous on the current stream."""
-        torch = _torch()
-        mats = self._batch_mats(torch, mats, 4)
-        R, H, N, _ = mats.shape
-        if starts.device != self.dev or starts.shape != (R,) or starts.dtype != torch.int32 \
-                or not starts.is_contiguous():
-            raise ValueError(f"starts must be a contiguous int32 [R] tensor on {self.dev}")
-        if wide is None:
-            wide = bool(R) and int(mats.max().item()) > 65535
-        n = N - 1
-        G = int(groups)
-        work_bytes = tsp_batch_lso_spread_work(R, N, max(1, min(G, int(nstarts)))) \
-            if R and 1 <= G <= 65535 else 0
-        work = torch.empty(max(work_bytes // 8, 1), dtype=torch.int64, device=self.dev)
-        tours = torch.empty((R, max(n, 1)), dtype=torch.int16, device=self.dev)
-        keys = torch.empty(R, dtype=torch.int64, device=self.dev)
-        durs = torch.empty(R, dtype=torch.int32, device=self.dev)
-        info = torch.empty((R, 2), dtype=torch.int32, device=self.dev)
+        mats, R, H, N, wide = self._tsp_batch_args(mats, starts, wide)
+        G, work, work_bytes = self._spread_work(tsp_batch_lso_spread_work, R, (N,), groups, nstarts)
+        out = self._batch_out(R, N - 1, info=True)
         check(self.lib.vrpms_tsp_batch_lso_spread(
             self._ctx, mats.data_ptr(), starts.data_ptr(), R, N, H, int(bool(wide)), int(nstarts),
-            int(rounds), int(moves), int(seed) & (2**64 - 1), G, work.data_ptr(), work_bytes,
-            tours.data_ptr(), keys.data_ptr(), durs.data_ptr(), info.data_ptr(), self.stream()))
-        return tours, keys, durs, info
+            int(rounds), int(moves), _u64(seed), G, work.data_ptr(), work_bytes,
+            *(t.data_ptr() for t in out), self.stream()))
+        return out
 
     def vrp_batch_lsr(self, mats, demand, caps, starts, objective: int, nstarts: int, rounds: int,
                       seed: int, wide=None):
@@ -1019,29 +961,13 @@ class Context:
         which synchronises.  The A9 guard and non-negative demands and
         capacities are the caller's promise.  Asynchronous on the current
         stream."""
-        torch = _torch()
-        mats = self._batch_mats(torch, mats, 4)
-        R, H, N, _ = mats.shape
-        self._batch_rows(torch, demand, caps, R, N)
-        K = caps.shape[1]
-        if starts.device != self.dev or starts.shape != caps.shape or starts.dtype != torch.int32 \
-                or not starts.is_contiguous():
-            raise ValueError(f"starts must be a contiguous int32 [R][K] tensor on {self.dev}")
-        if wide is None:
-            wide = bool(R) and int(mats.max().item()) > 65535
-        L = N - 1 + K - 1
-        tours = torch.empty((R, max(L, 1)), dtype=torch.int16, device=self.dev)
-        keys = torch.empty(R, dtype=torch.int64, device=self.dev)
-        durs = torch.empty((R, max(K, 1)), dtype=torch.int32, device=self.dev)
-        veh = torch.empty((R, max(L, 1)), dtype=torch.int8, device=self.dev)
-        info = torch.empty((R, 2), dtype=torch.int32, device=self.dev)
-        check(self.lib.vrpms_vrp_batch_lsr(self._ctx, mats.data_ptr(), demand.data_ptr(),
-                                           caps.data_ptr(), starts.data_ptr(), R, N, K, H,
-                                           int(objective), int(bool(wide)), int(nstarts), int(rounds),
-                                           int(seed) & (2**64 - 1), tours.data_ptr(),
-                                           keys.data_ptr(), durs.data_ptr(), veh.data_ptr(),
-                                           info.data_ptr(), self.stream()))
-        return tours, keys, durs, veh, info
+        mats, R, H, N, K, wide = self._vrp_batch_args(mats, demand, caps, starts, wide)
+        out = self._batch_out(R, N - 1 + K - 1, K, info=True)
+        check(self.lib.vrpms_vrp_batch_lsr(
+            self._ctx, mats.data_ptr(), demand.data_ptr(), caps.data_ptr(), starts.data_ptr(), R, N,
+            K, H, int(objective), int(bool(wide)), int(nstarts), int(rounds), _u64(seed),
+            *(t.data_ptr() for t in out), self.stream()))
+        return out
 
     def vrp_batch_lsr_spread(self, mats, demand, caps, starts, objective: int, nstarts: int,
                              rounds: int, seed: int, groups: int, wide=None):
@@ -1054,32 +980,15 @@ class Context:
         workspace (vrp_batch_lsr_spread_work) is allocated here, from torch's
         caching allocator, which keeps it alive for the stream's queued work.
         Asynchronous on the current stream."""
-        torch = _torch()
-        mats = self._batch_mats(torch, mats, 4)
-        R, H, N, _ = mats.shape
-        self._batch_rows(torch, demand, caps, R, N)
-        K = caps.shape[1]
-        if starts.device != self.dev or starts.shape != caps.shape or starts.dtype != torch.int32 \
-                or not starts.is_contiguous():
-            raise ValueError(f"starts must be a contiguous int32 [R][K] tensor on {self.dev}")
-        if wide is None:
-            wide = bool(R) and int(mats.max().item()) > 65535
-        L = N - 1 + K - 1
-        G = int(groups)
-        work_bytes = vrp_batch_lsr_spread_work(R, N, K, max(1, min(G, int(nstarts)))) \
-            if R and 1 <= G <= 65535 else 0
-        work = torch.empty(max(work_bytes // 8, 1), dtype=torch.int64, device=self.dev)
-        tours = torch.empty((R, max(L, 1)), dtype=torch.int16, device=self.dev)
-        keys = torch.empty(R, dtype=torch.int64, device=self.dev)
-        durs = torch.empty((R, max(K, 1)), dtype=torch.int32, device=self.dev)
-        veh = torch.empty((R, max(L, 1)), dtype=torch.int8, device=self.dev)
-        info = torch.empty((R, 2), dtype=torch.int32, device=self.dev)
+        mats, R, H, N, K, wide = self._vrp_batch_args(mats, demand, caps, starts, wide)
+        G, work, work_bytes = self._spread_work(vrp_batch_lsr_spread_work, R, (N, K), groups,
+                                                nstarts)
+        out = self._batch_out(R, N - 1 + K - 1, K, info=True)
         check(self.lib.vrpms_vrp_batch_lsr_spread(
             self._ctx, mats.data_ptr(), demand.data_ptr(), caps.data_ptr(), starts.data_ptr(), R, N,
-            K, H, int(objective), int(bool(wide)), int(nstarts), int(rounds),
-            int(seed) & (2**64 - 1), G, work.data_ptr(), work_bytes, tours.data_ptr(),
-            keys.data_ptr(), durs.data_ptr(), veh.data_ptr(), info.data_ptr(), self.stream()))
-        return tours, keys, durs, veh, info
+            K, H, int(objective), int(bool(wide)), int(nstarts), int(rounds), _u64(seed), G,
+            work.data_ptr(), work_bytes, *(t.data_ptr() for t in out), self.stream()))
+        return out
 
     def set_batch_dp_team(self, T: int):
         """Threads per request of tsp_batch_dp: 0 = auto (the n -> T table),

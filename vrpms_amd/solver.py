@@ -36,7 +36,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import runners
+from . import core, runners
 from .core import CVRP, OBJ_MAX, OBJ_SUM, TSP, Context
 
 ALGORITHMS = ("bf", "ga", "sa", "aco", "dp", "sp", "tdp", "tdsp", "ls", "lsr", "lso")
@@ -578,25 +578,15 @@ def solve_tsp(algorithm: str, durations, customers, start_node, start_time=0, *,
         _check_tdp(ci, knobs.get("upper_bound"))
     if algorithm == "lso":
         ci = compact_tsp(durations, customers, start_node, start_time)
-        lso = (64 if knobs.get("starts") is None else int(knobs["starts"]),
-               1000 if knobs.get("rounds") is None else int(knobs["rounds"]),
-               31 if knobs.get("moves") is None else int(knobs["moves"]))
-        lso_spread = check_lso_spread(knobs.get("spread"))
-        if isinstance(lso_spread, int):   # only a number travels to a GPU box as a knob
-            knobs["spread"] = lso_spread
-        else:
-            knobs.pop("spread", None)
-        _check_lso(ci, *lso)
+        lso = _single_knobs("lso", ci, knobs)
         if ci.n == 0:              # no customer: answered on the host
-            return tsp_result(ci, [], _td_duration(ci, []))
+            return _heuristic_result(ci, None)
     rem = _remote()
     if rem is not None:
         return rem.solve_tsp(algorithm, durations, customers, start_node, start_time, seed=seed,
                              time_limit=time_limit, **knobs)
     if algorithm == "lso":         # a one-request tsp_batch_lso launch on one device
-        tours, durs = batch_lso_launch(context(devices[0] if devices else device), [ci], *lso, seed,
-                                       spread=lso_spread)
-        return tsp_result(ci, tours[0], durs[0])
+        return _solve_single("lso", ci, *lso, seed, devices[0] if devices else device)
     if ci is None:
         ci = compact_tsp(durations, customers, start_node, start_time)
     ctx, tour = _searched(ci, algorithm, seed, time_limit, device, devices, OBJ_SUM, knobs)
@@ -654,27 +644,12 @@ def solve_vrp(algorithm: str, durations, locations, capacities, start_times,
         ci = compact_vrp(durations, locations, capacities, start_times, ignored_customers,
                          completed_customers)
         _check_tdsp(ci, OBJ_MAX if objective == "max" else OBJ_SUM, knobs.get("upper_bound"))
-    if algorithm == "ls":
+    if algorithm in ("ls", "lsr"):
         if objective not in ("sum", "max"):
             raise ValueError("objective must be 'sum' or 'max'")
         ci = compact_vrp(durations, locations, capacities, start_times, ignored_customers,
                          completed_customers)
-        ls_starts = 64 if knobs.get("starts") is None else int(knobs["starts"])
-        ls_rounds = 1000 if knobs.get("rounds") is None else int(knobs["rounds"])
-        _check_ls(ci, ls_starts, ls_rounds)
-    if algorithm == "lsr":
-        if objective not in ("sum", "max"):
-            raise ValueError("objective must be 'sum' or 'max'")
-        ci = compact_vrp(durations, locations, capacities, start_times, ignored_customers,
-                         completed_customers)
-        ls_starts = 64 if knobs.get("starts") is None else int(knobs["starts"])
-        ls_rounds = 1000 if knobs.get("rounds") is None else int(knobs["rounds"])
-        ls_spread = check_lsr_spread(knobs.get("spread"))
-        if isinstance(ls_spread, int):   # only a number travels to a GPU box as a knob
-            knobs["spread"] = ls_spread
-        else:
-            knobs.pop("spread", None)
-        _check_lsr(ci, ls_starts, ls_rounds)
+        ls = _single_knobs(algorithm, ci, knobs)
     rem = _remote()
     if rem is not None:
         out = rem.solve_vrp(algorithm, durations, locations, capacities, start_times,
@@ -686,18 +661,9 @@ def solve_vrp(algorithm: str, durations, locations, capacities, start_times,
                                            completed_customers)
             out["unvisited"] = [c for c in nodes[1:] if c not in served]
         return out
-    if algorithm == "ls":          # a one-request vrp_batch_ls launch on one device
-        if ci.n == 0:
-            return sa_result(ci, [], [], [0] * len(ci.capacities), with_unvisited)
-        rows = batch_ls_launch(context(devices[0] if devices else device), [ci], ls_starts,
-                               ls_rounds, seed, objective)
-        return sa_result(ci, rows[0][0], rows[1][0], rows[2][0], with_unvisited)
-    if algorithm == "lsr":         # a one-request vrp_batch_lsr launch on one device
-        if ci.n == 0:
-            return sa_result(ci, [], [], [0] * len(ci.capacities), with_unvisited)
-        rows = batch_lsr_launch(context(devices[0] if devices else device), [ci], ls_starts,
-                                ls_rounds, seed, objective, spread=ls_spread)
-        return sa_result(ci, rows[0][0], rows[1][0], rows[2][0], with_unvisited)
+    if algorithm in ("ls", "lsr"):   # a one-request launch on one device
+        return _solve_single(algorithm, ci, *ls, seed, devices[0] if devices else device, objective,
+                             with_unvisited)
     if ci is None:
         ci = compact_vrp(durations, locations, capacities, start_times, ignored_customers,
                          completed_customers)
@@ -903,6 +869,13 @@ def batch_tdsp_fits(ci: CompactInstance, bound) -> bool:
     return vrp_batch_tdsp_lds(ci.n, K, len(set(starts)), H, W) <= BATCH_TDSP_LDS_BYTES
 
 
+def _check_contract(kernel: str, keys):
+    """An all-ones key after a launch of requests that passed the host's
+    checks: the kernel refused what the host let through."""
+    if (keys == -1).any().item():
+        raise RuntimeError(f"{kernel}: a request was outside the launch's contract")
+
+
 def batch_tdsp_launch(ctx: Context, cis, bounds, objective: str = "sum"):
     """One upload and one vrp_batch_tdsp launch for compact instances of one
     (N, K, H, number of distinct starts) (each passed batch_sp_guard and
@@ -915,8 +888,7 @@ def batch_tdsp_launch(ctx: Context, cis, bounds, objective: str = "sum"):
     tours, keys, durs = ctx.vrp_batch_tdsp(*_stage(ctx, cis, hours=True), starts,
                                            np.array([int(b) for b in bounds], dtype=np.int64),
                                            OBJ_MAX if objective == "max" else OBJ_SUM, G=G, W=W)
-    if (keys == -1).any().item():
-        raise RuntimeError("vrp_batch_tdsp: a request was outside the launch's contract")
+    _check_contract("vrp_batch_tdsp", keys)
     return tours.cpu().tolist(), durs.cpu().tolist()
 
 
@@ -1110,6 +1082,274 @@ def solve_vrp_tdsp_batch(requests, *, objective: str = "sum", with_unvisited: bo
 
 
 # ---------------------------------------------------------------------------
+# batched heuristics (A22-A27): one table, one domain, one launch and one loop
+# ---------------------------------------------------------------------------
+@dataclass(frozen=True)
+class Knob:
+    """A knob of a batched heuristic that its domain caps."""
+    name: str            # as solve_vrp / solve_tsp take it: the name it travels under
+    lo: int
+    hi: int
+    default: int = 0     # solve_vrp's / solve_tsp's, where the launch is their only path
+    takes: str = "{}..{}"  # the domain message's words for the range
+
+
+@dataclass(frozen=True)
+class HeuristicKind:
+    """What one batched heuristic does differently from the others."""
+    # TSP or CVRP: _tsp_request, compact_tsp, solve_tsp and tsp_result, or
+    # _sp_request, compact_vrp, solve_vrp and sa_result
+    problem: int
+    # the Context method and the contract error's name; core's "<kernel>_lds"
+    # sizes one request, and lds_bytes is what that may be
+    kernel: str
+    lds_bytes: int
+    # the capped knobs, in the order the key, the domain and the launch take
+    # them; "<kernel>_lds" takes the first lds_knobs of them after the shape
+    knobs: tuple = ()
+    lds_knobs: int = 0
+    # a request outside the domain raises the domain's message (there is no
+    # other path); else it takes the single-request solver
+    strict: bool = False
+    # the tours carry K - 1 separators, and have a token limit
+    separators: bool = False
+    # "<kernel>_spread" takes up to that many workgroups per request; 0: no such form
+    max_spread: int = 0
+    # _check_heuristic applies the int32 guard to a request of no customer
+    guard_empty: bool = False
+    # (ctx, cis, *the launch's knobs) -> (device buffers after the starts,
+    # scalars after the objective); None: no buffer, int(knob) each
+    launch_args: object = None
+
+
+def _ls_knobs(max_starts: int, max_rounds: int, *more) -> tuple:
+    """The local searches' `starts` and `rounds` at an algorithm's caps."""
+    return (Knob("starts", 1, max_starts, 64, "{}..{} starts"),
+            Knob("rounds", 0, max_rounds, 1000, "{}..{} rounds")) + more
+
+
+def _sa_launch_args(ctx: Context, cis, steps):
+    """vrp_batch_sa's own arguments: every request on its batch_sa_schedule."""
+    import torch
+    sched = [batch_sa_schedule(ci, steps) for ci in cis]
+    inv_t0 = torch.from_numpy(np.array([s[0] for s in sched], dtype=np.float32)).to(ctx.dev)
+    return (inv_t0,), (int(steps), sched[0][1])
+
+
+# guard_empty: on solve_tsp's path "lso" applies the A9 guard to a request of no
+# customer, on solve_vrp's "ls" and "lsr" return before it.  The table keeps
+# what each did when it was written; which of the two is meant is an open question
+HEURISTIC_KINDS = {
+    "sa": HeuristicKind(CVRP, "vrp_batch_sa", BATCH_SA_LDS_BYTES, launch_args=_sa_launch_args),
+    "ga": HeuristicKind(CVRP, "vrp_batch_ga", BATCH_GA_LDS_BYTES,
+                        (Knob("random_permutation_count", 2, BATCH_GA_MAX_POP),
+                         Knob("iteration_count", 0, BATCH_GA_MAX_GENERATIONS)), lds_knobs=1,
+                        launch_args=lambda ctx, cis, pop, gens, pmut:
+                        ((), (int(pop), int(gens), float(pmut)))),
+    "aco": HeuristicKind(CVRP, "vrp_batch_aco", BATCH_ACO_LDS_BYTES,
+                         (Knob("ants", 1, BATCH_ACO_MAX_ANTS),
+                          Knob("iteration_count", 1, BATCH_ACO_MAX_ITERATIONS)), lds_knobs=1),
+    "ls": HeuristicKind(CVRP, "vrp_batch_ls", BATCH_LS_LDS_BYTES,
+                        _ls_knobs(BATCH_LS_MAX_STARTS, BATCH_LS_MAX_ROUNDS), strict=True),
+    "lsr": HeuristicKind(CVRP, "vrp_batch_lsr", BATCH_LSR_LDS_BYTES,
+                         _ls_knobs(BATCH_LSR_MAX_STARTS, BATCH_LSR_MAX_ROUNDS), strict=True,
+                         separators=True, max_spread=BATCH_LSR_MAX_SPREAD),
+    "lso": HeuristicKind(TSP, "tsp_batch_lso", BATCH_LSO_LDS_BYTES,
+                         _ls_knobs(BATCH_LSO_MAX_STARTS, BATCH_LSO_MAX_ROUNDS,
+                                   Knob("moves", 1, 31, 31, "a move mask of {}..{}")), strict=True,
+                         max_spread=BATCH_LSO_MAX_SPREAD, guard_empty=True),
+}
+
+
+def _domain_message(algorithm: str, ci: CompactInstance, knobs, empty_ok: bool = False):
+    """The limit of the algorithm's domain this request fails -> its message,
+    or None: the problem, the knobs' ranges, at least one customer (unless
+    `empty_ok`) and at most 65534, 1..64 vehicles, a static or 24-slice matrix,
+    the token limit of separator tours, and the LDS bytes of one request
+    (uint16 cells unless an entry is above 65535).  Where a request outside
+    the domain has another path the message is only a verdict.  Needs the
+    library, no GPU."""
+    kind = HEURISTIC_KINDS[algorithm]
+    tsp = kind.problem == TSP
+    what = f"{algorithm} (local search)" if kind.strict else algorithm
+    if ci.problem != kind.problem:
+        return f"{algorithm} solves the {'TSP' if tsp else 'VRP'} only"
+    for k, v in zip(kind.knobs, knobs):
+        if not k.lo <= int(v) <= k.hi:
+            return f"{what} takes {k.takes.format(k.lo, k.hi)} ({v} given)"
+    if ci.n < 1:
+        return None if empty_ok else f"{what} needs at least one customer"
+    if ci.N > 65535:
+        return f"{what} supports at most 65534 customers ({ci.n} given)"
+    N, K, H, wide = ci.N, 1 if tsp else len(ci.capacities), ci.durations.shape[0], batch_sa_wide(ci)
+    if not 1 <= K <= BATCH_SA_MAX_VEHICLES:
+        return f"{what} supports 1..{BATCH_SA_MAX_VEHICLES} vehicles ({K} given)"
+    if H not in (1, 24):
+        return f"{what} needs a static or 24-slice duration matrix ({H} slices given)"
+    if kind.separators and N + K - 2 > 65535:
+        return f"{what} supports at most 65535 tokens ({N + K - 2} given)"
+    shape = (N, H, wide) if tsp else (N, K, H, wide)
+    need = getattr(core, kind.kernel + "_lds")(*shape, *map(int, knobs[:kind.lds_knobs]))
+    if need > kind.lds_bytes:
+        held = f"matrix in LDS: {ci.n} customers" if tsp else \
+            f"instance in LDS: {ci.n} customers, {K} vehicles"
+        return (f"{what} keeps the {held} and {H} hour slice(s) of "
+                f"{'int32' if wide else 'uint16'} cells need {need} bytes; the limit is "
+                f"{kind.lds_bytes} bytes")
+    return None
+
+
+def _check_heuristic(algorithm: str, ci: CompactInstance, knobs):
+    """solve_vrp's / solve_tsp's check where the launch is the only path: the
+    domain's message first, then the int32 guards; no customer is inside."""
+    msg = _domain_message(algorithm, ci, knobs, empty_ok=True)
+    if msg is None and (ci.n or HEURISTIC_KINDS[algorithm].guard_empty):
+        msg = batch_guard_message(ci)
+    if msg is not None:
+        raise ValueError(msg)
+
+
+def _check_spread(spread, cap: int):
+    """-> None, "auto" or an int in 1..cap; anything else is a ValueError."""
+    if spread is None or (isinstance(spread, str) and spread == "auto"):
+        return spread
+    if isinstance(spread, (int, np.integer)) and not isinstance(spread, bool) and \
+            1 <= int(spread) <= cap:
+        return int(spread)
+    raise ValueError(f'spread must be None, "auto" or an integer in 1..{cap} ({spread!r} given)')
+
+
+def _auto_spread(R: int, S: int, cus: int) -> int:
+    """min(S, max(1, 16 cus // R)) workgroups per request."""
+    return min(int(S), max(1, (16 * int(cus)) // max(int(R), 1)))
+
+
+def _heuristic_launch(algorithm: str, ctx: Context, cis, knobs, seed: int, objective: str = "sum",
+                      spread=None):
+    """One upload and one launch of the algorithm's kernel -- of its spread
+    form when `spread` says so -- for compact instances of one key -> the rows
+    as lists: (tours, veh, durs) for a VRP, (tours, durs) for a TSP."""
+    import torch
+    kind = HEURISTIC_KINDS[algorithm]
+    vrp = kind.problem == CVRP
+    if kind.max_spread:
+        spread = _check_spread(spread, kind.max_spread)
+    bufs = _stage(ctx, cis, hours=True)
+    st = [ci.start_times if vrp else int(ci.start_times[0]) for ci in cis]
+    bufs.append(torch.from_numpy(np.array(st, dtype=np.int32)).to(ctx.dev))
+    more, scalars = kind.launch_args(ctx, cis, *knobs) if kind.launch_args else \
+        ((), [int(k) for k in knobs])
+    if spread == "auto":
+        spread = _auto_spread(len(cis), int(knobs[0]), ctx.cus)
+        spread = None if spread == 1 else min(spread, kind.max_spread)
+    method = getattr(ctx, kind.kernel if spread is None else kind.kernel + "_spread")
+    out = method(*bufs, *more, *([OBJ_MAX if objective == "max" else OBJ_SUM] if vrp else []),
+                 *scalars, seed, *([] if spread is None else [spread]), wide=batch_sa_wide(cis[0]))
+    _check_contract(kind.kernel, out[1])
+    rows = (out[0], out[3], out[2]) if vrp else (out[0], out[2])
+    return tuple(t.cpu().tolist() for t in rows)
+
+
+def _launch(algorithm: str, ctx, cis, knobs, seed, objective, spread):
+    """batch_<algorithm>_launch as the module has it when called (a caller may
+    have put its own there), with the arguments that one takes."""
+    kind = HEURISTIC_KINDS[algorithm]
+    args = tuple(knobs) + (seed,) + ((objective,) if kind.problem == CVRP else ())
+    more = dict(spread=spread) if kind.max_spread else {}
+    return globals()[f"batch_{algorithm}_launch"](ctx, cis, *args, **more)
+
+
+def _heuristic_result(ci: CompactInstance, row, with_unvisited: bool = False) -> dict:
+    """The slot dict from one request's rows of a launch; for no customer
+    (`row` None) the trivial one, built on the host."""
+    if ci.problem == TSP:
+        return tsp_result(ci, *(([], _td_duration(ci, [])) if row is None else row))
+    return sa_result(ci, *(([], [], [0] * len(ci.capacities)) if row is None else row),
+                     with_unvisited)
+
+
+def _single_knobs(algorithm: str, ci: CompactInstance, knobs: dict):
+    """solve_vrp's / solve_tsp's host side of a one-request launch: the knobs'
+    values or their defaults, `spread` checked and kept in `knobs` only as a
+    number, then _check_heuristic -> (values, spread)."""
+    kind = HEURISTIC_KINDS[algorithm]
+    values = tuple(k.default if knobs.get(k.name) is None else int(knobs[k.name])
+                   for k in kind.knobs)
+    spread = None
+    if kind.max_spread:
+        spread = _check_spread(knobs.get("spread"), kind.max_spread)
+        if isinstance(spread, int):   # only a number travels to a GPU box as a knob
+            knobs["spread"] = spread
+        else:
+            knobs.pop("spread", None)
+    _check_heuristic(algorithm, ci, values)
+    return values, spread
+
+
+def _solve_single(algorithm: str, ci: CompactInstance, values, spread, seed, device,
+                  objective=None, with_unvisited: bool = False) -> dict:
+    """One checked request on a one-request launch; no customer on the host."""
+    if ci.n == 0:
+        return _heuristic_result(ci, None, with_unvisited)
+    rows = _launch(algorithm, context(device), [ci], values, seed, objective, spread)
+    return _heuristic_result(ci, [r[0] for r in rows], with_unvisited)
+
+
+def _solve_heuristic_batch(algorithm: str, requests, knobs, seed, device, objective=None,
+                           with_unvisited: bool = False, spread=None, launch_knobs=None) -> list:
+    """The heuristics' batch entry points' one loop, after each has checked its
+    own knobs: every request normalised, compacted and guarded on the host,
+    and held against the domain where that is strict (a bad one raises with
+    its index); with no local GPU each goes to the GPU box; else no customer is
+    answered on the host, the requests inside the domain share one launch per
+    key, and the rest take the single-request solver.  `knobs` are the
+    table's, `launch_knobs` what the launch takes in their place."""
+    kind = HEURISTIC_KINDS[algorithm]
+    tsp = kind.problem == TSP
+    request, compact, single = (_tsp_request, compact_tsp, solve_tsp) if tsp else \
+        (_sp_request, compact_vrp, solve_vrp)
+    reqs, cis = [], []
+    for x, r in enumerate(requests):
+        try:
+            r, _ = request(r)
+            ci = compact(*r)
+            msg = batch_guard_message(ci)
+            if msg is None and ci.n and kind.strict:
+                msg = _domain_message(algorithm, ci, knobs)
+            if msg is not None:
+                raise ValueError(msg)
+        except ValueError as e:
+            raise ValueError(f"request {x}: {e}") from None
+        reqs.append(r)
+        cis.append(ci)
+    shared = dict(seed=seed) if tsp else \
+        dict(seed=seed, objective=objective, with_unvisited=with_unvisited)
+    shared.update((k.name, int(v)) for k, v in zip(kind.knobs, knobs))
+    if isinstance(spread, int):    # "auto" is the GPU box's own to decide
+        shared["spread"] = spread
+    if _remote() is not None:      # no local GPU: the GPU box answers each request
+        return [single(algorithm, *r, **shared) for r in reqs]
+    out = [None] * len(cis)
+    groups: dict = {}
+    key = globals()[f"batch_{algorithm}_key"]
+    for x, ci in enumerate(cis):
+        if ci.n == 0:
+            out[x] = _heuristic_result(ci, None, with_unvisited)
+        elif kind.strict or _domain_message(algorithm, ci, knobs) is None:
+            groups.setdefault(key(ci, *knobs), []).append(x)
+        else:
+            out[x] = single(algorithm, *reqs[x], device=device, **shared)
+    if groups:
+        ctx = context(device)
+        for xs in groups.values():
+            rows = _launch(algorithm, ctx, [cis[x] for x in xs],
+                           knobs if launch_knobs is None else launch_knobs, seed, objective, spread)
+            for x, *row in zip(xs, *rows):
+                out[x] = _heuristic_result(cis[x], row, with_unvisited)
+    return out
+
+
+# ---------------------------------------------------------------------------
 # batched VRP annealing (A22): small-fleet requests share launches
 # ---------------------------------------------------------------------------
 def batch_sa_wide(ci: CompactInstance) -> bool:
@@ -1139,13 +1379,7 @@ def batch_sa_fits(ci: CompactInstance) -> bool:
     static or 24-slice matrix whose whole instance and twelve tours fit
     BATCH_SA_LDS_BYTES (vrpms_vrp_batch_sa_lds; uint16 cells unless an entry
     is above 65535).  Needs the library, no GPU."""
-    from .core import vrp_batch_sa_lds
-    if ci.problem != CVRP or ci.n < 1 or ci.N > 65535:
-        return False
-    N, K, H, wide = batch_sa_key(ci)
-    if not 1 <= K <= BATCH_SA_MAX_VEHICLES or H not in (1, 24):
-        return False
-    return vrp_batch_sa_lds(N, K, H, wide) <= BATCH_SA_LDS_BYTES
+    return _domain_message("sa", ci, ()) is None
 
 
 def batch_sa_launch(ctx: Context, cis, steps: int, seed: int, objective: str = "sum"):
@@ -1154,18 +1388,7 @@ def batch_sa_launch(ctx: Context, cis, steps: int, seed: int, objective: str = "
     request on its own batch_sa_schedule -> (tours, veh, durs): per instance
     the n + K - 1 tour tokens, each token's vehicle (-1 unvisited, -2 a
     separator) and the K route durations."""
-    import torch
-    mats, demand, caps = _stage(ctx, cis, hours=True)
-    starts = torch.from_numpy(np.array([ci.start_times for ci in cis], dtype=np.int32)).to(ctx.dev)
-    sched = [batch_sa_schedule(ci, steps) for ci in cis]
-    inv_t0 = torch.from_numpy(np.array([s[0] for s in sched], dtype=np.float32)).to(ctx.dev)
-    tours, keys, durs, veh = ctx.vrp_batch_sa(mats, demand, caps, starts, inv_t0,
-                                              OBJ_MAX if objective == "max" else OBJ_SUM,
-                                              int(steps), sched[0][1], seed,
-                                              wide=batch_sa_wide(cis[0]))
-    if (keys == -1).any().item():
-        raise RuntimeError("vrp_batch_sa: a request was outside the launch's contract")
-    return tours.cpu().tolist(), veh.cpu().tolist(), durs.cpu().tolist()
+    return _heuristic_launch("sa", ctx, cis, (steps,), seed, objective)
 
 
 def sa_result(ci: CompactInstance, tour, veh, durs, with_unvisited: bool = False) -> dict:
@@ -1216,37 +1439,8 @@ def solve_vrp_sa_batch(requests, *, steps: int = 2000, seed: int = 0, objective:
         raise ValueError("objective must be 'sum' or 'max'")
     if int(steps) < 0:
         raise ValueError("steps must not be negative")
-    reqs, cis = [], []
-    for x, r in enumerate(requests):
-        try:
-            r, _ = _sp_request(r)
-            ci = compact_vrp(*r)
-            msg = batch_guard_message(ci)
-            if msg is not None:
-                raise ValueError(msg)
-        except ValueError as e:
-            raise ValueError(f"request {x}: {e}") from None
-        reqs.append(r)
-        cis.append(ci)
-    shared = dict(seed=seed, objective=objective, with_unvisited=with_unvisited)
-    if _remote() is not None:      # no local GPU: the GPU box answers each request
-        return [solve_vrp("sa", *r, **shared) for r in reqs]
-    out = [None] * len(cis)
-    groups: dict = {}
-    for x, ci in enumerate(cis):
-        if ci.n == 0:
-            out[x] = sa_result(ci, [], [], [0] * len(ci.capacities), with_unvisited)
-        elif batch_sa_fits(ci):
-            groups.setdefault(batch_sa_key(ci), []).append(x)
-        else:
-            out[x] = solve_vrp("sa", *reqs[x], device=device, **shared)
-    if groups:
-        ctx = context(device)
-        for xs in groups.values():
-            rows = batch_sa_launch(ctx, [cis[x] for x in xs], steps, seed, objective)
-            for x, tour, veh, durs in zip(xs, *rows):
-                out[x] = sa_result(cis[x], tour, veh, durs, with_unvisited)
-    return out
+    return _solve_heuristic_batch("sa", requests, (), seed, device, objective, with_unvisited,
+                                  launch_knobs=(steps,))
 
 
 # ---------------------------------------------------------------------------
@@ -1264,15 +1458,7 @@ def batch_ga_fits(ci: CompactInstance, pop: int, gens: int) -> bool:
     BATCH_GA_MAX_GENERATIONS, and an instance that fits BATCH_GA_LDS_BYTES
     together with its 2 pop tours (vrpms_vrp_batch_ga_lds; uint16 cells unless
     an entry is above 65535).  Needs the library, no GPU."""
-    from .core import vrp_batch_ga_lds
-    if ci.problem != CVRP or ci.n < 1 or ci.N > 65535:
-        return False
-    if not 2 <= int(pop) <= BATCH_GA_MAX_POP or not 0 <= int(gens) <= BATCH_GA_MAX_GENERATIONS:
-        return False
-    N, K, H, wide = batch_sa_key(ci)
-    if not 1 <= K <= BATCH_SA_MAX_VEHICLES or H not in (1, 24):
-        return False
-    return vrp_batch_ga_lds(N, K, H, wide, int(pop)) <= BATCH_GA_LDS_BYTES
+    return _domain_message("ga", ci, (pop, gens)) is None
 
 
 def batch_ga_launch(ctx: Context, cis, pop: int, gens: int, pmut: float, seed: int,
@@ -1281,16 +1467,7 @@ def batch_ga_launch(ctx: Context, cis, pop: int, gens: int, pmut: float, seed: i
     batch_ga_key (each passed batch_guard_message and batch_ga_fits) ->
     (tours, veh, durs): per instance the n genes of the best member, each
     gene's vehicle (-1 unvisited) and the K route durations."""
-    import torch
-    mats, demand, caps = _stage(ctx, cis, hours=True)
-    starts = torch.from_numpy(np.array([ci.start_times for ci in cis], dtype=np.int32)).to(ctx.dev)
-    tours, keys, durs, veh = ctx.vrp_batch_ga(mats, demand, caps, starts,
-                                              OBJ_MAX if objective == "max" else OBJ_SUM,
-                                              int(pop), int(gens), float(pmut), seed,
-                                              wide=batch_sa_wide(cis[0]))
-    if (keys == -1).any().item():
-        raise RuntimeError("vrp_batch_ga: a request was outside the launch's contract")
-    return tours.cpu().tolist(), veh.cpu().tolist(), durs.cpu().tolist()
+    return _heuristic_launch("ga", ctx, cis, (pop, gens, pmut), seed, objective)
 
 
 def ga_knobs(random_permutation_count=None, iteration_count=None):
@@ -1335,38 +1512,8 @@ def solve_vrp_ga_batch(requests, *, pop: int = 256, gens: int = 400, pmut: float
         raise ValueError("gens must not be negative")
     if not 0.0 <= float(pmut) <= 1.0:
         raise ValueError("pmut must be a probability")
-    reqs, cis = [], []
-    for x, r in enumerate(requests):
-        try:
-            r, _ = _sp_request(r)
-            ci = compact_vrp(*r)
-            msg = batch_guard_message(ci)
-            if msg is not None:
-                raise ValueError(msg)
-        except ValueError as e:
-            raise ValueError(f"request {x}: {e}") from None
-        reqs.append(r)
-        cis.append(ci)
-    shared = dict(seed=seed, objective=objective, with_unvisited=with_unvisited,
-                  random_permutation_count=int(pop), iteration_count=int(gens))
-    if _remote() is not None:      # no local GPU: the GPU box answers each request
-        return [solve_vrp("ga", *r, **shared) for r in reqs]
-    out = [None] * len(cis)
-    groups: dict = {}
-    for x, ci in enumerate(cis):
-        if ci.n == 0:
-            out[x] = sa_result(ci, [], [], [0] * len(ci.capacities), with_unvisited)
-        elif batch_ga_fits(ci, pop, gens):
-            groups.setdefault(batch_ga_key(ci, pop, gens), []).append(x)
-        else:
-            out[x] = solve_vrp("ga", *reqs[x], device=device, **shared)
-    if groups:
-        ctx = context(device)
-        for xs in groups.values():
-            rows = batch_ga_launch(ctx, [cis[x] for x in xs], pop, gens, pmut, seed, objective)
-            for x, tour, veh, durs in zip(xs, *rows):
-                out[x] = sa_result(cis[x], tour, veh, durs, with_unvisited)
-    return out
+    return _solve_heuristic_batch("ga", requests, (pop, gens), seed, device, objective,
+                                  with_unvisited, launch_knobs=(pop, gens, pmut))
 
 
 # ---------------------------------------------------------------------------
@@ -1385,15 +1532,7 @@ def batch_aco_fits(ci: CompactInstance, ants: int, iters: int) -> bool:
     together with its pheromone tables and ants + 1 tours
     (vrpms_vrp_batch_aco_lds; uint16 cells unless an entry is above 65535).
     Needs the library, no GPU."""
-    from .core import vrp_batch_aco_lds
-    if ci.problem != CVRP or ci.n < 1 or ci.N > 65535:
-        return False
-    if not 1 <= int(ants) <= BATCH_ACO_MAX_ANTS or not 1 <= int(iters) <= BATCH_ACO_MAX_ITERATIONS:
-        return False
-    N, K, H, wide = batch_sa_key(ci)
-    if not 1 <= K <= BATCH_SA_MAX_VEHICLES or H not in (1, 24):
-        return False
-    return vrp_batch_aco_lds(N, K, H, wide, int(ants)) <= BATCH_ACO_LDS_BYTES
+    return _domain_message("aco", ci, (ants, iters)) is None
 
 
 def batch_aco_launch(ctx: Context, cis, ants: int, iters: int, seed: int, objective: str = "sum"):
@@ -1402,16 +1541,7 @@ def batch_aco_launch(ctx: Context, cis, ants: int, iters: int, seed: int, object
     ACORunner's pheromone parameters -> (tours, veh, durs): per instance the n
     customers of the best-so-far tour, each one's vehicle (-1 unvisited) and
     the K route durations."""
-    import torch
-    mats, demand, caps = _stage(ctx, cis, hours=True)
-    starts = torch.from_numpy(np.array([ci.start_times for ci in cis], dtype=np.int32)).to(ctx.dev)
-    tours, keys, durs, veh = ctx.vrp_batch_aco(mats, demand, caps, starts,
-                                               OBJ_MAX if objective == "max" else OBJ_SUM,
-                                               int(ants), int(iters), seed,
-                                               wide=batch_sa_wide(cis[0]))
-    if (keys == -1).any().item():
-        raise RuntimeError("vrp_batch_aco: a request was outside the launch's contract")
-    return tours.cpu().tolist(), veh.cpu().tolist(), durs.cpu().tolist()
+    return _heuristic_launch("aco", ctx, cis, (ants, iters), seed, objective)
 
 
 def solve_vrp_aco_batch(requests, *, ants: int = 64, iters: int = 100, seed: int = 0,
@@ -1449,38 +1579,8 @@ def solve_vrp_aco_batch(requests, *, ants: int = 64, iters: int = 100, seed: int
         raise ValueError("ants must be at least 1")
     if int(iters) < 1:
         raise ValueError("iters must be at least 1")
-    reqs, cis = [], []
-    for x, r in enumerate(requests):
-        try:
-            r, _ = _sp_request(r)
-            ci = compact_vrp(*r)
-            msg = batch_guard_message(ci)
-            if msg is not None:
-                raise ValueError(msg)
-        except ValueError as e:
-            raise ValueError(f"request {x}: {e}") from None
-        reqs.append(r)
-        cis.append(ci)
-    shared = dict(seed=seed, objective=objective, with_unvisited=with_unvisited,
-                  iteration_count=int(iters), ants=int(ants))
-    if _remote() is not None:      # no local GPU: the GPU box answers each request
-        return [solve_vrp("aco", *r, **shared) for r in reqs]
-    out = [None] * len(cis)
-    groups: dict = {}
-    for x, ci in enumerate(cis):
-        if ci.n == 0:
-            out[x] = sa_result(ci, [], [], [0] * len(ci.capacities), with_unvisited)
-        elif batch_aco_fits(ci, ants, iters):
-            groups.setdefault(batch_aco_key(ci, ants, iters), []).append(x)
-        else:
-            out[x] = solve_vrp("aco", *reqs[x], device=device, **shared)
-    if groups:
-        ctx = context(device)
-        for xs in groups.values():
-            rows = batch_aco_launch(ctx, [cis[x] for x in xs], ants, iters, seed, objective)
-            for x, tour, veh, durs in zip(xs, *rows):
-                out[x] = sa_result(cis[x], tour, veh, durs, with_unvisited)
-    return out
+    return _solve_heuristic_batch("aco", requests, (ants, iters), seed, device, objective,
+                                  with_unvisited)
 
 
 # ---------------------------------------------------------------------------
@@ -1499,29 +1599,7 @@ def batch_ls_message(ci: CompactInstance, starts: int, rounds: int):
     BATCH_LS_MAX_ROUNDS, and an instance that fits BATCH_LS_LDS_BYTES together
     with its eight tours (vrpms_vrp_batch_ls_lds; uint16 cells unless an entry
     is above 65535).  Needs the library, no GPU."""
-    from .core import vrp_batch_ls_lds
-    if ci.problem != CVRP:
-        return 'ls solves the VRP only'
-    if not 1 <= int(starts) <= BATCH_LS_MAX_STARTS:
-        return f"ls (local search) takes 1..{BATCH_LS_MAX_STARTS} starts ({starts} given)"
-    if not 0 <= int(rounds) <= BATCH_LS_MAX_ROUNDS:
-        return f"ls (local search) takes 0..{BATCH_LS_MAX_ROUNDS} rounds ({rounds} given)"
-    if ci.n < 1:
-        return "ls (local search) needs at least one customer"
-    if ci.N > 65535:
-        return f"ls (local search) supports at most 65534 customers ({ci.n} given)"
-    N, K, H, wide = batch_sa_key(ci)
-    if not 1 <= K <= BATCH_SA_MAX_VEHICLES:
-        return (f"ls (local search) supports 1..{BATCH_SA_MAX_VEHICLES} vehicles "
-                f"({K} given)")
-    if H not in (1, 24):
-        return f"ls (local search) needs a static or 24-slice duration matrix ({H} slices given)"
-    need = vrp_batch_ls_lds(N, K, H, wide)
-    if need > BATCH_LS_LDS_BYTES:
-        return (f"ls (local search) keeps the instance in LDS: {ci.n} customers, {K} vehicles and "
-                f"{H} hour slice(s) of {'int32' if wide else 'uint16'} cells need {need} bytes; "
-                f"the limit is {BATCH_LS_LDS_BYTES} bytes")
-    return None
+    return _domain_message("ls", ci, (starts, rounds))
 
 
 def batch_ls_fits(ci: CompactInstance, starts: int, rounds: int) -> bool:
@@ -1533,12 +1611,7 @@ def batch_ls_fits(ci: CompactInstance, starts: int, rounds: int) -> bool:
 def _check_ls(ci: CompactInstance, starts, rounds):
     """A25's domain and the int32 guards, checked on the host before any device
     or remote is touched.  No customer is solve_vrp's trivial answer."""
-    if ci.problem == CVRP and ci.n == 0 and 1 <= int(starts) <= BATCH_LS_MAX_STARTS and \
-            0 <= int(rounds) <= BATCH_LS_MAX_ROUNDS:
-        return
-    msg = batch_ls_message(ci, starts, rounds) or batch_guard_message(ci)
-    if msg is not None:
-        raise ValueError(msg)
+    _check_heuristic("ls", ci, (starts, rounds))
 
 
 def batch_ls_launch(ctx: Context, cis, starts: int, rounds: int, seed: int, objective: str = "sum"):
@@ -1546,16 +1619,7 @@ def batch_ls_launch(ctx: Context, cis, starts: int, rounds: int, seed: int, obje
     batch_ls_key (each passed batch_guard_message and batch_ls_fits) ->
     (tours, veh, durs): per instance the n genes of the best end tour, each
     gene's vehicle (-1 unvisited) and the K route durations."""
-    import torch
-    mats, demand, caps = _stage(ctx, cis, hours=True)
-    st = torch.from_numpy(np.array([ci.start_times for ci in cis], dtype=np.int32)).to(ctx.dev)
-    tours, keys, durs, veh, _ = ctx.vrp_batch_ls(mats, demand, caps, st,
-                                                 OBJ_MAX if objective == "max" else OBJ_SUM,
-                                                 int(starts), int(rounds), seed,
-                                                 wide=batch_sa_wide(cis[0]))
-    if (keys == -1).any().item():
-        raise RuntimeError("vrp_batch_ls: a request was outside the launch's contract")
-    return tours.cpu().tolist(), veh.cpu().tolist(), durs.cpu().tolist()
+    return _heuristic_launch("ls", ctx, cis, (starts, rounds), seed, objective)
 
 
 def solve_vrp_ls_batch(requests, *, starts: int = 64, rounds: int = 1000, seed: int = 0,
@@ -1590,38 +1654,8 @@ def solve_vrp_ls_batch(requests, *, starts: int = 64, rounds: int = 1000, seed: 
         raise ValueError(f"starts must be in 1..{BATCH_LS_MAX_STARTS} ({starts} given)")
     if not 0 <= int(rounds) <= BATCH_LS_MAX_ROUNDS:
         raise ValueError(f"rounds must be in 0..{BATCH_LS_MAX_ROUNDS} ({rounds} given)")
-    reqs, cis = [], []
-    for x, r in enumerate(requests):
-        try:
-            r, _ = _sp_request(r)
-            ci = compact_vrp(*r)
-            msg = batch_guard_message(ci)
-            if msg is None and ci.n:
-                msg = batch_ls_message(ci, starts, rounds)
-            if msg is not None:
-                raise ValueError(msg)
-        except ValueError as e:
-            raise ValueError(f"request {x}: {e}") from None
-        reqs.append(r)
-        cis.append(ci)
-    shared = dict(seed=seed, objective=objective, with_unvisited=with_unvisited,
-                  starts=int(starts), rounds=int(rounds))
-    if _remote() is not None:      # no local GPU: the GPU box answers each request
-        return [solve_vrp("ls", *r, **shared) for r in reqs]
-    out = [None] * len(cis)
-    groups: dict = {}
-    for x, ci in enumerate(cis):
-        if ci.n == 0:
-            out[x] = sa_result(ci, [], [], [0] * len(ci.capacities), with_unvisited)
-        else:
-            groups.setdefault(batch_ls_key(ci, starts, rounds), []).append(x)
-    if groups:
-        ctx = context(device)
-        for xs in groups.values():
-            rows = batch_ls_launch(ctx, [cis[x] for x in xs], starts, rounds, seed, objective)
-            for x, tour, veh, durs in zip(xs, *rows):
-                out[x] = sa_result(cis[x], tour, veh, durs, with_unvisited)
-    return out
+    return _solve_heuristic_batch("ls", requests, (starts, rounds), seed, device, objective,
+                                  with_unvisited)
 
 
 # ---------------------------------------------------------------------------
@@ -1641,28 +1675,7 @@ def batch_lso_message(ci: CompactInstance, starts: int, rounds: int, moves: int 
     BATCH_LSO_LDS_BYTES together with the wavefronts' tours and prefix rows
     (vrpms_tsp_batch_lso_lds; uint16 cells unless an entry is above 65535).
     Needs the library, no GPU."""
-    from .core import tsp_batch_lso_lds
-    if ci.problem != TSP:
-        return 'lso solves the TSP only'
-    if not 1 <= int(starts) <= BATCH_LSO_MAX_STARTS:
-        return f"lso (local search) takes 1..{BATCH_LSO_MAX_STARTS} starts ({starts} given)"
-    if not 0 <= int(rounds) <= BATCH_LSO_MAX_ROUNDS:
-        return f"lso (local search) takes 0..{BATCH_LSO_MAX_ROUNDS} rounds ({rounds} given)"
-    if not 1 <= int(moves) <= 31:
-        return f"lso (local search) takes a move mask of 1..31 ({moves} given)"
-    if ci.n < 1:
-        return "lso (local search) needs at least one customer"
-    if ci.N > 65535:
-        return f"lso (local search) supports at most 65534 customers ({ci.n} given)"
-    N, H, wide = batch_lso_key(ci, starts, rounds, moves)[:3]
-    if H not in (1, 24):
-        return f"lso (local search) needs a static or 24-slice duration matrix ({H} slices given)"
-    need = tsp_batch_lso_lds(N, H, wide)
-    if need > BATCH_LSO_LDS_BYTES:
-        return (f"lso (local search) keeps the matrix in LDS: {ci.n} customers and {H} hour "
-                f"slice(s) of {'int32' if wide else 'uint16'} cells need {need} bytes; the limit "
-                f"is {BATCH_LSO_LDS_BYTES} bytes")
-    return None
+    return _domain_message("lso", ci, (starts, rounds, moves))
 
 
 def batch_lso_fits(ci: CompactInstance, starts: int, rounds: int, moves: int = 31) -> bool:
@@ -1674,25 +1687,13 @@ def batch_lso_fits(ci: CompactInstance, starts: int, rounds: int, moves: int = 3
 def _check_lso(ci: CompactInstance, starts, rounds, moves):
     """A27's domain and the A9 guard, checked on the host before any device or
     remote is touched.  No customer is answered on the host."""
-    if ci.problem == TSP and ci.n == 0 and 1 <= int(starts) <= BATCH_LSO_MAX_STARTS and \
-            0 <= int(rounds) <= BATCH_LSO_MAX_ROUNDS and 1 <= int(moves) <= 31:
-        msg = batch_guard_message(ci)
-    else:
-        msg = batch_lso_message(ci, starts, rounds, moves) or batch_guard_message(ci)
-    if msg is not None:
-        raise ValueError(msg)
+    _check_heuristic("lso", ci, (starts, rounds, moves))
 
 
 def check_lso_spread(spread):
     """`spread` as batch_lso_launch takes it -> None, "auto" or an int in
     1..BATCH_LSO_MAX_SPREAD; anything else is a ValueError."""
-    if spread is None or (isinstance(spread, str) and spread == "auto"):
-        return spread
-    if isinstance(spread, (int, np.integer)) and not isinstance(spread, bool) and \
-            1 <= int(spread) <= BATCH_LSO_MAX_SPREAD:
-        return int(spread)
-    raise ValueError(f'spread must be None, "auto" or an integer in 1..{BATCH_LSO_MAX_SPREAD} '
-                     f"({spread!r} given)")
+    return _check_spread(spread, BATCH_LSO_MAX_SPREAD)
 
 
 def batch_lso_spread(R: int, S: int, cus: int) -> int:
@@ -1702,7 +1703,7 @@ def batch_lso_spread(R: int, S: int, cus: int) -> int:
     the requests are few.  1 means tsp_batch_lso itself, one workgroup per
     request.  The factor is the largest of 1, 2, 4, 8 and 16 measured (DESIGN
     §4.3t): at every launch size each step up was faster."""
-    return min(int(S), max(1, (16 * int(cus)) // max(int(R), 1)))
+    return _auto_spread(R, S, cus)
 
 
 def batch_lso_launch(ctx: Context, cis, starts: int, rounds: int, moves: int, seed: int,
@@ -1716,22 +1717,7 @@ def batch_lso_launch(ctx: Context, cis, starts: int, rounds: int, moves: int, se
     at a time); "auto" takes batch_lso_spread's for the launch's size and the
     device, and tsp_batch_lso when that is 1.  The rows are the same whichever
     it is."""
-    import torch
-    spread = check_lso_spread(spread)
-    mats, = _stage(ctx, cis, hours=True)
-    st = torch.from_numpy(np.array([int(ci.start_times[0]) for ci in cis],
-                                   dtype=np.int32)).to(ctx.dev)
-    if spread == "auto":
-        spread = batch_lso_spread(len(cis), int(starts), ctx.cus)
-        spread = None if spread == 1 else min(spread, BATCH_LSO_MAX_SPREAD)
-    args = (mats, st, int(starts), int(rounds), int(moves), seed)
-    if spread is None:
-        tours, keys, durs, _ = ctx.tsp_batch_lso(*args, wide=batch_sa_wide(cis[0]))
-    else:
-        tours, keys, durs, _ = ctx.tsp_batch_lso_spread(*args, spread, wide=batch_sa_wide(cis[0]))
-    if (keys == -1).any().item():
-        raise RuntimeError("tsp_batch_lso: a request was outside the launch's contract")
-    return tours.cpu().tolist(), durs.cpu().tolist()
+    return _heuristic_launch("lso", ctx, cis, (starts, rounds, moves), seed, spread=spread)
 
 
 def solve_tsp_lso_batch(requests, *, starts: int = 64, rounds: int = 1000, moves: int = 31,
@@ -1768,40 +1754,8 @@ def solve_tsp_lso_batch(requests, *, starts: int = 64, rounds: int = 1000, moves
         raise ValueError(f"rounds must be in 0..{BATCH_LSO_MAX_ROUNDS} ({rounds} given)")
     if not 1 <= int(moves) <= 31:
         raise ValueError(f"moves must be in 1..31 ({moves} given)")
-    reqs, cis = [], []
-    for x, r in enumerate(requests):
-        try:
-            r, _ = _tsp_request(r)
-            ci = compact_tsp(*r)
-            msg = batch_guard_message(ci)
-            if msg is None and ci.n:
-                msg = batch_lso_message(ci, starts, rounds, moves)
-            if msg is not None:
-                raise ValueError(msg)
-        except ValueError as e:
-            raise ValueError(f"request {x}: {e}") from None
-        reqs.append(r)
-        cis.append(ci)
-    if _remote() is not None:      # no local GPU: the GPU box answers each request
-        shared = dict(seed=seed, starts=int(starts), rounds=int(rounds), moves=int(moves))
-        if isinstance(spread, int):   # "auto" is the GPU box's own to decide
-            shared["spread"] = spread
-        return [solve_tsp("lso", *r, **shared) for r in reqs]
-    out = [None] * len(cis)
-    groups: dict = {}
-    for x, ci in enumerate(cis):
-        if ci.n == 0:
-            out[x] = tsp_result(ci, [], _td_duration(ci, []))
-        else:
-            groups.setdefault(batch_lso_key(ci, starts, rounds, moves), []).append(x)
-    if groups:
-        ctx = context(device)
-        for xs in groups.values():
-            tours, durs = batch_lso_launch(ctx, [cis[x] for x in xs], starts, rounds, moves, seed,
-                                           spread=spread)
-            for x, tour, dur in zip(xs, tours, durs):
-                out[x] = tsp_result(cis[x], tour, dur)
-    return out
+    return _solve_heuristic_batch("lso", requests, (starts, rounds, moves), seed, device,
+                                  spread=spread)
 
 
 # ---------------------------------------------------------------------------
@@ -1822,31 +1776,7 @@ def batch_lsr_message(ci: CompactInstance, starts: int, rounds: int):
     and an instance that fits BATCH_LSR_LDS_BYTES together with its eight tours
     of tokens (vrpms_vrp_batch_lsr_lds; uint16 cells unless an entry is above
     65535).  Needs the library, no GPU."""
-    from .core import vrp_batch_lsr_lds
-    if ci.problem != CVRP:
-        return 'lsr solves the VRP only'
-    if not 1 <= int(starts) <= BATCH_LSR_MAX_STARTS:
-        return f"lsr (local search) takes 1..{BATCH_LSR_MAX_STARTS} starts ({starts} given)"
-    if not 0 <= int(rounds) <= BATCH_LSR_MAX_ROUNDS:
-        return f"lsr (local search) takes 0..{BATCH_LSR_MAX_ROUNDS} rounds ({rounds} given)"
-    if ci.n < 1:
-        return "lsr (local search) needs at least one customer"
-    if ci.N > 65535:
-        return f"lsr (local search) supports at most 65534 customers ({ci.n} given)"
-    N, K, H, wide = batch_sa_key(ci)
-    if not 1 <= K <= BATCH_SA_MAX_VEHICLES:
-        return (f"lsr (local search) supports 1..{BATCH_SA_MAX_VEHICLES} vehicles "
-                f"({K} given)")
-    if H not in (1, 24):
-        return f"lsr (local search) needs a static or 24-slice duration matrix ({H} slices given)"
-    if N + K - 2 > 65535:
-        return f"lsr (local search) supports at most 65535 tokens ({N + K - 2} given)"
-    need = vrp_batch_lsr_lds(N, K, H, wide)
-    if need > BATCH_LSR_LDS_BYTES:
-        return (f"lsr (local search) keeps the instance in LDS: {ci.n} customers, {K} vehicles and "
-                f"{H} hour slice(s) of {'int32' if wide else 'uint16'} cells need {need} bytes; "
-                f"the limit is {BATCH_LSR_LDS_BYTES} bytes")
-    return None
+    return _domain_message("lsr", ci, (starts, rounds))
 
 
 def batch_lsr_fits(ci: CompactInstance, starts: int, rounds: int) -> bool:
@@ -1858,24 +1788,13 @@ def batch_lsr_fits(ci: CompactInstance, starts: int, rounds: int) -> bool:
 def _check_lsr(ci: CompactInstance, starts, rounds):
     """A26's domain and the int32 guards, checked on the host before any device
     or remote is touched.  No customer is solve_vrp's trivial answer."""
-    if ci.problem == CVRP and ci.n == 0 and 1 <= int(starts) <= BATCH_LSR_MAX_STARTS and \
-            0 <= int(rounds) <= BATCH_LSR_MAX_ROUNDS:
-        return
-    msg = batch_lsr_message(ci, starts, rounds) or batch_guard_message(ci)
-    if msg is not None:
-        raise ValueError(msg)
+    _check_heuristic("lsr", ci, (starts, rounds))
 
 
 def check_lsr_spread(spread):
     """`spread` as batch_lsr_launch takes it -> None, "auto" or an int in
     1..BATCH_LSR_MAX_SPREAD; anything else is a ValueError."""
-    if spread is None or (isinstance(spread, str) and spread == "auto"):
-        return spread
-    if isinstance(spread, (int, np.integer)) and not isinstance(spread, bool) and \
-            1 <= int(spread) <= BATCH_LSR_MAX_SPREAD:
-        return int(spread)
-    raise ValueError(f'spread must be None, "auto" or an integer in 1..{BATCH_LSR_MAX_SPREAD} '
-                     f"({spread!r} given)")
+    return _check_spread(spread, BATCH_LSR_MAX_SPREAD)
 
 
 def batch_lsr_spread(R: int, S: int, cus: int) -> int:
@@ -1885,7 +1804,7 @@ def batch_lsr_spread(R: int, S: int, cus: int) -> int:
     the requests are few.  1 means vrp_batch_lsr itself, one workgroup per
     request.  The factor is the largest of 1, 2, 4, 8 and 16 measured (DESIGN
     §4.3r): at every launch size each step up was faster."""
-    return min(int(S), max(1, (16 * int(cus)) // max(int(R), 1)))
+    return _auto_spread(R, S, cus)
 
 
 def batch_lsr_launch(ctx: Context, cis, starts: int, rounds: int, seed: int,
@@ -1900,23 +1819,7 @@ def batch_lsr_launch(ctx: Context, cis, starts: int, rounds: int, seed: int,
     one descent at a time); "auto" takes batch_lsr_spread's for the launch's
     size and the device, and vrp_batch_lsr when that is 1.  The rows are the
     same whichever it is."""
-    import torch
-    spread = check_lsr_spread(spread)
-    mats, demand, caps = _stage(ctx, cis, hours=True)
-    st = torch.from_numpy(np.array([ci.start_times for ci in cis], dtype=np.int32)).to(ctx.dev)
-    if spread == "auto":
-        spread = batch_lsr_spread(len(cis), int(starts), ctx.cus)
-        spread = None if spread == 1 else min(spread, BATCH_LSR_MAX_SPREAD)
-    args = (mats, demand, caps, st, OBJ_MAX if objective == "max" else OBJ_SUM, int(starts),
-            int(rounds), seed)
-    if spread is None:
-        tours, keys, durs, veh, _ = ctx.vrp_batch_lsr(*args, wide=batch_sa_wide(cis[0]))
-    else:
-        tours, keys, durs, veh, _ = ctx.vrp_batch_lsr_spread(*args, spread,
-                                                             wide=batch_sa_wide(cis[0]))
-    if (keys == -1).any().item():
-        raise RuntimeError("vrp_batch_lsr: a request was outside the launch's contract")
-    return tours.cpu().tolist(), veh.cpu().tolist(), durs.cpu().tolist()
+    return _heuristic_launch("lsr", ctx, cis, (starts, rounds), seed, objective, spread)
 
 
 def solve_vrp_lsr_batch(requests, *, starts: int = 64, rounds: int = 1000, seed: int = 0,
@@ -1955,41 +1858,8 @@ def solve_vrp_lsr_batch(requests, *, starts: int = 64, rounds: int = 1000, seed:
         raise ValueError(f"starts must be in 1..{BATCH_LSR_MAX_STARTS} ({starts} given)")
     if not 0 <= int(rounds) <= BATCH_LSR_MAX_ROUNDS:
         raise ValueError(f"rounds must be in 0..{BATCH_LSR_MAX_ROUNDS} ({rounds} given)")
-    reqs, cis = [], []
-    for x, r in enumerate(requests):
-        try:
-            r, _ = _sp_request(r)
-            ci = compact_vrp(*r)
-            msg = batch_guard_message(ci)
-            if msg is None and ci.n:
-                msg = batch_lsr_message(ci, starts, rounds)
-            if msg is not None:
-                raise ValueError(msg)
-        except ValueError as e:
-            raise ValueError(f"request {x}: {e}") from None
-        reqs.append(r)
-        cis.append(ci)
-    shared = dict(seed=seed, objective=objective, with_unvisited=with_unvisited,
-                  starts=int(starts), rounds=int(rounds))
-    if _remote() is not None:      # no local GPU: the GPU box answers each request
-        if isinstance(spread, int):   # "auto" is the GPU box's own to decide
-            shared["spread"] = spread
-        return [solve_vrp("lsr", *r, **shared) for r in reqs]
-    out = [None] * len(cis)
-    groups: dict = {}
-    for x, ci in enumerate(cis):
-        if ci.n == 0:
-            out[x] = sa_result(ci, [], [], [0] * len(ci.capacities), with_unvisited)
-        else:
-            groups.setdefault(batch_lsr_key(ci, starts, rounds), []).append(x)
-    if groups:
-        ctx = context(device)
-        for xs in groups.values():
-            rows = batch_lsr_launch(ctx, [cis[x] for x in xs], starts, rounds, seed, objective,
-                                    spread=spread)
-            for x, tour, veh, durs in zip(xs, *rows):
-                out[x] = sa_result(cis[x], tour, veh, durs, with_unvisited)
-    return out
+    return _solve_heuristic_batch("lsr", requests, (starts, rounds), seed, device, objective,
+                                  with_unvisited, spread)
 
 
 # ---------------------------------------------------------------------------
