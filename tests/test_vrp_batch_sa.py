@@ -169,6 +169,7 @@ NTOK_EDGES = [((1, 1, 1, 0, ""), 8), ((2, 1, 1, 1, ""), 8), ((1, 2, 24, 2, "belo
               ((58, 6, 1, 6, ""), 12), ((59, 6, 1, 7, ""), 12), ((60, 6, 1, 8, ""), 12)]
 STEP_TAILS = [((8, 3, 1, 9, ""), s) for s in (0, 1, 3, 4, 5, 41)]
 HOURS = [((6, 3, 24, s, "hours"), 20) for s in (10, 11)]
+WIDE_HOURS = [((7, 3, 24, 31, "e65536"), 10)]   # an int32 matrix at H = 24
 FLEETS = [((3, 64, 1, 12, ""), 10), ((9, 5, 24, 13, "zerocap"), 10), ((9, 3, 1, 14, "zerodem"), 10),
           ((9, 3, 24, 15, "tight"), 10)]
 SIX = [(10, 3, 24, 20 + x, "") for x in range(6)]
@@ -529,7 +530,7 @@ def gpu_batch(ctx, cases, objective, steps, wide=None):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("objective", OBJECTIVES)
-@pytest.mark.parametrize("case,steps", NTOK_EDGES + STEP_TAILS + HOURS + FLEETS)
+@pytest.mark.parametrize("case,steps", NTOK_EDGES + STEP_TAILS + HOURS + WIDE_HOURS + FLEETS)
 def test_gpu_equals_reference(ctx, case, steps, objective):
     got = gpu_batch(ctx, [case], objective, steps)
     want = expected([case], objective, steps)

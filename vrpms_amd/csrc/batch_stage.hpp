@@ -1,6 +1,10 @@
 // What the one-workgroup-per-request VRP kernels share (vrp_batch_sa.hip, A22;
-// vrp_batch_ga.hip, A23; vrp_batch_aco.hip, A24; vrp_batch_ls.hip, A25; vrp_batch_lsr.hip, A26): staging a request's instance into LDS with the entry
-// check on the way, the refusal row, and the final walk of the winning tour.
+// vrp_batch_ga.hip, A23; vrp_batch_aco.hip, A24; vrp_batch_ls.hip, A25;
+// vrp_batch_lsr.hip and vrp_batch_lsr_spread.hip, A26): the sizes of a request's
+// instance in LDS -- one description for the host, which sizes the launch, and
+// for a kernel that carves by it (vrp_batch_sa so far; DESIGN.md §4.3u has why
+// the others keep their own) -- staging it with the entry check on the way, the
+// refusal row, and the final walk of the winning tour.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -9,6 +13,58 @@
 #include "tour.hpp"
 
 namespace vrpms {
+
+// x rounded up to a multiple of the power of two `to`
+template <typename I>
+__host__ __device__ constexpr I batch_align(I x, I to) {
+  return (x + (to - 1)) & ~(to - 1);
+}
+
+// The parts of a VRP request's instance, with which every kernel's dynamic LDS
+// begins, in their order: the [H][N][N] matrix (cells of `cell` bytes, padded to
+// 16 bytes), align4(N) demand words, align4(K) capacity words and align4(K)
+// start-time words.  The host, which sizes the launch, sums them (bytes()); a
+// kernel steps through them (BatchInst): both read the sizes here and nowhere
+// else.  I is size_t on the host, which is asked about N up to 65535 (H N N 4
+// is then far above 2^32), and uint32_t in a kernel, whose launch has passed
+// the LDS check.
+template <typename I>
+struct BatchInstParts {
+  I cells, mat_bytes, dem_words, row_words;
+  __host__ __device__ BatchInstParts(I N, I K, I H, I cell) {
+    cells = H * N * N;
+    mat_bytes = batch_align<I>(cells * cell, 16);
+    dem_words = batch_align<I>(N, 4);
+    row_words = batch_align<I>(K, 4);
+  }
+  __host__ __device__ I bytes() const { return mat_bytes + 4 * dem_words + 2 * 4 * row_words; }
+};
+
+inline size_t batch_inst_bytes(int N, int K, int H, int wide) {
+  return BatchInstParts<size_t>((size_t)N, (size_t)K, (size_t)H, wide ? 4 : 2).bytes();
+}
+
+// The kernel's carve of them; the kernel's own parts follow at `rest`.
+template <typename MatT, int HM>
+struct BatchInst {
+  MatT* M;
+  int32_t *dem, *cap, *start;
+  unsigned char* rest;
+  uint32_t cells;
+  int N, K;
+  using Parts = BatchInstParts<uint32_t>;
+  static VRPMS_DEV Parts parts(int N, int K) {
+    return Parts((uint32_t)N, (uint32_t)K, (uint32_t)HM, (uint32_t)sizeof(MatT));
+  }
+  VRPMS_DEV BatchInst(unsigned char* mem, const Parts& l, int N_, int K_) : N(N_), K(K_) {
+    cells = l.cells;
+    M = reinterpret_cast<MatT*>(mem);
+    dem = reinterpret_cast<int32_t*>(mem + l.mat_bytes);
+    cap = dem + l.dem_words;
+    start = cap + l.row_words;
+    rest = reinterpret_cast<unsigned char*>(start + l.row_words);
+  }
+};
 
 // Request r's [HM][N][N] int32 matrix into M (as MatT), its demand row and its
 // two fleet rows into dem / cap / start.  -> whether the request is outside
@@ -41,6 +97,13 @@ VRPMS_DEV bool batch_stage_request(const int32_t* mats, const int32_t* demand, c
   bad = *flag != 0;
   __syncthreads();   // every wavefront has read the word before anything replaces it
   return bad;
+}
+
+// the same from a kernel's argument struct `a` (any of them) into its carve
+template <typename Args, typename MatT, int HM>
+VRPMS_DEV bool batch_stage_request(const Args& a, int64_t r, const BatchInst<MatT, HM>& c, void* flag) {
+  return batch_stage_request(a.mats, a.demand, a.cap, a.start, r, c.cells, c.N, c.K, c.M, c.dem, c.cap,
+                             c.start, static_cast<uint32_t*>(flag));
 }
 
 // The refusal row of a request outside the launch's promise: an all-ones key,

@@ -72,6 +72,12 @@
 
 namespace vrpms {
 
+inline size_t batch_lso_lds(int N, int H, int wide) {
+  // behind the shared parts: 4 waves' best end tours of align8(n) uint16, then [4] BatchLsWave
+  return batch_lso_shared_bytes(N, H, wide) + 4 * batch_align<size_t>((size_t)N - 1, 8) * 2 +
+         4 * sizeof(BatchLsWave);
+}
+
 template <typename MatT, int HM>
 __global__ __launch_bounds__(256) void tsp_batch_lso_kernel(TspBatchLsoArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char batch_lso_lds_mem[];
@@ -183,10 +189,10 @@ __global__ __launch_bounds__(256) void tsp_batch_lso_kernel(TspBatchLsoArgs a) {
 using namespace vrpms;
 
 extern "C" int vrpms_tsp_batch_lso_lds(int32_t N, int32_t H, int32_t wide, uint64_t* bytes) {
-  if (!bytes) return fail(VRPMS_EINVAL, "vrpms_tsp_batch_lso_lds: bytes is NULL");
-  const int rc = batch_lso_check("vrpms_tsp_batch_lso_lds", N, H, wide);
-  if (rc) return rc;
-  *bytes = batch_lso_lds(N, H, wide).total;
+  const char* who = "vrpms_tsp_batch_lso_lds";
+  if (const int rc = batch_check_bytes(who, bytes)) return rc;
+  if (const int rc = batch_lso_check(who, N, H, wide)) return rc;
+  *bytes = batch_lso_lds(N, H, wide);
   return VRPMS_OK;
 }
 
@@ -194,28 +200,24 @@ extern "C" int vrpms_tsp_batch_lso(vrpms_ctx* ctx, const int32_t* d_mats, const 
                                    int32_t R, int32_t N, int32_t H, int32_t wide, int32_t S,
                                    int32_t rounds, int32_t moves, uint64_t seed, uint16_t* d_tours,
                                    uint64_t* d_keys, int32_t* d_durs, int32_t* d_info, void* stream) {
-  if (!ctx) return fail(VRPMS_EINVAL, "vrpms_tsp_batch_lso: ctx is NULL");
-  if (R < 0) return fail(VRPMS_EINVAL, "vrpms_tsp_batch_lso: R must not be negative");
-  const int rc = batch_lso_check("vrpms_tsp_batch_lso", N, H, wide);
-  if (rc) return rc;
-  const int rs = batch_lso_check_search("vrpms_tsp_batch_lso", S, rounds, moves);
-  if (rs) return rs;
+  const char* who = "vrpms_tsp_batch_lso";
+  if (const int rc = batch_check_ctx(who, ctx, R)) return rc;
+  if (const int rc = batch_lso_check(who, N, H, wide)) return rc;
+  if (const int rc = batch_lso_check_search(who, S, rounds, moves)) return rc;
   if (R == 0) return VRPMS_OK;
-  if (!d_mats || !d_start || !d_tours || !d_keys || !d_durs || !d_info)
-    return fail(VRPMS_EINVAL, "vrpms_tsp_batch_lso: NULL matrix/start/tour/key/duration/info buffer");
-  const size_t lds = batch_lso_lds(N, H, wide).total;
-  if (lds > ctx->max_lds)
-    return batch_lso_lds_refusal("vrpms_tsp_batch_lso", N, H, wide, lds, ctx->max_lds);
+  if (const int rc = batch_check_buffers(who, "matrix/start/tour/key/duration/info",
+                                         {d_mats, d_start, d_tours, d_keys, d_durs, d_info}))
+    return rc;
+  const size_t lds = batch_lso_lds(N, H, wide);
+  if (lds > ctx->max_lds) return batch_lds_refusal(who, N, -1, H, wide, "", lds, ctx->max_lds);
   VRPMS_HIP(hipSetDevice(ctx->device));
   const TspBatchLsoArgs a{d_mats, d_start, R, N, S, rounds, (uint32_t)moves, (uint32_t)seed,
                           (uint32_t)(seed >> 32), d_tours, d_keys, d_durs, d_info};
-  void (*kernel)(TspBatchLsoArgs) =
-      wide ? (H == 24 ? tsp_batch_lso_kernel<int32_t, 24> : tsp_batch_lso_kernel<int32_t, 1>)
-           : (H == 24 ? tsp_batch_lso_kernel<uint16_t, 24> : tsp_batch_lso_kernel<uint16_t, 1>);
-  if (lds > 65536)
-    VRPMS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  kernel<<<(unsigned)R, 256, lds, (hipStream_t)stream>>>(a);
-  VRPMS_HIP(hipGetLastError());
+  const char* what = "";
+  const hipError_t e = batch_with_matrix(wide, H, [&](auto m, auto hm) {
+    return batch_launch_blocks(tsp_batch_lso_kernel<decltype(m), decltype(hm)::value>, a, (unsigned)R, lds,
+                               (hipStream_t)stream, &what);
+  });
+  if (e != hipSuccess) return hip_fail(e, what);
   return VRPMS_OK;
 }

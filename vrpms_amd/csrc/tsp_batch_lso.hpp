@@ -19,7 +19,9 @@
 
 #include <string>
 
+#include "batch_launch.hpp"
 #include "batch_ls.hpp"
+#include "batch_stage.hpp"
 #include "common.hpp"
 #include "ctx.hpp"
 #include "tour.hpp"
@@ -27,8 +29,6 @@
 namespace vrpms {
 
 constexpr int kLsoTypes = 5;
-constexpr int kBatchLsoMaxN = 65535;   // genes are uint16
-constexpr int kBatchLsoMaxS = 65535;
 
 struct TspBatchLsoArgs {
   const int32_t* mats;    // [R][H][N][N]
@@ -41,54 +41,70 @@ struct TspBatchLsoArgs {
   int32_t* info;          // [R][2]: the answer's start, the capped descents
 };
 
-struct BatchLsoLds {
-  size_t mat, row, cur, best, total;   // bytes of the matrix, one int32 row, one padded tour, one tour
+// What both mappings keep in LDS, the first parts of their dynamic LDS, in their
+// order: the [H][N][N] matrix (cells of `cell` bytes, padded to 16 bytes), per
+// wavefront the int32 rows F and B (H = 1) or T (H = 24) of align4(n + 2)
+// words, per wavefront the current tour of align8(n + 2) uint16 with node 0 at
+// both ends.  The host sums the parts, a kernel steps through them (LsoCarve);
+// I is size_t on the host and uint32_t in a kernel, as for BatchInstParts.
+template <typename I>
+struct BatchLsoParts {
+  I cells, mat_bytes, rows, row_words, cpad;   // rows: F and B, or T alone
+  __host__ __device__ BatchLsoParts(I N, I H, I cell) {
+    cells = H * N * N;
+    mat_bytes = batch_align<I>(cells * cell, 16);
+    rows = H == 1 ? 2 : 1;
+    row_words = batch_align<I>(N - 1 + 2, 4);
+    cpad = batch_align<I>(N - 1 + 2, 8);
+  }
+  __host__ __device__ I bytes() const { return mat_bytes + 4 * rows * row_words * 4 + 4 * cpad * 2; }
 };
 
-inline BatchLsoLds batch_lso_lds(int N, int H, int wide) {
-  BatchLsoLds l;
-  const size_t n = (size_t)N - 1;
-  l.mat = ((size_t)H * N * N * (wide ? 4 : 2) + 15) & ~(size_t)15;
-  l.row = ((n + 2 + 3) & ~(size_t)3) * 4;
-  l.cur = ((n + 2 + 7) & ~(size_t)7) * 2;
-  l.best = ((n + 7) & ~(size_t)7) * 2;
-  l.total = l.mat + 4 * ((H == 1 ? 2 : 1) * l.row + l.cur + l.best) + 4 * 16;
-  return l;
+// tsp_batch_lso_spread's own part behind them: [2][4] BatchLsRec
+constexpr size_t kBatchLsoSpreadOwnBytes = 2 * 4 * sizeof(BatchLsRec);
+
+inline size_t batch_lso_shared_bytes(int N, int H, int wide) {
+  return BatchLsoParts<size_t>((size_t)N, (size_t)H, wide ? 4 : 2).bytes();
 }
+
+// the kernels' carve of the shared parts; the kernel's own follow at `rest`
+template <typename MatT, int HM>
+struct LsoCarve {
+  static constexpr uint32_t kRows = HM == 1 ? 2u : 1u;
+  MatT* M;
+  int32_t* rows;    // [4][kRows][row_words]
+  uint16_t* curs;   // [4][cpad]
+  unsigned char* rest;
+  uint32_t cells, row_words, cpad;
+  VRPMS_DEV LsoCarve(unsigned char* mem, int N) {
+    const BatchLsoParts<uint32_t> l((uint32_t)N, (uint32_t)HM, (uint32_t)sizeof(MatT));
+    cells = l.cells;
+    row_words = l.row_words;
+    cpad = l.cpad;
+    M = reinterpret_cast<MatT*>(mem);
+    rows = reinterpret_cast<int32_t*>(mem + l.mat_bytes);
+    curs = reinterpret_cast<uint16_t*>(rows + 4 * kRows * row_words);
+    rest = reinterpret_cast<unsigned char*>(curs + 4 * cpad);
+  }
+  VRPMS_DEV int32_t* F(int wave) const { return rows + wave * kRows * row_words; }   // H = 24: the arrival row T
+  VRPMS_DEV int32_t* B(int wave) const { return F(wave) + (kRows - 1) * row_words; }   // H = 1 only
+  VRPMS_DEV uint16_t* P(int wave) const { return curs + wave * cpad; }   // node 0 at both ends
+};
 
 // the shape checks every entry point shares; 0 or the refusal's code
 inline int batch_lso_check(const char* who, int32_t N, int32_t H, int32_t wide) {
-  const std::string w(who);
-  if (N < 2 || N > kBatchLsoMaxN)
-    return fail(VRPMS_EINVAL, w + ": needs 2 <= N <= 65535 (" + std::to_string(N) + " given)");
-  if (H != 1 && H != 24)
-    return fail(VRPMS_EINVAL, w + ": H must be 1 or 24 (" + std::to_string(H) + " given)");
-  if (wide != 0 && wide != 1)
-    return fail(VRPMS_EINVAL, w + ": wide must be 0 (uint16 matrix) or 1 (int32) (" + std::to_string(wide) +
-                                  " given)");
-  return VRPMS_OK;
+  if (const int rc = batch_check_N(who, N)) return rc;
+  return batch_check_matrix(who, H, wide);
 }
 
 // the checks of the search's own arguments; 0 or the refusal's code
 inline int batch_lso_check_search(const char* who, int32_t S, int32_t rounds, int32_t moves) {
-  const std::string w(who);
-  if (S < 1 || S > kBatchLsoMaxS)
-    return fail(VRPMS_EINVAL, w + ": 1 <= S <= 65535 (" + std::to_string(S) + " given)");
-  if (rounds < 0)
-    return fail(VRPMS_EINVAL, w + ": rounds must not be negative (" + std::to_string(rounds) + " given)");
+  if (const int rc = batch_check_count(who, "S", S, kBatchMaxS)) return rc;
+  if (const int rc = batch_check_rounds(who, rounds)) return rc;
   if (moves < 1 || moves > 31)
-    return fail(VRPMS_EINVAL, w + ": 1 <= moves <= 31, bit t enabling move type t (" +
+    return fail(VRPMS_EINVAL, std::string(who) + ": 1 <= moves <= 31, bit t enabling move type t (" +
                                   std::to_string(moves) + " given)");
   return VRPMS_OK;
-}
-
-// the refusal of a launch whose request does not fit the device's LDS
-inline int batch_lso_lds_refusal(const char* who, int32_t N, int32_t H, int32_t wide, size_t lds,
-                                 size_t have) {
-  return fail(VRPMS_EINVAL, std::string(who) + ": a request of N = " + std::to_string(N) + ", H = " +
-                                std::to_string(H) + (wide ? " (int32 matrix)" : " (uint16 matrix)") +
-                                " needs " + std::to_string(lds) + " bytes of LDS (" +
-                                std::to_string(have) + " available)");
 }
 
 // the moves of type typ on n positions

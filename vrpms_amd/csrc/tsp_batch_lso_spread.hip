@@ -58,8 +58,6 @@
 
 namespace vrpms {
 
-constexpr int kBatchLsoMaxG = 65535;
-
 struct LsoSpreadHead {   // 24 bytes, in front of a record's tour
   uint64_t key;
   int32_t s, capped, dur, refused;
@@ -73,12 +71,11 @@ struct TspBatchLsoSpreadArgs {
 };
 
 inline size_t batch_lso_spread_lds(int N, int H, int wide) {
-  const BatchLsoLds l = batch_lso_lds(N, H, wide);
-  return l.mat + 4 * ((H == 1 ? 2 : 1) * l.row + l.cur) + 2 * 4 * sizeof(BatchLsRec);
+  return batch_lso_shared_bytes(N, H, wide) + kBatchLsoSpreadOwnBytes;
 }
 
 inline uint64_t batch_lso_spread_rec_bytes(int N) {
-  return sizeof(LsoSpreadHead) + 2 * (((uint64_t)N - 1 + 7) & ~(uint64_t)7);
+  return sizeof(LsoSpreadHead) + 2 * batch_align<uint64_t>((uint64_t)N - 1, 8);
 }
 
 template <typename MatT, int HM>
@@ -88,15 +85,8 @@ __global__ __launch_bounds__(256) void tsp_batch_lso_spread_kernel(TspBatchLsoSp
   const int N = a.N, n = N - 1, G = p.G;
   const int64_t r = blockIdx.x / (uint32_t)G;
   const int g = (int)(blockIdx.x % (uint32_t)G);
-  const uint32_t cells = (uint32_t)HM * (uint32_t)N * (uint32_t)N;
-  const uint32_t mat_bytes = (cells * (uint32_t)sizeof(MatT) + 15u) & ~15u;
-  constexpr uint32_t kRows = HM == 1 ? 2u : 1u;
-  const uint32_t row_words = ((uint32_t)n + 2u + 3u) & ~3u;
-  const uint32_t cpad = ((uint32_t)n + 2u + 7u) & ~7u;
-  MatT* M = reinterpret_cast<MatT*>(batch_lso_spread_lds_mem);
-  int32_t* rows = reinterpret_cast<int32_t*>(batch_lso_spread_lds_mem + mat_bytes);   // [4][kRows][row_words]
-  uint16_t* curs = reinterpret_cast<uint16_t*>(rows + 4 * kRows * row_words);          // [4][cpad]
-  BatchLsRec* rec = reinterpret_cast<BatchLsRec*>(curs + 4 * cpad);                    // [2][4]
+  const LsoCarve<MatT, HM> c(batch_lso_spread_lds_mem, N);
+  BatchLsRec* rec = reinterpret_cast<BatchLsRec*>(c.rest);   // [2][4]
 
   unsigned char* mine = p.work + (r * G + g) * (int64_t)p.rec_bytes;
   LsoSpreadHead* head = reinterpret_cast<LsoSpreadHead*>(mine);
@@ -104,17 +94,16 @@ __global__ __launch_bounds__(256) void tsp_batch_lso_spread_kernel(TspBatchLsoSp
 
   // stage and check the matrix; the selection kernel writes the refusal row.
   // The verdict goes through a word of the round records, free until then
-  if (lso_stage(a.mats, r, cells, M, reinterpret_cast<uint32_t*>(rec))) {
+  if (lso_stage(a.mats, r, c.cells, c.M, reinterpret_cast<uint32_t*>(rec))) {
     if (threadIdx.x == 0) *head = LsoSpreadHead{~0ull, -1, 0, 0, 1};
     return;
   }
 
   const int wave = (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = lane_id();
-  int32_t* F = rows + wave * kRows * row_words;   // H = 24: the arrival row T
-  int32_t* B = F + (kRows - 1) * row_words;       // H = 1 only
-  uint16_t* P = curs + wave * cpad;               // the wavefront's copy of the current tour, node 0 at both ends
+  int32_t *F = c.F(wave), *B = c.B(wave);
+  uint16_t* P = c.P(wave);                        // the wavefront's copy of the current tour
   uint16_t* A = P + 1;
-  const MatView<MatT, HM> D{M, (uint32_t)N, (uint32_t)N * (uint32_t)N, HM};
+  const MatView<MatT, HM> D{c.M, (uint32_t)N, (uint32_t)N * (uint32_t)N, HM};
   const int t0 = a.start[r];
   const uint32_t mask = a.moves;
 
@@ -193,26 +182,19 @@ __global__ __launch_bounds__(256) void tsp_batch_lso_select_kernel(TspBatchLsoSp
 using namespace vrpms;
 
 extern "C" int vrpms_tsp_batch_lso_spread_lds(int32_t N, int32_t H, int32_t wide, uint64_t* bytes) {
-  if (!bytes) return fail(VRPMS_EINVAL, "vrpms_tsp_batch_lso_spread_lds: bytes is NULL");
-  const int rc = batch_lso_check("vrpms_tsp_batch_lso_spread_lds", N, H, wide);
-  if (rc) return rc;
+  const char* who = "vrpms_tsp_batch_lso_spread_lds";
+  if (const int rc = batch_check_bytes(who, bytes)) return rc;
+  if (const int rc = batch_lso_check(who, N, H, wide)) return rc;
   *bytes = batch_lso_spread_lds(N, H, wide);
   return VRPMS_OK;
 }
 
 extern "C" int vrpms_tsp_batch_lso_spread_work(int32_t R, int32_t N, int32_t G, uint64_t* bytes) {
-  if (!bytes) return fail(VRPMS_EINVAL, "vrpms_tsp_batch_lso_spread_work: bytes is NULL");
-  if (R < 0) return fail(VRPMS_EINVAL, "vrpms_tsp_batch_lso_spread_work: R must not be negative");
-  const int rc = batch_lso_check("vrpms_tsp_batch_lso_spread_work", N, 1, 0);
-  if (rc) return rc;
-  if (G < 1 || G > kBatchLsoMaxG)
-    return fail(VRPMS_EINVAL,
-                "vrpms_tsp_batch_lso_spread_work: 1 <= G <= 65535 (" + std::to_string(G) + " given)");
-  if ((uint64_t)R * (uint64_t)G > 0x7fffffffull)
-    return fail(VRPMS_EINVAL, "vrpms_tsp_batch_lso_spread_work: R * G = " +
-                                  std::to_string((uint64_t)R * (uint64_t)G) + " records are above 2^31 - 1");
-  *bytes = (uint64_t)R * (uint64_t)G * batch_lso_spread_rec_bytes(N);   // < 2^31 2^18
-  return VRPMS_OK;
+  const char* who = "vrpms_tsp_batch_lso_spread_work";
+  if (const int rc = batch_check_bytes(who, bytes)) return rc;
+  if (const int rc = batch_check_R(who, R)) return rc;
+  if (const int rc = batch_lso_check(who, N, 1, 0)) return rc;
+  return batch_work_bytes(who, R, G, batch_lso_spread_rec_bytes(N), bytes);
 }
 
 extern "C" int vrpms_tsp_batch_lso_spread(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_start,
@@ -222,45 +204,31 @@ extern "C" int vrpms_tsp_batch_lso_spread(vrpms_ctx* ctx, const int32_t* d_mats,
                                           uint64_t* d_keys, int32_t* d_durs, int32_t* d_info,
                                           void* stream) {
   const char* who = "vrpms_tsp_batch_lso_spread";
-  const std::string w(who);
-  if (!ctx) return fail(VRPMS_EINVAL, w + ": ctx is NULL");
-  if (R < 0) return fail(VRPMS_EINVAL, w + ": R must not be negative");
-  const int rc = batch_lso_check(who, N, H, wide);
-  if (rc) return rc;
-  const int rs = batch_lso_check_search(who, S, rounds, moves);
-  if (rs) return rs;
-  if (G < 1 || G > kBatchLsoMaxG)
-    return fail(VRPMS_EINVAL, w + ": 1 <= G <= 65535 (" + std::to_string(G) + " given)");
+  if (const int rc = batch_check_ctx(who, ctx, R)) return rc;
+  if (const int rc = batch_lso_check(who, N, H, wide)) return rc;
+  if (const int rc = batch_lso_check_search(who, S, rounds, moves)) return rc;
+  if (const int rc = batch_check_count(who, "G", G, kBatchMaxG)) return rc;
   if (R == 0) return VRPMS_OK;
-  if (!d_mats || !d_start || !d_tours || !d_keys || !d_durs || !d_info)
-    return fail(VRPMS_EINVAL, w + ": NULL matrix/start/tour/key/duration/info buffer");
+  if (const int rc = batch_check_buffers(who, "matrix/start/tour/key/duration/info",
+                                         {d_mats, d_start, d_tours, d_keys, d_durs, d_info}))
+    return rc;
   const int Gc = G < S ? G : S;   // a workgroup without a start cannot occur
-  if ((uint64_t)R * (uint64_t)Gc > 0x7fffffffull)
-    return fail(VRPMS_EINVAL, w + ": R * min(G, S) = " + std::to_string((uint64_t)R * (uint64_t)Gc) +
-                                  " workgroups are above 2^31 - 1");
-  const uint64_t rec = batch_lso_spread_rec_bytes(N), need = (uint64_t)R * (uint64_t)Gc * rec;
-  if (!d_work) return fail(VRPMS_EINVAL, w + ": the workspace is NULL");
-  if ((uintptr_t)d_work & 7u) return fail(VRPMS_EINVAL, w + ": the workspace must be 8-byte aligned");
-  if (work_bytes < need)
-    return fail(VRPMS_EINVAL, w + ": the workspace has " + std::to_string(work_bytes) + " bytes, R = " +
-                                  std::to_string(R) + " requests of min(G, S) = " + std::to_string(Gc) +
-                                  " workgroups need " + std::to_string(need));
+  const uint64_t rec = batch_lso_spread_rec_bytes(N);
+  if (const int rc = batch_check_work(who, R, Gc, rec, d_work, work_bytes)) return rc;
   const size_t lds = batch_lso_spread_lds(N, H, wide);
-  if (lds > ctx->max_lds) return batch_lso_lds_refusal(who, N, H, wide, lds, ctx->max_lds);
+  if (lds > ctx->max_lds) return batch_lds_refusal(who, N, -1, H, wide, "", lds, ctx->max_lds);
   VRPMS_HIP(hipSetDevice(ctx->device));
   const TspBatchLsoSpreadArgs p{
       TspBatchLsoArgs{d_mats, d_start, R, N, S, rounds, (uint32_t)moves, (uint32_t)seed,
                       (uint32_t)(seed >> 32), d_tours, d_keys, d_durs, d_info},
       Gc, static_cast<unsigned char*>(d_work), (uint32_t)rec};
-  void (*descend)(TspBatchLsoSpreadArgs) =
-      wide ? (H == 24 ? tsp_batch_lso_spread_kernel<int32_t, 24> : tsp_batch_lso_spread_kernel<int32_t, 1>)
-           : (H == 24 ? tsp_batch_lso_spread_kernel<uint16_t, 24> : tsp_batch_lso_spread_kernel<uint16_t, 1>);
-  if (lds > 65536)
-    VRPMS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(descend),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  descend<<<(unsigned)((uint64_t)R * (uint64_t)Gc), 256, lds, (hipStream_t)stream>>>(p);
-  VRPMS_HIP(hipGetLastError());
-  tsp_batch_lso_select_kernel<<<(unsigned)R, 256, 0, (hipStream_t)stream>>>(p);
-  VRPMS_HIP(hipGetLastError());
+  const hipStream_t s = (hipStream_t)stream;
+  const char* what = "";
+  hipError_t e = batch_with_matrix(wide, H, [&](auto m, auto hm) {
+    return batch_launch_blocks(tsp_batch_lso_spread_kernel<decltype(m), decltype(hm)::value>, p,
+                               (unsigned)((uint64_t)R * (uint64_t)Gc), lds, s, &what);
+  });
+  if (e == hipSuccess) e = batch_enqueue(tsp_batch_lso_select_kernel, p, (unsigned)R, 0, s, &what);
+  if (e != hipSuccess) return hip_fail(e, what);
   return VRPMS_OK;
 }

@@ -52,6 +52,7 @@
 #include <string>
 
 #include "aco.hpp"
+#include "batch_launch.hpp"
 #include "batch_stage.hpp"
 #include "common.hpp"
 #include "ctx.hpp"
@@ -66,8 +67,6 @@
 
 namespace vrpms {
 
-constexpr int kBatchAcoMaxK = 64;      // one lane per route in the final walk
-constexpr int kBatchAcoMaxN = 65535;   // customers are uint16
 constexpr int kBatchAcoMaxA = 256;     // one lane per ant
 constexpr int kBatchAcoWaveMaxN = 128; // the wavefront-per-ant roulette at CH = 2
 constexpr int kBatchAcoLaneMaxN = VRPMS_BATCH_ACO_LANE_MAX_N;
@@ -88,27 +87,16 @@ struct VrpBatchAcoArgs {
   int8_t* veh;            // [R][n]
 };
 
-struct BatchAcoLds {
-  size_t mat, dem, row, red, tau, eta, rows, total;   // bytes of every part
-  int rs;                                             // row stride
-};
-
-constexpr size_t kBatchAcoRedBytes = 64;
-
 __host__ __device__ inline uint32_t batch_aco_row_stride(int n) { return 2u * ((((uint32_t)n + 1u) >> 1) | 1u); }
 
-inline BatchAcoLds batch_aco_lds(int N, int K, int H, int wide, int A) {
-  BatchAcoLds l;
-  l.rs = (int)batch_aco_row_stride(N - 1);
-  l.mat = ((size_t)H * N * N * (wide ? 4 : 2) + 15) & ~(size_t)15;
-  l.dem = (((size_t)N + 3) & ~(size_t)3) * 4;
-  l.row = (((size_t)K + 3) & ~(size_t)3) * 4;
-  l.red = kBatchAcoRedBytes;
-  l.tau = (size_t)N * N * 4;
-  l.eta = (size_t)N * N * 4;
-  l.rows = (size_t)(A + 1) * l.rs * 2;
-  l.total = l.mat + l.dem + 2 * l.row + l.red + l.tau + l.eta + l.rows;
-  return l;
+constexpr uint32_t kBatchAcoRedBytes = 64;
+
+// The kernel's own parts behind the instance: the reduction words, tau and eta
+// ([N][N] uint32 each), the A ants' rows and the best-so-far's (rs uint16 each).
+// The kernel steps through them itself (below).
+inline size_t batch_aco_lds(int N, int K, int H, int wide, int A) {
+  const size_t rs = batch_aco_row_stride(N - 1);
+  return batch_inst_bytes(N, K, H, wide) + kBatchAcoRedBytes + 2 * (size_t)N * N * 4 + ((size_t)A + 1) * rs * 2;
 }
 
 template <typename MatT, int HM>
@@ -274,18 +262,10 @@ __global__ __launch_bounds__(256) void vrp_batch_aco_kernel(VrpBatchAcoArgs a) {
 
 // the shape checks both entry points share; 0 or the refusal's code
 static int batch_aco_check(const char* who, int32_t N, int32_t K, int32_t H, int32_t wide, int32_t A) {
-  const std::string w(who);
-  if (N < 2 || N > kBatchAcoMaxN)
-    return fail(VRPMS_EINVAL, w + ": needs 2 <= N <= 65535 (" + std::to_string(N) + " given)");
-  if (K < 1 || K > kBatchAcoMaxK)
-    return fail(VRPMS_EINVAL, w + ": one lane per route needs 1 <= K <= 64 (" + std::to_string(K) + " given)");
-  if (H != 1 && H != 24)
-    return fail(VRPMS_EINVAL, w + ": H must be 1 or 24 (" + std::to_string(H) + " given)");
-  if (wide != 0 && wide != 1)
-    return fail(VRPMS_EINVAL, w + ": wide must be 0 (uint16 matrix) or 1 (int32) (" + std::to_string(wide) +
-                                  " given)");
+  if (const int rc = batch_check_shape(who, N, K, H, wide)) return rc;
   if (A < 1 || A > kBatchAcoMaxA)
-    return fail(VRPMS_EINVAL, w + ": one lane per ant needs 1 <= A <= 256 (" + std::to_string(A) + " given)");
+    return fail(VRPMS_EINVAL,
+                std::string(who) + ": one lane per ant needs 1 <= A <= 256 (" + std::to_string(A) + " given)");
   return VRPMS_OK;
 }
 
@@ -295,10 +275,10 @@ using namespace vrpms;
 
 extern "C" int vrpms_vrp_batch_aco_lds(int32_t N, int32_t K, int32_t H, int32_t wide, int32_t A,
                                        uint64_t* bytes) {
-  if (!bytes) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_aco_lds: bytes is NULL");
-  const int rc = batch_aco_check("vrpms_vrp_batch_aco_lds", N, K, H, wide, A);
-  if (rc) return rc;
-  *bytes = batch_aco_lds(N, K, H, wide, A).total;
+  const char* who = "vrpms_vrp_batch_aco_lds";
+  if (const int rc = batch_check_bytes(who, bytes)) return rc;
+  if (const int rc = batch_aco_check(who, N, K, H, wide, A)) return rc;
+  *bytes = batch_aco_lds(N, K, H, wide, A);
   return VRPMS_OK;
 }
 
@@ -309,12 +289,10 @@ extern "C" int vrpms_vrp_batch_aco(vrpms_ctx* ctx, const int32_t* d_mats, const 
                                    int32_t evap_shift, int32_t bsf_period, uint64_t seed,
                                    uint16_t* d_tours, uint64_t* d_keys, int32_t* d_durs, int8_t* d_veh,
                                    void* stream) {
-  if (!ctx) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_aco: ctx is NULL");
-  if (R < 0) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_aco: R must not be negative");
-  const int rc = batch_aco_check("vrpms_vrp_batch_aco", N, K, H, wide, A);
-  if (rc) return rc;
-  if (objective != VRPMS_OBJ_SUM && objective != VRPMS_OBJ_MAX)
-    return fail(VRPMS_EINVAL, "vrpms_vrp_batch_aco: objective must be VRPMS_OBJ_SUM or VRPMS_OBJ_MAX");
+  const char* who = "vrpms_vrp_batch_aco";
+  if (const int rc = batch_check_ctx(who, ctx, R)) return rc;
+  if (const int rc = batch_aco_check(who, N, K, H, wide, A)) return rc;
+  if (const int rc = batch_check_objective(who, objective)) return rc;
   if (I < 1)
     return fail(VRPMS_EINVAL, "vrpms_vrp_batch_aco: I must be at least 1 (" + std::to_string(I) + " given)");
   if (evap_shift < 1 || evap_shift > 31)
@@ -328,16 +306,12 @@ extern "C" int vrpms_vrp_batch_aco(vrpms_ctx* ctx, const int32_t* d_mats, const 
                                   std::to_string(tau_min) + ", " + std::to_string(tau0) + ", " +
                                   std::to_string(tau_max) + " given)");
   if (R == 0) return VRPMS_OK;
-  if (!d_mats || !d_demand || !d_cap || !d_start || !d_tours || !d_keys || !d_durs || !d_veh)
-    return fail(VRPMS_EINVAL,
-                "vrpms_vrp_batch_aco: NULL matrix/demand/capacity/start/tour/key/duration/vehicle buffer");
-  const size_t lds = batch_aco_lds(N, K, H, wide, A).total;
+  if (const int rc = batch_check_buffers(who, "matrix/demand/capacity/start/tour/key/duration/vehicle",
+                                         {d_mats, d_demand, d_cap, d_start, d_tours, d_keys, d_durs, d_veh}))
+    return rc;
+  const size_t lds = batch_aco_lds(N, K, H, wide, A);
   if (lds > ctx->max_lds)
-    return fail(VRPMS_EINVAL, "vrpms_vrp_batch_aco: a request of N = " + std::to_string(N) + ", K = " +
-                                  std::to_string(K) + ", H = " + std::to_string(H) +
-                                  (wide ? " (int32 matrix)" : " (uint16 matrix)") + " at A = " +
-                                  std::to_string(A) + " needs " + std::to_string(lds) +
-                                  " bytes of LDS (" + std::to_string(ctx->max_lds) + " available)");
+    return batch_lds_refusal(who, N, K, H, wide, " at A = " + std::to_string(A), lds, ctx->max_lds);
   // 10 * 129 * 129 bytes are above the 160 KiB of a CU, so this refuses nothing
   // the formula admits there; it keeps a larger LDS from outgrowing CH = 2
   if (N > kBatchAcoWaveMaxN)
@@ -347,13 +321,11 @@ extern "C" int vrpms_vrp_batch_aco(vrpms_ctx* ctx, const int32_t* d_mats, const 
   const VrpBatchAcoArgs a{d_mats, d_demand, d_cap, d_start, R, N, K, H, objective, A, I,
                           tau0, tau_min, tau_max, (uint32_t)evap_shift, bsf_period,
                           (uint32_t)seed, (uint32_t)(seed >> 32), d_tours, d_keys, d_durs, d_veh};
-  void (*kernel)(VrpBatchAcoArgs) =
-      wide ? (H == 24 ? vrp_batch_aco_kernel<int32_t, 24> : vrp_batch_aco_kernel<int32_t, 1>)
-           : (H == 24 ? vrp_batch_aco_kernel<uint16_t, 24> : vrp_batch_aco_kernel<uint16_t, 1>);
-  if (lds > 65536)
-    VRPMS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  kernel<<<(unsigned)R, 256, lds, (hipStream_t)stream>>>(a);
-  VRPMS_HIP(hipGetLastError());
+  const char* what = "";
+  const hipError_t e = batch_with_matrix(wide, H, [&](auto m, auto hm) {
+    return batch_launch_blocks(vrp_batch_aco_kernel<decltype(m), decltype(hm)::value>, a, (unsigned)R, lds,
+                               (hipStream_t)stream, &what);
+  });
+  if (e != hipSuccess) return hip_fail(e, what);
   return VRPMS_OK;
 }

@@ -43,6 +43,7 @@
 
 #include <string>
 
+#include "batch_launch.hpp"
 #include "batch_stage.hpp"
 #include "common.hpp"
 #include "ctx.hpp"
@@ -52,8 +53,6 @@
 
 namespace vrpms {
 
-constexpr int kBatchGaMaxK = 64;      // one lane per route in the final walk
-constexpr int kBatchGaMaxN = 65535;   // genes are uint16
 constexpr int kBatchGaMaxP = 256;     // one lane per member
 
 struct VrpBatchGaArgs {
@@ -70,11 +69,6 @@ struct VrpBatchGaArgs {
   int8_t* veh;            // [R][n]
 };
 
-struct BatchGaLds {
-  size_t mat, dem, row, sortk, sorti, keys, used, rows, maps, total;   // bytes of every part
-  int M, rs;                                                           // sort pairs, row stride
-};
-
 __host__ __device__ inline int batch_ga_sort_pairs(int P) {
   int M = 2;
   while (M < 2 * P) M <<= 1;
@@ -87,21 +81,13 @@ __host__ __device__ inline uint32_t batch_ga_used_words(int N) {
   return ((((uint32_t)N + 31u) >> 5) + 3u) & ~3u;
 }
 
-inline BatchGaLds batch_ga_lds(int N, int K, int H, int wide, int P) {
-  BatchGaLds l;
-  l.M = batch_ga_sort_pairs(P);
-  l.rs = (int)batch_ga_row_stride(N - 1);
-  l.mat = ((size_t)H * N * N * (wide ? 4 : 2) + 15) & ~(size_t)15;
-  l.dem = (((size_t)N + 3) & ~(size_t)3) * 4;
-  l.row = (((size_t)K + 3) & ~(size_t)3) * 4;
-  l.sortk = (size_t)l.M * 8;
-  l.sorti = (size_t)l.M * 4;
-  l.keys = (size_t)2 * P * 8;
-  l.used = (size_t)4 * batch_ga_used_words(N) * 4;
-  l.rows = (size_t)2 * P * l.rs * 2;
-  l.maps = (size_t)2 * P * 2;
-  l.total = l.mat + l.dem + 2 * l.row + l.sortk + l.sorti + l.keys + l.used + l.rows + l.maps;
-  return l;
+// The kernel's own parts behind the instance: M2 sort pairs (uint64 key, uint32
+// index), P parent and P child keys, the four `used` bitmaps, 2P rows of rs
+// genes, prow and crow.  The kernel steps through them itself (below).
+inline size_t batch_ga_lds(int N, int K, int H, int wide, int P) {
+  const size_t M2 = batch_ga_sort_pairs(P), rs = batch_ga_row_stride(N - 1), uw = batch_ga_used_words(N);
+  return batch_inst_bytes(N, K, H, wide) + 12 * M2 + 2 * 8 * (size_t)P + 4 * 4 * uw + 2 * (size_t)P * rs * 2 +
+         2 * 2 * (size_t)P;
 }
 
 template <typename MatT, int HM>
@@ -346,18 +332,10 @@ __global__ __launch_bounds__(256) void vrp_batch_ga_kernel(VrpBatchGaArgs a) {
 
 // the shape checks both entry points share; 0 or the refusal's code
 static int batch_ga_check(const char* who, int32_t N, int32_t K, int32_t H, int32_t wide, int32_t P) {
-  const std::string w(who);
-  if (N < 2 || N > kBatchGaMaxN)
-    return fail(VRPMS_EINVAL, w + ": needs 2 <= N <= 65535 (" + std::to_string(N) + " given)");
-  if (K < 1 || K > kBatchGaMaxK)
-    return fail(VRPMS_EINVAL, w + ": one lane per route needs 1 <= K <= 64 (" + std::to_string(K) + " given)");
-  if (H != 1 && H != 24)
-    return fail(VRPMS_EINVAL, w + ": H must be 1 or 24 (" + std::to_string(H) + " given)");
-  if (wide != 0 && wide != 1)
-    return fail(VRPMS_EINVAL, w + ": wide must be 0 (uint16 matrix) or 1 (int32) (" + std::to_string(wide) +
-                                  " given)");
+  if (const int rc = batch_check_shape(who, N, K, H, wide)) return rc;
   if (P < 2 || P > kBatchGaMaxP)
-    return fail(VRPMS_EINVAL, w + ": one lane per member needs 2 <= P <= 256 (" + std::to_string(P) + " given)");
+    return fail(VRPMS_EINVAL, std::string(who) + ": one lane per member needs 2 <= P <= 256 (" +
+                                  std::to_string(P) + " given)");
   return VRPMS_OK;
 }
 
@@ -367,10 +345,10 @@ using namespace vrpms;
 
 extern "C" int vrpms_vrp_batch_ga_lds(int32_t N, int32_t K, int32_t H, int32_t wide, int32_t P,
                                       uint64_t* bytes) {
-  if (!bytes) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_ga_lds: bytes is NULL");
-  const int rc = batch_ga_check("vrpms_vrp_batch_ga_lds", N, K, H, wide, P);
-  if (rc) return rc;
-  *bytes = batch_ga_lds(N, K, H, wide, P).total;
+  const char* who = "vrpms_vrp_batch_ga_lds";
+  if (const int rc = batch_check_bytes(who, bytes)) return rc;
+  if (const int rc = batch_ga_check(who, N, K, H, wide, P)) return rc;
+  *bytes = batch_ga_lds(N, K, H, wide, P);
   return VRPMS_OK;
 }
 
@@ -379,36 +357,28 @@ extern "C" int vrpms_vrp_batch_ga(vrpms_ctx* ctx, const int32_t* d_mats, const i
                                   int32_t K, int32_t H, int32_t objective, int32_t wide, int32_t P,
                                   int32_t G, uint32_t pmut, uint64_t seed, uint16_t* d_tours,
                                   uint64_t* d_keys, int32_t* d_durs, int8_t* d_veh, void* stream) {
-  if (!ctx) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_ga: ctx is NULL");
-  if (R < 0) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_ga: R must not be negative");
-  const int rc = batch_ga_check("vrpms_vrp_batch_ga", N, K, H, wide, P);
-  if (rc) return rc;
-  if (objective != VRPMS_OBJ_SUM && objective != VRPMS_OBJ_MAX)
-    return fail(VRPMS_EINVAL, "vrpms_vrp_batch_ga: objective must be VRPMS_OBJ_SUM or VRPMS_OBJ_MAX");
+  const char* who = "vrpms_vrp_batch_ga";
+  if (const int rc = batch_check_ctx(who, ctx, R)) return rc;
+  if (const int rc = batch_ga_check(who, N, K, H, wide, P)) return rc;
+  if (const int rc = batch_check_objective(who, objective)) return rc;
   if (G < 0)
     return fail(VRPMS_EINVAL, "vrpms_vrp_batch_ga: G must not be negative (" + std::to_string(G) + " given)");
   if (R == 0) return VRPMS_OK;
-  if (!d_mats || !d_demand || !d_cap || !d_start || !d_tours || !d_keys || !d_durs || !d_veh)
-    return fail(VRPMS_EINVAL,
-                "vrpms_vrp_batch_ga: NULL matrix/demand/capacity/start/tour/key/duration/vehicle buffer");
-  const size_t lds = batch_ga_lds(N, K, H, wide, P).total;
+  if (const int rc = batch_check_buffers(who, "matrix/demand/capacity/start/tour/key/duration/vehicle",
+                                         {d_mats, d_demand, d_cap, d_start, d_tours, d_keys, d_durs, d_veh}))
+    return rc;
+  const size_t lds = batch_ga_lds(N, K, H, wide, P);
   if (lds > ctx->max_lds)
-    return fail(VRPMS_EINVAL, "vrpms_vrp_batch_ga: a request of N = " + std::to_string(N) + ", K = " +
-                                  std::to_string(K) + ", H = " + std::to_string(H) +
-                                  (wide ? " (int32 matrix)" : " (uint16 matrix)") + " at P = " +
-                                  std::to_string(P) + " needs " + std::to_string(lds) +
-                                  " bytes of LDS (" + std::to_string(ctx->max_lds) + " available)");
+    return batch_lds_refusal(who, N, K, H, wide, " at P = " + std::to_string(P), lds, ctx->max_lds);
   VRPMS_HIP(hipSetDevice(ctx->device));
   const VrpBatchGaArgs a{d_mats, d_demand, d_cap, d_start, R,    N,
                          K,      H,        objective, P,   G,    pmut,
                          (uint32_t)seed, (uint32_t)(seed >> 32), d_tours, d_keys, d_durs, d_veh};
-  void (*kernel)(VrpBatchGaArgs) =
-      wide ? (H == 24 ? vrp_batch_ga_kernel<int32_t, 24> : vrp_batch_ga_kernel<int32_t, 1>)
-           : (H == 24 ? vrp_batch_ga_kernel<uint16_t, 24> : vrp_batch_ga_kernel<uint16_t, 1>);
-  if (lds > 65536)
-    VRPMS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  kernel<<<(unsigned)R, 256, lds, (hipStream_t)stream>>>(a);
-  VRPMS_HIP(hipGetLastError());
+  const char* what = "";
+  const hipError_t e = batch_with_matrix(wide, H, [&](auto m, auto hm) {
+    return batch_launch_blocks(vrp_batch_ga_kernel<decltype(m), decltype(hm)::value>, a, (unsigned)R, lds,
+                               (hipStream_t)stream, &what);
+  });
+  if (e != hipSuccess) return hip_fail(e, what);
   return VRPMS_OK;
 }

@@ -42,48 +42,9 @@
 // + 4 * 16                                   the waves' best key, best s, capped count
 #include <hip/hip_runtime.h>
 
-#include <string>
-
-#include "batch_ls.hpp"
-#include "batch_stage.hpp"
-#include "common.hpp"
-#include "ctx.hpp"
-#include "staging.hpp"
-#include "tour.hpp"
+#include "vrp_batch_lsr.hpp"
 
 namespace vrpms {
-
-constexpr int kBatchLsMaxK = 64;      // one lane per route in the final walk
-constexpr int kBatchLsMaxN = 65535;   // genes are uint16
-constexpr int kBatchLsMaxS = 65535;
-
-struct VrpBatchLsArgs {
-  const int32_t* mats;    // [R][H][N][N]
-  const int32_t* demand;  // [R][N]
-  const int32_t* cap;     // [R][K]
-  const int32_t* start;   // [R][K]
-  int R, N, K, H, objective, S, rounds;
-  uint32_t seed_lo, seed_hi;
-  uint16_t* tours;        // [R][n]
-  uint64_t* keys;         // [R]
-  int32_t* durs;          // [R][K]
-  int8_t* veh;            // [R][n]
-  int32_t* info;          // [R][2]: the answer's start, the capped descents
-};
-
-struct BatchLsLds {
-  size_t mat, dem, row, tour, total;   // bytes of the matrix, the demand row, one K row, one tour
-};
-
-inline BatchLsLds batch_ls_lds(int N, int K, int H, int wide) {
-  BatchLsLds l;
-  l.mat = ((size_t)H * N * N * (wide ? 4 : 2) + 15) & ~(size_t)15;
-  l.dem = (((size_t)N + 3) & ~(size_t)3) * 4;
-  l.row = (((size_t)K + 3) & ~(size_t)3) * 4;
-  l.tour = (((size_t)N - 1 + 7) & ~(size_t)7) * 2;
-  l.total = l.mat + l.dem + 2 * l.row + 4 * 2 * l.tour + 4 * 16;
-  return l;
-}
 
 template <typename MatT, int HM>
 __global__ __launch_bounds__(256) void vrp_batch_ls_kernel(VrpBatchLsArgs a) {
@@ -161,30 +122,15 @@ __global__ __launch_bounds__(256) void vrp_batch_ls_kernel(VrpBatchLsArgs a) {
   }
 }
 
-// the shape checks both entry points share; 0 or the refusal's code
-static int batch_ls_check(const char* who, int32_t N, int32_t K, int32_t H, int32_t wide) {
-  const std::string w(who);
-  if (N < 2 || N > kBatchLsMaxN)
-    return fail(VRPMS_EINVAL, w + ": needs 2 <= N <= 65535 (" + std::to_string(N) + " given)");
-  if (K < 1 || K > kBatchLsMaxK)
-    return fail(VRPMS_EINVAL, w + ": one lane per route needs 1 <= K <= 64 (" + std::to_string(K) + " given)");
-  if (H != 1 && H != 24)
-    return fail(VRPMS_EINVAL, w + ": H must be 1 or 24 (" + std::to_string(H) + " given)");
-  if (wide != 0 && wide != 1)
-    return fail(VRPMS_EINVAL, w + ": wide must be 0 (uint16 matrix) or 1 (int32) (" + std::to_string(wide) +
-                                  " given)");
-  return VRPMS_OK;
-}
-
 }  // namespace vrpms
 
 using namespace vrpms;
 
 extern "C" int vrpms_vrp_batch_ls_lds(int32_t N, int32_t K, int32_t H, int32_t wide, uint64_t* bytes) {
-  if (!bytes) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_ls_lds: bytes is NULL");
-  const int rc = batch_ls_check("vrpms_vrp_batch_ls_lds", N, K, H, wide);
-  if (rc) return rc;
-  *bytes = batch_ls_lds(N, K, H, wide).total;
+  const char* who = "vrpms_vrp_batch_ls_lds";
+  if (const int rc = batch_check_bytes(who, bytes)) return rc;
+  if (const int rc = batch_check_shape(who, N, K, H, wide)) return rc;
+  *bytes = batch_ls_lds(N, K, H, wide, N - 1);
   return VRPMS_OK;
 }
 
@@ -193,39 +139,13 @@ extern "C" int vrpms_vrp_batch_ls(vrpms_ctx* ctx, const int32_t* d_mats, const i
                                   int32_t K, int32_t H, int32_t objective, int32_t wide, int32_t S,
                                   int32_t rounds, uint64_t seed, uint16_t* d_tours, uint64_t* d_keys,
                                   int32_t* d_durs, int8_t* d_veh, int32_t* d_info, void* stream) {
-  if (!ctx) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_ls: ctx is NULL");
-  if (R < 0) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_ls: R must not be negative");
-  const int rc = batch_ls_check("vrpms_vrp_batch_ls", N, K, H, wide);
-  if (rc) return rc;
-  if (objective != VRPMS_OBJ_SUM && objective != VRPMS_OBJ_MAX)
-    return fail(VRPMS_EINVAL, "vrpms_vrp_batch_ls: objective must be VRPMS_OBJ_SUM or VRPMS_OBJ_MAX");
-  if (S < 1 || S > kBatchLsMaxS)
-    return fail(VRPMS_EINVAL, "vrpms_vrp_batch_ls: 1 <= S <= 65535 (" + std::to_string(S) + " given)");
-  if (rounds < 0)
-    return fail(VRPMS_EINVAL,
-                "vrpms_vrp_batch_ls: rounds must not be negative (" + std::to_string(rounds) + " given)");
-  if (R == 0) return VRPMS_OK;
-  if (!d_mats || !d_demand || !d_cap || !d_start || !d_tours || !d_keys || !d_durs || !d_veh || !d_info)
-    return fail(VRPMS_EINVAL,
-                "vrpms_vrp_batch_ls: NULL matrix/demand/capacity/start/tour/key/duration/vehicle/info buffer");
-  const size_t lds = batch_ls_lds(N, K, H, wide).total;
-  if (lds > ctx->max_lds)
-    return fail(VRPMS_EINVAL, "vrpms_vrp_batch_ls: a request of N = " + std::to_string(N) + ", K = " +
-                                  std::to_string(K) + ", H = " + std::to_string(H) +
-                                  (wide ? " (int32 matrix)" : " (uint16 matrix)") + " needs " +
-                                  std::to_string(lds) + " bytes of LDS (" + std::to_string(ctx->max_lds) +
-                                  " available)");
-  VRPMS_HIP(hipSetDevice(ctx->device));
+  const char* who = "vrpms_vrp_batch_ls";
+  if (const int rc = batch_check_ctx(who, ctx, R)) return rc;
+  if (const int rc = batch_check_shape(who, N, K, H, wide)) return rc;
   const VrpBatchLsArgs a{d_mats, d_demand, d_cap,  d_start, R,      N,      K,      H,     objective,
                          S,      rounds,   (uint32_t)seed, (uint32_t)(seed >> 32), d_tours, d_keys,
                          d_durs, d_veh,    d_info};
-  void (*kernel)(VrpBatchLsArgs) =
-      wide ? (H == 24 ? vrp_batch_ls_kernel<int32_t, 24> : vrp_batch_ls_kernel<int32_t, 1>)
-           : (H == 24 ? vrp_batch_ls_kernel<uint16_t, 24> : vrp_batch_ls_kernel<uint16_t, 1>);
-  if (lds > 65536)
-    VRPMS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  kernel<<<(unsigned)R, 256, lds, (hipStream_t)stream>>>(a);
-  VRPMS_HIP(hipGetLastError());
-  return VRPMS_OK;
+  return batch_ls_launch(who, ctx, a, wide, N - 1, stream, [](auto m, auto hm) {
+    return vrp_batch_ls_kernel<decltype(m), decltype(hm)::value>;
+  });
 }

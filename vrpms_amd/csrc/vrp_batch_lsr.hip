@@ -38,20 +38,12 @@
 // + 4 * 16                                   the waves' best key, best s, capped count
 #include <hip/hip_runtime.h>
 
-#include <string>
-
-#include "batch_ls.hpp"
-#include "batch_stage.hpp"
-#include "common.hpp"
-#include "ctx.hpp"
-#include "staging.hpp"
-#include "tour.hpp"
 #include "vrp_batch_lsr.hpp"
 
 namespace vrpms {
 
 template <typename MatT, int HM>
-__global__ __launch_bounds__(256) void vrp_batch_lsr_kernel(VrpBatchLsrArgs a) {
+__global__ __launch_bounds__(256) void vrp_batch_lsr_kernel(VrpBatchLsArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char batch_lsr_lds_mem[];
   const int N = a.N, n = N - 1, K = a.K, L = n + K - 1;
   const int64_t r = blockIdx.x;
@@ -132,10 +124,10 @@ __global__ __launch_bounds__(256) void vrp_batch_lsr_kernel(VrpBatchLsrArgs a) {
 using namespace vrpms;
 
 extern "C" int vrpms_vrp_batch_lsr_lds(int32_t N, int32_t K, int32_t H, int32_t wide, uint64_t* bytes) {
-  if (!bytes) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_lsr_lds: bytes is NULL");
-  const int rc = batch_lsr_check("vrpms_vrp_batch_lsr_lds", N, K, H, wide);
-  if (rc) return rc;
-  *bytes = batch_lsr_lds(N, K, H, wide).total;
+  const char* who = "vrpms_vrp_batch_lsr_lds";
+  if (const int rc = batch_check_bytes(who, bytes)) return rc;
+  if (const int rc = batch_lsr_check(who, N, K, H, wide)) return rc;
+  *bytes = batch_ls_lds(N, K, H, wide, N - 1 + K - 1);
   return VRPMS_OK;
 }
 
@@ -144,30 +136,13 @@ extern "C" int vrpms_vrp_batch_lsr(vrpms_ctx* ctx, const int32_t* d_mats, const 
                                    int32_t K, int32_t H, int32_t objective, int32_t wide, int32_t S,
                                    int32_t rounds, uint64_t seed, uint16_t* d_tours, uint64_t* d_keys,
                                    int32_t* d_durs, int8_t* d_veh, int32_t* d_info, void* stream) {
-  if (!ctx) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_lsr: ctx is NULL");
-  if (R < 0) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_lsr: R must not be negative");
-  const int rc = batch_lsr_check("vrpms_vrp_batch_lsr", N, K, H, wide);
-  if (rc) return rc;
-  const int rs = batch_lsr_check_search("vrpms_vrp_batch_lsr", objective, S, rounds);
-  if (rs) return rs;
-  if (R == 0) return VRPMS_OK;
-  if (!d_mats || !d_demand || !d_cap || !d_start || !d_tours || !d_keys || !d_durs || !d_veh || !d_info)
-    return fail(VRPMS_EINVAL,
-                "vrpms_vrp_batch_lsr: NULL matrix/demand/capacity/start/tour/key/duration/vehicle/info buffer");
-  const size_t lds = batch_lsr_lds(N, K, H, wide).total;
-  if (lds > ctx->max_lds)
-    return batch_lsr_lds_refusal("vrpms_vrp_batch_lsr", N, K, H, wide, lds, ctx->max_lds);
-  VRPMS_HIP(hipSetDevice(ctx->device));
-  const VrpBatchLsrArgs a{d_mats, d_demand, d_cap,  d_start, R,      N,      K,      H,     objective,
-                          S,      rounds,   (uint32_t)seed, (uint32_t)(seed >> 32), d_tours, d_keys,
-                          d_durs, d_veh,    d_info};
-  void (*kernel)(VrpBatchLsrArgs) =
-      wide ? (H == 24 ? vrp_batch_lsr_kernel<int32_t, 24> : vrp_batch_lsr_kernel<int32_t, 1>)
-           : (H == 24 ? vrp_batch_lsr_kernel<uint16_t, 24> : vrp_batch_lsr_kernel<uint16_t, 1>);
-  if (lds > 65536)
-    VRPMS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  kernel<<<(unsigned)R, 256, lds, (hipStream_t)stream>>>(a);
-  VRPMS_HIP(hipGetLastError());
-  return VRPMS_OK;
+  const char* who = "vrpms_vrp_batch_lsr";
+  if (const int rc = batch_check_ctx(who, ctx, R)) return rc;
+  if (const int rc = batch_lsr_check(who, N, K, H, wide)) return rc;
+  const VrpBatchLsArgs a{d_mats, d_demand, d_cap,  d_start, R,      N,      K,      H,     objective,
+                         S,      rounds,   (uint32_t)seed, (uint32_t)(seed >> 32), d_tours, d_keys,
+                         d_durs, d_veh,    d_info};
+  return batch_ls_launch(who, ctx, a, wide, N - 1 + K - 1, stream, [](auto m, auto hm) {
+    return vrp_batch_lsr_kernel<decltype(m), decltype(hm)::value>;
+  });
 }

@@ -1,90 +1,60 @@
-// What the two mappings of the local search over separator tours share (spec
-// A26: vrp_batch_lsr.hip, one workgroup per request; vrp_batch_lsr_spread.hip,
-// G workgroups per request): the launch's arguments, its shape checks, the LDS
-// carve of the instance and the first-fit start.
+// What the VRP local searches share on top of batch_ls.hpp's descent:
+// vrp_batch_ls.hip (A25, tours of n customers) and vrp_batch_lsr.hip (A26, tours
+// of L = n + K - 1 tokens with separators) have one argument struct, one LDS
+// size and one host tail behind their shape checks; vrp_batch_lsr_spread.hip
+// (A26 with G workgroups per request) takes the arguments, the checks and the
+// first-fit start.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <string>
 
+#include "batch_launch.hpp"
 #include "batch_ls.hpp"
+#include "batch_stage.hpp"
 #include "common.hpp"
 #include "ctx.hpp"
+#include "staging.hpp"
 #include "tour.hpp"
 
 namespace vrpms {
 
-constexpr int kBatchLsrMaxK = 64;      // one lane per route in the first-fit start
-constexpr int kBatchLsrMaxN = 65535;   // tokens are uint16
-constexpr int kBatchLsrMaxL = 65535;   // positions too
-constexpr int kBatchLsrMaxS = 65535;
-
-struct VrpBatchLsrArgs {
+struct VrpBatchLsArgs {
   const int32_t* mats;    // [R][H][N][N]
   const int32_t* demand;  // [R][N]
   const int32_t* cap;     // [R][K]
   const int32_t* start;   // [R][K]
   int R, N, K, H, objective, S, rounds;
   uint32_t seed_lo, seed_hi;
-  uint16_t* tours;        // [R][L]
+  uint16_t* tours;        // [R][L]; L = n for vrp_batch_ls
   uint64_t* keys;         // [R]
   int32_t* durs;          // [R][K]
   int8_t* veh;            // [R][L]
   int32_t* info;          // [R][2]: the answer's start, the capped descents
 };
 
-struct BatchLsrLds {
-  size_t mat, dem, row, tour, total;   // bytes of the matrix, the demand row, one K row, one tour
-};
-
-inline BatchLsrLds batch_lsr_lds(int N, int K, int H, int wide) {
-  BatchLsrLds l;
-  l.mat = ((size_t)H * N * N * (wide ? 4 : 2) + 15) & ~(size_t)15;
-  l.dem = (((size_t)N + 3) & ~(size_t)3) * 4;
-  l.row = (((size_t)K + 3) & ~(size_t)3) * 4;
-  l.tour = (((size_t)N - 1 + K - 1 + 7) & ~(size_t)7) * 2;
-  l.total = l.mat + l.dem + 2 * l.row + 4 * 2 * l.tour + 4 * 16;
-  return l;
+// vrp_batch_ls (L = n) and vrp_batch_lsr (L = n + K - 1): behind the instance 4
+// waves x (current, best end) uint16 tours of align8(L), then [4] BatchLsWave
+inline size_t batch_ls_lds(int N, int K, int H, int wide, int L) {
+  return batch_inst_bytes(N, K, H, wide) + 4 * 2 * batch_align<size_t>(L, 8) * 2 + 4 * sizeof(BatchLsWave);
 }
 
-// the shape checks every entry point shares; 0 or the refusal's code
+// the shape checks of every lsr entry point: vrp_batch_ls's with the bound on L
+// behind K
 inline int batch_lsr_check(const char* who, int32_t N, int32_t K, int32_t H, int32_t wide) {
-  const std::string w(who);
-  if (N < 2 || N > kBatchLsrMaxN)
-    return fail(VRPMS_EINVAL, w + ": needs 2 <= N <= 65535 (" + std::to_string(N) + " given)");
-  if (K < 1 || K > kBatchLsrMaxK)
-    return fail(VRPMS_EINVAL, w + ": one lane per route needs 1 <= K <= 64 (" + std::to_string(K) + " given)");
-  if (N - 1 + K - 1 > kBatchLsrMaxL)
-    return fail(VRPMS_EINVAL, w + ": positions are uint16: needs N + K - 2 <= 65535 (" +
+  if (const int rc = batch_check_N(who, N)) return rc;
+  if (const int rc = batch_check_K(who, K)) return rc;
+  if (N - 1 + K - 1 > kBatchMaxN)
+    return fail(VRPMS_EINVAL, std::string(who) + ": positions are uint16: needs N + K - 2 <= 65535 (" +
                                   std::to_string(N - 1 + K - 1) + " given)");
-  if (H != 1 && H != 24)
-    return fail(VRPMS_EINVAL, w + ": H must be 1 or 24 (" + std::to_string(H) + " given)");
-  if (wide != 0 && wide != 1)
-    return fail(VRPMS_EINVAL, w + ": wide must be 0 (uint16 matrix) or 1 (int32) (" + std::to_string(wide) +
-                                  " given)");
-  return VRPMS_OK;
+  return batch_check_matrix(who, H, wide);
 }
 
-// the checks of the search's own arguments; 0 or the refusal's code
-inline int batch_lsr_check_search(const char* who, int32_t objective, int32_t S, int32_t rounds) {
-  const std::string w(who);
-  if (objective != VRPMS_OBJ_SUM && objective != VRPMS_OBJ_MAX)
-    return fail(VRPMS_EINVAL, w + ": objective must be VRPMS_OBJ_SUM or VRPMS_OBJ_MAX");
-  if (S < 1 || S > kBatchLsrMaxS)
-    return fail(VRPMS_EINVAL, w + ": 1 <= S <= 65535 (" + std::to_string(S) + " given)");
-  if (rounds < 0)
-    return fail(VRPMS_EINVAL, w + ": rounds must not be negative (" + std::to_string(rounds) + " given)");
-  return VRPMS_OK;
-}
-
-// the refusal of a launch whose request does not fit the device's LDS
-inline int batch_lsr_lds_refusal(const char* who, int32_t N, int32_t K, int32_t H, int32_t wide,
-                                 size_t lds, size_t have) {
-  return fail(VRPMS_EINVAL, std::string(who) + ": a request of N = " + std::to_string(N) + ", K = " +
-                                std::to_string(K) + ", H = " + std::to_string(H) +
-                                (wide ? " (int32 matrix)" : " (uint16 matrix)") + " needs " +
-                                std::to_string(lds) + " bytes of LDS (" + std::to_string(have) +
-                                " available)");
+// the checks of a local search's own arguments
+inline int batch_ls_check_search(const char* who, int32_t objective, int32_t S, int32_t rounds) {
+  if (const int rc = batch_check_objective(who, objective)) return rc;
+  if (const int rc = batch_check_count(who, "S", S, kBatchMaxS)) return rc;
+  return batch_check_rounds(who, rounds);
 }
 
 // One wavefront builds start s in A (L = n + K - 1 tokens): K - 1 separators
@@ -110,6 +80,29 @@ VRPMS_DEV void batch_lsr_start(uint16_t* A, const int32_t* dem, const int32_t* c
     if (lane >= b) ++end;
     if (pos < at) batch_ls_apply(A, Move{kMoveRelocate, at, pos}, lane);
   }
+}
+
+// What the entry points vrpms_vrp_batch_ls (SEP = false) and vrpms_vrp_batch_lsr
+// (SEP = true) do behind their shape check; `kernel` picks the instantiation
+// of the one's or the other's __global__ wrapper.
+template <class Kernel>
+int batch_ls_launch(const char* who, vrpms_ctx* ctx, const VrpBatchLsArgs& a, int wide, int L, void* stream,
+                    Kernel&& kernel) {
+  if (const int rc = batch_ls_check_search(who, a.objective, a.S, a.rounds)) return rc;
+  if (a.R == 0) return VRPMS_OK;
+  if (const int rc = batch_check_buffers(
+          who, "matrix/demand/capacity/start/tour/key/duration/vehicle/info",
+          {a.mats, a.demand, a.cap, a.start, a.tours, a.keys, a.durs, a.veh, a.info}))
+    return rc;
+  const size_t lds = batch_ls_lds(a.N, a.K, a.H, wide, L);
+  if (lds > ctx->max_lds) return batch_lds_refusal(who, a.N, a.K, a.H, wide, "", lds, ctx->max_lds);
+  VRPMS_HIP(hipSetDevice(ctx->device));
+  const char* what = "";
+  const hipError_t e = batch_with_matrix(wide, a.H, [&](auto m, auto hm) {
+    return batch_launch_blocks(kernel(m, hm), a, (unsigned)a.R, lds, (hipStream_t)stream, &what);
+  });
+  if (e != hipSuccess) return hip_fail(e, what);
+  return VRPMS_OK;
 }
 
 }  // namespace vrpms

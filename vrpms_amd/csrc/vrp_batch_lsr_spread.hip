@@ -46,32 +46,25 @@
 
 #include <string>
 
-#include "batch_ls.hpp"
-#include "batch_stage.hpp"
-#include "common.hpp"
-#include "ctx.hpp"
-#include "staging.hpp"
-#include "tour.hpp"
 #include "vrp_batch_lsr.hpp"
 
 namespace vrpms {
 
-constexpr int kBatchLsrMaxG = 65535;
-
 struct VrpBatchLsrSpreadArgs {
-  VrpBatchLsrArgs a;
+  VrpBatchLsArgs a;
   int G;                  // workgroups per request, 1 <= G <= S
   unsigned char* work;    // [R][G] records of rec_bytes
   uint32_t rec_bytes;     // 16 + 2 align8(L)
 };
 
+// behind the instance: the 4 wavefronts' copies of the tour, then [2][4] BatchLsRec
 inline size_t batch_lsr_spread_lds(int N, int K, int H, int wide) {
-  const BatchLsrLds l = batch_lsr_lds(N, K, H, wide);
-  return l.mat + l.dem + 2 * l.row + 4 * l.tour + 2 * 4 * sizeof(BatchLsRec);
+  return batch_inst_bytes(N, K, H, wide) + 4 * batch_align<size_t>((size_t)N - 1 + K - 1, 8) * 2 +
+         2 * 4 * sizeof(BatchLsRec);
 }
 
 inline uint64_t batch_lsr_spread_rec_bytes(int N, int K) {
-  return 16 + 2 * (((uint64_t)N - 1 + K - 1 + 7) & ~(uint64_t)7);
+  return 16 + 2 * batch_align<uint64_t>((uint64_t)N - 1 + K - 1, 8);
 }
 
 // the LDS carve both kernels share
@@ -99,7 +92,7 @@ struct BatchLsrSpreadCarve {
 template <typename MatT, int HM>
 __global__ __launch_bounds__(256) void vrp_batch_lsr_spread_kernel(VrpBatchLsrSpreadArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char batch_lsr_spread_lds_mem[];
-  const VrpBatchLsrArgs& a = p.a;
+  const VrpBatchLsArgs& a = p.a;
   const int N = a.N, n = N - 1, K = a.K, L = n + K - 1, G = p.G;
   const int64_t r = blockIdx.x / (uint32_t)G;
   const int g = (int)(blockIdx.x % (uint32_t)G);
@@ -140,7 +133,7 @@ __global__ __launch_bounds__(256) void vrp_batch_lsr_spread_kernel(VrpBatchLsrSp
 template <typename MatT, int HM>
 __global__ __launch_bounds__(256) void vrp_batch_lsr_select_kernel(VrpBatchLsrSpreadArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char batch_lsr_select_lds_mem[];
-  const VrpBatchLsrArgs& a = p.a;
+  const VrpBatchLsArgs& a = p.a;
   const int N = a.N, n = N - 1, K = a.K, L = n + K - 1, G = p.G;
   const int64_t r = blockIdx.x;
   const BatchLsrSpreadCarve<MatT, HM> c(batch_lsr_select_lds_mem, N, K, L);
@@ -208,27 +201,20 @@ using namespace vrpms;
 
 extern "C" int vrpms_vrp_batch_lsr_spread_lds(int32_t N, int32_t K, int32_t H, int32_t wide,
                                               uint64_t* bytes) {
-  if (!bytes) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_lsr_spread_lds: bytes is NULL");
-  const int rc = batch_lsr_check("vrpms_vrp_batch_lsr_spread_lds", N, K, H, wide);
-  if (rc) return rc;
+  const char* who = "vrpms_vrp_batch_lsr_spread_lds";
+  if (const int rc = batch_check_bytes(who, bytes)) return rc;
+  if (const int rc = batch_lsr_check(who, N, K, H, wide)) return rc;
   *bytes = batch_lsr_spread_lds(N, K, H, wide);
   return VRPMS_OK;
 }
 
 extern "C" int vrpms_vrp_batch_lsr_spread_work(int32_t R, int32_t N, int32_t K, int32_t G,
                                                uint64_t* bytes) {
-  if (!bytes) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_lsr_spread_work: bytes is NULL");
-  if (R < 0) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_lsr_spread_work: R must not be negative");
-  const int rc = batch_lsr_check("vrpms_vrp_batch_lsr_spread_work", N, K, 1, 0);
-  if (rc) return rc;
-  if (G < 1 || G > kBatchLsrMaxG)
-    return fail(VRPMS_EINVAL,
-                "vrpms_vrp_batch_lsr_spread_work: 1 <= G <= 65535 (" + std::to_string(G) + " given)");
-  if ((uint64_t)R * (uint64_t)G > 0x7fffffffull)
-    return fail(VRPMS_EINVAL, "vrpms_vrp_batch_lsr_spread_work: R * G = " +
-                                  std::to_string((uint64_t)R * (uint64_t)G) + " records are above 2^31 - 1");
-  *bytes = (uint64_t)R * (uint64_t)G * batch_lsr_spread_rec_bytes(N, K);   // < 2^31 2^18
-  return VRPMS_OK;
+  const char* who = "vrpms_vrp_batch_lsr_spread_work";
+  if (const int rc = batch_check_bytes(who, bytes)) return rc;
+  if (const int rc = batch_check_R(who, R)) return rc;
+  if (const int rc = batch_lsr_check(who, N, K, 1, 0)) return rc;
+  return batch_work_bytes(who, R, G, batch_lsr_spread_rec_bytes(N, K), bytes);
 }
 
 extern "C" int vrpms_vrp_batch_lsr_spread(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_demand,
@@ -239,52 +225,36 @@ extern "C" int vrpms_vrp_batch_lsr_spread(vrpms_ctx* ctx, const int32_t* d_mats,
                                           uint16_t* d_tours, uint64_t* d_keys, int32_t* d_durs,
                                           int8_t* d_veh, int32_t* d_info, void* stream) {
   const char* who = "vrpms_vrp_batch_lsr_spread";
-  const std::string w(who);
-  if (!ctx) return fail(VRPMS_EINVAL, w + ": ctx is NULL");
-  if (R < 0) return fail(VRPMS_EINVAL, w + ": R must not be negative");
-  const int rc = batch_lsr_check(who, N, K, H, wide);
-  if (rc) return rc;
-  const int rs = batch_lsr_check_search(who, objective, S, rounds);
-  if (rs) return rs;
-  if (G < 1 || G > kBatchLsrMaxG)
-    return fail(VRPMS_EINVAL, w + ": 1 <= G <= 65535 (" + std::to_string(G) + " given)");
+  if (const int rc = batch_check_ctx(who, ctx, R)) return rc;
+  if (const int rc = batch_lsr_check(who, N, K, H, wide)) return rc;
+  if (const int rc = batch_ls_check_search(who, objective, S, rounds)) return rc;
+  if (const int rc = batch_check_count(who, "G", G, kBatchMaxG)) return rc;
   if (R == 0) return VRPMS_OK;
-  if (!d_mats || !d_demand || !d_cap || !d_start || !d_tours || !d_keys || !d_durs || !d_veh || !d_info)
-    return fail(VRPMS_EINVAL,
-                w + ": NULL matrix/demand/capacity/start/tour/key/duration/vehicle/info buffer");
+  if (const int rc = batch_check_buffers(
+          who, "matrix/demand/capacity/start/tour/key/duration/vehicle/info",
+          {d_mats, d_demand, d_cap, d_start, d_tours, d_keys, d_durs, d_veh, d_info}))
+    return rc;
   const int Gc = G < S ? G : S;   // a workgroup without a start cannot occur
-  if ((uint64_t)R * (uint64_t)Gc > 0x7fffffffull)
-    return fail(VRPMS_EINVAL, w + ": R * min(G, S) = " + std::to_string((uint64_t)R * (uint64_t)Gc) +
-                                  " workgroups are above 2^31 - 1");
-  const uint64_t rec = batch_lsr_spread_rec_bytes(N, K), need = (uint64_t)R * (uint64_t)Gc * rec;
-  if (!d_work) return fail(VRPMS_EINVAL, w + ": the workspace is NULL");
-  if ((uintptr_t)d_work & 7u) return fail(VRPMS_EINVAL, w + ": the workspace must be 8-byte aligned");
-  if (work_bytes < need)
-    return fail(VRPMS_EINVAL, w + ": the workspace has " + std::to_string(work_bytes) + " bytes, R = " +
-                                  std::to_string(R) + " requests of min(G, S) = " + std::to_string(Gc) +
-                                  " workgroups need " + std::to_string(need));
+  const uint64_t rec = batch_lsr_spread_rec_bytes(N, K);
+  if (const int rc = batch_check_work(who, R, Gc, rec, d_work, work_bytes)) return rc;
   const size_t lds = batch_lsr_spread_lds(N, K, H, wide);
-  if (lds > ctx->max_lds) return batch_lsr_lds_refusal(who, N, K, H, wide, lds, ctx->max_lds);
+  if (lds > ctx->max_lds) return batch_lds_refusal(who, N, K, H, wide, "", lds, ctx->max_lds);
   VRPMS_HIP(hipSetDevice(ctx->device));
   const VrpBatchLsrSpreadArgs p{
-      VrpBatchLsrArgs{d_mats, d_demand, d_cap, d_start, R, N, K, H, objective, S, rounds, (uint32_t)seed,
-                      (uint32_t)(seed >> 32), d_tours, d_keys, d_durs, d_veh, d_info},
+      VrpBatchLsArgs{d_mats, d_demand, d_cap, d_start, R, N, K, H, objective, S, rounds, (uint32_t)seed,
+                     (uint32_t)(seed >> 32), d_tours, d_keys, d_durs, d_veh, d_info},
       Gc, static_cast<unsigned char*>(d_work), (uint32_t)rec};
-  void (*descend)(VrpBatchLsrSpreadArgs) =
-      wide ? (H == 24 ? vrp_batch_lsr_spread_kernel<int32_t, 24> : vrp_batch_lsr_spread_kernel<int32_t, 1>)
-           : (H == 24 ? vrp_batch_lsr_spread_kernel<uint16_t, 24> : vrp_batch_lsr_spread_kernel<uint16_t, 1>);
-  void (*select)(VrpBatchLsrSpreadArgs) =
-      wide ? (H == 24 ? vrp_batch_lsr_select_kernel<int32_t, 24> : vrp_batch_lsr_select_kernel<int32_t, 1>)
-           : (H == 24 ? vrp_batch_lsr_select_kernel<uint16_t, 24> : vrp_batch_lsr_select_kernel<uint16_t, 1>);
-  if (lds > 65536) {
-    VRPMS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(descend),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    VRPMS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(select),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  descend<<<(unsigned)((uint64_t)R * (uint64_t)Gc), 256, lds, (hipStream_t)stream>>>(p);
-  VRPMS_HIP(hipGetLastError());
-  select<<<(unsigned)R, 256, lds, (hipStream_t)stream>>>(p);
-  VRPMS_HIP(hipGetLastError());
+  const hipStream_t s = (hipStream_t)stream;
+  const char* what = "";
+  const hipError_t e = batch_with_matrix(wide, H, [&](auto m, auto hm) {
+    const auto descend = vrp_batch_lsr_spread_kernel<decltype(m), decltype(hm)::value>;
+    const auto select = vrp_batch_lsr_select_kernel<decltype(m), decltype(hm)::value>;
+    hipError_t x = batch_raise_lds(descend, lds, &what);   // both limits before either launch
+    if (x == hipSuccess) x = batch_raise_lds(select, lds, &what);
+    if (x == hipSuccess) x = batch_enqueue(descend, p, (unsigned)((uint64_t)R * (uint64_t)Gc), lds, s, &what);
+    if (x == hipSuccess) x = batch_enqueue(select, p, (unsigned)R, lds, s, &what);
+    return x;
+  });
+  if (e != hipSuccess) return hip_fail(e, what);
   return VRPMS_OK;
 }

@@ -32,6 +32,7 @@
 
 #include <string>
 
+#include "batch_launch.hpp"
 #include "batch_stage.hpp"
 #include "common.hpp"
 #include "ctx.hpp"
@@ -39,9 +40,6 @@
 #include "tour.hpp"
 
 namespace vrpms {
-
-constexpr int kBatchSaMaxK = 64;      // one lane per route in the first-fit start
-constexpr int kBatchSaMaxN = 65535;   // tokens are uint16
 
 struct VrpBatchSaArgs {
   const int32_t* mats;    // [R][H][N][N]
@@ -58,18 +56,17 @@ struct VrpBatchSaArgs {
   int8_t* veh;            // [R][ntok]
 };
 
-struct BatchSaLds {
-  size_t mat, dem, row, tour, total;   // bytes of the matrix, the demand row, one K row, one tour
+// the kernel's own parts behind the instance, in their order
+template <typename I>
+struct BatchSaParts {
+  I tpad;   // a tour's padded tokens
+  __host__ __device__ explicit BatchSaParts(I ntok) : tpad(batch_align<I>(ntok, 8)) {}
+  __host__ __device__ I tour_tokens() const { return 4 * 3 * tpad; }   // 4 chains x (current, scratch, best), uint16
+  __host__ __device__ I bytes() const { return 2 * tour_tokens() + 4 * 8; }   // then the chains' best keys, uint64
 };
 
-inline BatchSaLds batch_sa_lds(int N, int K, int H, int wide) {
-  BatchSaLds l;
-  l.mat = ((size_t)H * N * N * (wide ? 4 : 2) + 15) & ~(size_t)15;
-  l.dem = (((size_t)N + 3) & ~(size_t)3) * 4;
-  l.row = (((size_t)K + 3) & ~(size_t)3) * 4;
-  l.tour = (((size_t)N - 1 + K - 1 + 7) & ~(size_t)7) * 2;
-  l.total = l.mat + l.dem + 2 * l.row + 4 * 3 * l.tour + 4 * 8;
-  return l;
+inline size_t batch_sa_lds(int N, int K, int H, int wide) {
+  return batch_inst_bytes(N, K, H, wide) + BatchSaParts<size_t>((size_t)N - 1 + K - 1).bytes();
 }
 
 template <typename MatT, int HM>
@@ -77,16 +74,14 @@ __global__ __launch_bounds__(256) void vrp_batch_sa_kernel(VrpBatchSaArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char batch_sa_lds_mem[];
   const int N = a.N, n = N - 1, K = a.K, ntok = n + K - 1;
   const int64_t r = blockIdx.x;
-  const uint32_t cells = (uint32_t)HM * (uint32_t)N * (uint32_t)N;
-  const uint32_t mat_bytes = (cells * (uint32_t)sizeof(MatT) + 15u) & ~15u;
-  const uint32_t dem_words = ((uint32_t)N + 3u) & ~3u, row_words = ((uint32_t)K + 3u) & ~3u;
-  const uint32_t tpad = ((uint32_t)ntok + 7u) & ~7u;
-  MatT* M = reinterpret_cast<MatT*>(batch_sa_lds_mem);
-  int32_t* dem = reinterpret_cast<int32_t*>(batch_sa_lds_mem + mat_bytes);
-  int32_t* cap = dem + dem_words;
-  int32_t* start = cap + row_words;
-  uint16_t* tours = reinterpret_cast<uint16_t*>(start + row_words);
-  uint64_t* wbest = reinterpret_cast<uint64_t*>(tours + 4 * 3 * tpad);
+  const auto ip = BatchInst<MatT, HM>::parts(N, K);
+  const BatchSaParts<uint32_t> l((uint32_t)ntok);
+  const BatchInst<MatT, HM> c(batch_sa_lds_mem, ip, N, K);
+  const uint32_t cells = c.cells, tpad = l.tpad;
+  MatT* M = c.M;
+  int32_t *dem = c.dem, *cap = c.cap, *start = c.start;
+  uint16_t* tours = reinterpret_cast<uint16_t*>(c.rest);
+  uint64_t* wbest = reinterpret_cast<uint64_t*>(tours + l.tour_tokens());
 
   // stage and check the request (batch_stage.hpp); the verdict goes through
   // a word of wbest, free until the chains end
@@ -239,30 +234,15 @@ __global__ __launch_bounds__(256) void vrp_batch_sa_kernel(VrpBatchSaArgs a) {
   if (lane == 0) a.keys[r] = bk;
 }
 
-// the shape checks both entry points share; 0 or the refusal's code
-static int batch_sa_check(const char* who, int32_t N, int32_t K, int32_t H, int32_t wide) {
-  const std::string w(who);
-  if (N < 2 || N > kBatchSaMaxN)
-    return fail(VRPMS_EINVAL, w + ": needs 2 <= N <= 65535 (" + std::to_string(N) + " given)");
-  if (K < 1 || K > kBatchSaMaxK)
-    return fail(VRPMS_EINVAL, w + ": one lane per route needs 1 <= K <= 64 (" + std::to_string(K) + " given)");
-  if (H != 1 && H != 24)
-    return fail(VRPMS_EINVAL, w + ": H must be 1 or 24 (" + std::to_string(H) + " given)");
-  if (wide != 0 && wide != 1)
-    return fail(VRPMS_EINVAL, w + ": wide must be 0 (uint16 matrix) or 1 (int32) (" + std::to_string(wide) +
-                                  " given)");
-  return VRPMS_OK;
-}
-
 }  // namespace vrpms
 
 using namespace vrpms;
 
 extern "C" int vrpms_vrp_batch_sa_lds(int32_t N, int32_t K, int32_t H, int32_t wide, uint64_t* bytes) {
-  if (!bytes) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_sa_lds: bytes is NULL");
-  const int rc = batch_sa_check("vrpms_vrp_batch_sa_lds", N, K, H, wide);
-  if (rc) return rc;
-  *bytes = batch_sa_lds(N, K, H, wide).total;
+  const char* who = "vrpms_vrp_batch_sa_lds";
+  if (const int rc = batch_check_bytes(who, bytes)) return rc;
+  if (const int rc = batch_check_shape(who, N, K, H, wide)) return rc;
+  *bytes = batch_sa_lds(N, K, H, wide);
   return VRPMS_OK;
 }
 
@@ -272,35 +252,27 @@ extern "C" int vrpms_vrp_batch_sa(vrpms_ctx* ctx, const int32_t* d_mats, const i
                                   int32_t wide, int32_t steps, float inv_alpha, uint64_t seed,
                                   uint16_t* d_tours, uint64_t* d_keys, int32_t* d_durs, int8_t* d_veh,
                                   void* stream) {
-  if (!ctx) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_sa: ctx is NULL");
-  if (R < 0) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_sa: R must not be negative");
-  const int rc = batch_sa_check("vrpms_vrp_batch_sa", N, K, H, wide);
-  if (rc) return rc;
-  if (objective != VRPMS_OBJ_SUM && objective != VRPMS_OBJ_MAX)
-    return fail(VRPMS_EINVAL, "vrpms_vrp_batch_sa: objective must be VRPMS_OBJ_SUM or VRPMS_OBJ_MAX");
+  const char* who = "vrpms_vrp_batch_sa";
+  if (const int rc = batch_check_ctx(who, ctx, R)) return rc;
+  if (const int rc = batch_check_shape(who, N, K, H, wide)) return rc;
+  if (const int rc = batch_check_objective(who, objective)) return rc;
   if (steps < 0) return fail(VRPMS_EINVAL, "vrpms_vrp_batch_sa: steps must not be negative");
   if (R == 0) return VRPMS_OK;
-  if (!d_mats || !d_demand || !d_cap || !d_start || !d_inv_t0 || !d_tours || !d_keys || !d_durs || !d_veh)
-    return fail(VRPMS_EINVAL,
-                "vrpms_vrp_batch_sa: NULL matrix/demand/capacity/start/inv_t0/tour/key/duration/vehicle buffer");
-  const size_t lds = batch_sa_lds(N, K, H, wide).total;
-  if (lds > ctx->max_lds)
-    return fail(VRPMS_EINVAL, "vrpms_vrp_batch_sa: a request of N = " + std::to_string(N) + ", K = " +
-                                  std::to_string(K) + ", H = " + std::to_string(H) +
-                                  (wide ? " (int32 matrix)" : " (uint16 matrix)") + " needs " +
-                                  std::to_string(lds) + " bytes of LDS (" + std::to_string(ctx->max_lds) +
-                                  " available)");
+  if (const int rc = batch_check_buffers(
+          who, "matrix/demand/capacity/start/inv_t0/tour/key/duration/vehicle",
+          {d_mats, d_demand, d_cap, d_start, d_inv_t0, d_tours, d_keys, d_durs, d_veh}))
+    return rc;
+  const size_t lds = batch_sa_lds(N, K, H, wide);
+  if (lds > ctx->max_lds) return batch_lds_refusal(who, N, K, H, wide, "", lds, ctx->max_lds);
   VRPMS_HIP(hipSetDevice(ctx->device));
   const VrpBatchSaArgs a{d_mats, d_demand, d_cap,  d_start, d_inv_t0, R,      N,      K,
                          H,      objective, steps, inv_alpha, (uint32_t)seed, (uint32_t)(seed >> 32),
                          d_tours, d_keys, d_durs, d_veh};
-  void (*kernel)(VrpBatchSaArgs) =
-      wide ? (H == 24 ? vrp_batch_sa_kernel<int32_t, 24> : vrp_batch_sa_kernel<int32_t, 1>)
-           : (H == 24 ? vrp_batch_sa_kernel<uint16_t, 24> : vrp_batch_sa_kernel<uint16_t, 1>);
-  if (lds > 65536)
-    VRPMS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  kernel<<<(unsigned)R, 256, lds, (hipStream_t)stream>>>(a);
-  VRPMS_HIP(hipGetLastError());
+  const char* what = "";
+  const hipError_t e = batch_with_matrix(wide, H, [&](auto m, auto hm) {
+    return batch_launch_blocks(vrp_batch_sa_kernel<decltype(m), decltype(hm)::value>, a, (unsigned)R, lds,
+                               (hipStream_t)stream, &what);
+  });
+  if (e != hipSuccess) return hip_fail(e, what);
   return VRPMS_OK;
 }
