@@ -774,6 +774,32 @@ int vrpms_vrp_batch_lsr(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_
                         int32_t rounds, uint64_t seed, uint16_t* d_tours, uint64_t* d_keys,
                         int32_t* d_durs, int8_t* d_veh, int32_t* d_info, void* stream);
 
+/* Batched VRP local search over PLAIN separator tours on a static matrix, with
+ * delta pricing (spec A28): vrpms_vrp_batch_lsr's requests,
+ * buffers, arguments, mapping, starts, moves, answer and refusal row, with H
+ * kept in the argument list and required to be 1 (an hour-indexed launch keeps
+ * vrpms_vrp_batch_lsr).  A tour of n customers and K - 1 separators is plain
+ * when the customers between separator g - 1 and separator g weigh at most
+ * cap[g] for every g = 0..K-1, so that the separators alone decide the routes.
+ * A round considers vrpms_vrp_batch_lsr's moves in its order, but a move whose
+ * moved tour is not plain is no candidate; the rest are priced by their A8 key
+ * -- from per-wavefront prefix rows, never by a walk -- and the least (key,
+ * typ, i, j) is applied while it is below the tour's key.  A start that is not
+ * plain (the first fit found no room for a customer) does not descend: its end
+ * tour is its start tour with its A8 key, and it is never capped.  With every
+ * capacity at least the total demand every tour is plain and the rows are
+ * vrpms_vrp_batch_lsr's bit for bit; with K = 1 and such a capacity they are
+ * vrpms_vrp_batch_ls's.  vrpms_vrp_batch_lsf_lds gives the launch's
+ * dynamic-LDS bytes for (N, K, wide) (host only, no context); a launch that
+ * needs more than the device has is refused with that byte count.
+ * VRPMS_EINVAL as for vrpms_vrp_batch_lsr, and for H other than 1. */
+int vrpms_vrp_batch_lsf_lds(int32_t N, int32_t K, int32_t wide, uint64_t* bytes);
+int vrpms_vrp_batch_lsf(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_demand,
+                        const int32_t* d_cap, const int32_t* d_start, int32_t R, int32_t N,
+                        int32_t K, int32_t H, int32_t objective, int32_t wide, int32_t S,
+                        int32_t rounds, uint64_t seed, uint16_t* d_tours, uint64_t* d_keys,
+                        int32_t* d_durs, int8_t* d_veh, int32_t* d_info, void* stream);
+
 /* vrpms_vrp_batch_lsr by another mapping: the same requests,
  * buffers and arguments, and per request the identical d_tours, d_keys, d_durs,
  * d_veh and d_info rows, refusal rows included -- A26 fixes the starts, the

@@ -131,6 +131,9 @@ SIGNATURES = {
     "vrpms_vrp_batch_lsr_lds": (_c.c_int, [_i32, _i32, _i32, _i32, _c.POINTER(_u64)]),
     "vrpms_vrp_batch_lsr": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
                                        _i32, _i32, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vrpms_vrp_batch_lsf_lds": (_c.c_int, [_i32, _i32, _i32, _c.POINTER(_u64)]),
+    "vrpms_vrp_batch_lsf": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
+                                       _i32, _i32, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vrpms_vrp_batch_lsr_spread_lds": (_c.c_int, [_i32, _i32, _i32, _i32, _c.POINTER(_u64)]),
     "vrpms_vrp_batch_lsr_spread_work": (_c.c_int, [_i32, _i32, _i32, _i32, _c.POINTER(_u64)]),
     "vrpms_vrp_batch_lsr_spread": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32,

@@ -140,6 +140,17 @@ def vrp_batch_lsr_lds(N: int, K: int, H: int, wide) -> int:
     return _bytes("vrpms_vrp_batch_lsr_lds", N, K, H, wide)
 
 
+def vrp_batch_lsf_lds(N: int, K: int, H: int, wide) -> int:
+    """vrpms_vrp_batch_lsf_lds: the dynamic-LDS bytes of a vrp_batch_lsf launch
+    for N nodes, K vehicles and a uint16 (`wide` false) or int32 (`wide` true)
+    static matrix.  H is taken so that the call reads like the other _lds
+    functions and must be 1.  Host only: needs the library, no GPU."""
+    if int(H) != 1:
+        raise ValueError(f"vrp_batch_lsf_lds: H must be 1 ({H} given): an hour-indexed matrix "
+                         "keeps vrp_batch_lsr")
+    return _bytes("vrpms_vrp_batch_lsf_lds", N, K, wide)
+
+
 def vrp_batch_lsr_spread_lds(N: int, K: int, H: int, wide) -> int:
     """vrpms_vrp_batch_lsr_spread_lds: the dynamic-LDS bytes of either launch
     of vrp_batch_lsr_spread for N nodes, K vehicles, H hour slices (1 or 24)
@@ -964,6 +975,25 @@ class Context:
         mats, R, H, N, K, wide = self._vrp_batch_args(mats, demand, caps, starts, wide)
         out = self._batch_out(R, N - 1 + K - 1, K, info=True)
         check(self.lib.vrpms_vrp_batch_lsr(
+            self._ctx, mats.data_ptr(), demand.data_ptr(), caps.data_ptr(), starts.data_ptr(), R, N,
+            K, H, int(objective), int(bool(wide)), int(nstarts), int(rounds), _u64(seed),
+            *(t.data_ptr() for t in out), self.stream()))
+        return out
+
+    def vrp_batch_lsf(self, mats, demand, caps, starts, objective: int, nstarts: int, rounds: int,
+                      seed: int, wide=None):
+        """vrp_batch_lsr on the plain separator tours of a static matrix, with
+        delta pricing (spec A28): the same arguments (H = 1
+        only) and the same five tensors.  A tour is plain when the customers
+        between separator g - 1 and separator g weigh at most caps[g]; a move
+        onto a tour that is not plain is no candidate, and a start that is not
+        plain ends where it starts and is never capped.  With every capacity
+        at least the total demand the tensors are vrp_batch_lsr's bit for bit.
+        An hour-indexed batch is refused: it keeps vrp_batch_lsr.
+        Asynchronous on the current stream."""
+        mats, R, H, N, K, wide = self._vrp_batch_args(mats, demand, caps, starts, wide)
+        out = self._batch_out(R, N - 1 + K - 1, K, info=True)
+        check(self.lib.vrpms_vrp_batch_lsf(
             self._ctx, mats.data_ptr(), demand.data_ptr(), caps.data_ptr(), starts.data_ptr(), R, N,
             K, H, int(objective), int(bool(wide)), int(nstarts), int(rounds), _u64(seed),
             *(t.data_ptr() for t in out), self.stream()))

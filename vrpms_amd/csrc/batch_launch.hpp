@@ -1,7 +1,7 @@
 // Host-side code the batched solvers share.  The exact ones (tsp_batch_dp,
 // vrp_batch_sp, tsp_batch_tdp, vrp_batch_tdsp): a team of T threads owns one
 // request and a 256-thread workgroup holds 256 / T requests.  The heuristic
-// ones (vrp_batch_sa, _ga, _aco, _ls, _lsr, _lsr_spread, tsp_batch_lso,
+// ones (vrp_batch_sa, _ga, _aco, _ls, _lsr, _lsr_spread, _lsf, tsp_batch_lso,
 // _lso_spread): a workgroup owns a request whose instance lives in LDS
 // (batch_stage.hpp has the layout); their argument checks, the LDS refusal,
 // the choice of the kernel's matrix type and the launch are below.
@@ -121,6 +121,15 @@ inline int batch_check_matrix(const char* who, int32_t H, int32_t wide) {
   if (wide != 0 && wide != 1)
     return fail(VRPMS_EINVAL, std::string(who) + ": wide must be 0 (uint16 matrix) or 1 (int32) (" +
                                   std::to_string(wide) + " given)");
+  return VRPMS_OK;
+}
+
+// behind batch_check_matrix, for a solver of static matrices only; `other` is
+// the entry point that takes the hour-indexed ones
+inline int batch_check_static(const char* who, int32_t H, const char* other) {
+  if (H != 1)
+    return fail(VRPMS_EINVAL, std::string(who) + ": H must be 1 (" + std::to_string(H) +
+                                  " given): an hour-indexed matrix keeps " + other);
   return VRPMS_OK;
 }
 

@@ -37,11 +37,11 @@ TITLES = {"bf": "Brute Force", "ga": "Genetic Algorithm", "sa": "Simulated Annea
 # and the exact solvers, "dp" (Held-Karp) for the TSP and "sp" (set
 # partitioning) for the VRP, and "tdp" (time-expanded subset DP, hour-indexed
 # matrices) for the TSP and "tdsp" (its fleet counterpart, per-vehicle start
-# times) for the VRP, and the local searches "ls" / "lsr" (VRP) and "lso" (TSP)
+# times) for the VRP, and the local searches "ls" / "lsr" / "lsf" (VRP) and "lso" (TSP)
 # (they have no /api endpoint: the eight endpoints are the reference's wire
 # contract)
 INLINE_ALGORITHMS = {"tsp": tuple(TITLES) + ("dp", "tdp", "lso"),
-                     "vrp": tuple(TITLES) + ("ls", "lsr", "tdsp", "sp")}
+                     "vrp": tuple(TITLES) + ("ls", "lsr", "lsf", "tdsp", "sp")}
 
 # (body key, params key) in the order the reference checks them
 # (api/parameters.py:4-15 and 34-44); 'auth' is the only optional one
@@ -669,6 +669,46 @@ class VrpLsrBatcher(VrpLsBatcher):
         return tours, list(zip(veh, durs))
 
 
+class VrpLsfBatcher(VrpLsBatcher):
+    """Coalesces concurrent /solve/vrp/lsf requests into one `vrp_batch_lsf`
+    launch per (node count, fleet size, cell width, objective) (spec A28:
+    VrpLsrBatcher's local search restricted to the plain separator tours of a
+    static matrix, priced without walking them).  Every launch descends from
+    `starts` starts for at most `rounds` rounds each, the batcher's own; a
+    request that names either inline takes the unbatched path, and so does an
+    hour-indexed one, which is told there that "lsr" takes it.  A batched
+    answer does not depend on the batch: it is
+    solver.solve_vrp_lsf_batch([request], starts=, rounds=, seed=the app's,
+    objective=)'s, which is also the unbatched route's at the same knobs and
+    seed."""
+
+    def __init__(self, app, window_s: float = 0.005, rounds: int = 1000, starts: int = 64,
+                 max_batch: int = 16384, launch=None):
+        from . import solver
+        if not 1 <= int(starts) <= solver.BATCH_LSF_MAX_STARTS:
+            raise ValueError(f"starts must be in 1..{solver.BATCH_LSF_MAX_STARTS} ({starts} given)")
+        if not 0 <= int(rounds) <= solver.BATCH_LSF_MAX_ROUNDS:
+            raise ValueError(f"rounds must be in 0..{solver.BATCH_LSF_MAX_ROUNDS} "
+                             f"({rounds} given)")
+        super().__init__(app, window_s, rounds, starts, max_batch=max_batch, launch=launch)
+
+    def accepts(self, ci) -> bool:
+        """Requests inside A28's domain (a static matrix, LDS) that pass the
+        int32 guards; anything else takes the unbatched path, which raises the
+        domain's message."""
+        from . import solver
+        return solver.batch_lsf_fits(ci, self.starts, self.rounds) and \
+            solver.batch_guard_message(ci) is None
+
+    def _gpu_launch(self, key, cis, device=None):
+        from . import solver
+        dev = self.devices[0] if device is None else device
+        with self.app.locks[dev]:
+            tours, veh, durs = solver.batch_lsf_launch(solver.context(dev), cis, self.starts,
+                                                       self.rounds, self.app.seed, key[-1])
+        return tours, list(zip(veh, durs))
+
+
 # ---------------------------------------------------------------------------
 # the endpoint logic
 # ---------------------------------------------------------------------------
@@ -700,7 +740,9 @@ class App:
                  batch_ls_starts: int = 64, batch_ls_rounds: int = 1000,
                  batch_vrp_lsr: bool = False, batch_vrp_lsr_launch=None,
                  batch_lsr_starts: int = 64, batch_lsr_rounds: int = 1000,
-                 batch_lsr_spread=None):
+                 batch_lsr_spread=None,
+                 batch_vrp_lsf: bool = False, batch_vrp_lsf_launch=None,
+                 batch_lsf_starts: int = 64, batch_lsf_rounds: int = 1000):
         self.store = store
         self.devices = list(devices) if devices else [device]
         self.device = self.devices[0]
@@ -754,6 +796,10 @@ class App:
                                              batch_lsr_starts, launch=batch_vrp_lsr_launch,
                                              spread=batch_lsr_spread) \
             if batch_vrp_lsr else None
+        # and those over plain separator tours vrp_batch_lsf launches
+        self.vrp_lsf_batcher = VrpLsfBatcher(self, batch_window_s, batch_lsf_rounds,
+                                             batch_lsf_starts, launch=batch_vrp_lsf_launch) \
+            if batch_vrp_lsf else None
 
     def _scheduled(self, problem, algorithm, params, knobs, locations, durations):
         """Run the solve on a device: all of them (in order, as an island
@@ -868,6 +914,20 @@ class App:
                                 params["ignored_customers"], params["completed_customers"])
         return ci if self.vrp_lsr_batcher.accepts(ci) else None
 
+    def _batched_vrp_lsf(self, problem, algorithm, params, knobs, locations, durations):
+        """The compact instance when this request rides the batcher of the
+        local search over plain separator tours, else None: the flag is on,
+        the route is vrp / lsf, the request names no inline knob of its own
+        and it is inside the batcher's domain (outside it the unbatched path
+        raises the domain's message)."""
+        if self.vrp_lsf_batcher is None or (problem, algorithm) != ("vrp", "lsf") or \
+                knobs.get("inline"):
+            return None
+        from . import solver
+        ci = solver.compact_vrp(durations, locations, params["capacities"], params["start_times"],
+                                params["ignored_customers"], params["completed_customers"])
+        return ci if self.vrp_lsf_batcher.accepts(ci) else None
+
     def _batched_vrp(self, problem, algorithm, params, knobs, locations, durations):
         """A thunk that solves this request on the VRP SA, GA, ACO or one of
         the local-search batchers, else None."""
@@ -887,6 +947,9 @@ class App:
         rci = self._batched_vrp_lsr(problem, algorithm, params, knobs, locations, durations)
         if rci is not None:
             return lambda: self.vrp_lsr_batcher.solve(rci, objective)
+        fci = self._batched_vrp_lsf(problem, algorithm, params, knobs, locations, durations)
+        if fci is not None:
+            return lambda: self.vrp_lsf_batcher.solve(fci, objective)
         return None
 
     def _exact_batcher(self, problem, algorithm):
@@ -1263,6 +1326,19 @@ def main(argv=None):
                          "workgroups, 1..1024 (solver.BATCH_LSR_MAX_SPREAD), or over as many as "
                          "keep the device busy (auto: solver.batch_lsr_spread); the answers are "
                          "the same, a window that caught few requests answers sooner")
+    ap.add_argument("--batch-vrp-lsf", action="store_true",
+                    help="coalesce concurrent small-fleet VRP requests of the local search over "
+                         "plain separator tours (/solve/vrp/lsf, static matrix, 1..64 vehicles, an "
+                         "instance that fits the LDS) into vrp_batch_lsf launches of "
+                         "--batch-lsf-starts starts and at most --batch-lsf-rounds rounds a "
+                         "descent; the answer depends on the request alone, not on the batch it "
+                         "rode in")
+    ap.add_argument("--batch-lsf-starts", type=_int_in(1, solver.BATCH_LSF_MAX_STARTS), default=64,
+                    help="starts of a vrp_batch_lsf launch, 1..1024 (solver.BATCH_LSF_MAX_STARTS)")
+    ap.add_argument("--batch-lsf-rounds", type=_int_in(0, solver.BATCH_LSF_MAX_ROUNDS),
+                    default=1000,
+                    help="applied moves a descent of a vrp_batch_lsf launch may take, 0..1000 "
+                         "(solver.BATCH_LSF_MAX_ROUNDS)")
     ap.add_argument("--batch-window-ms", type=float, default=5.0)
     ap.add_argument("--batch-steps", type=int, default=2000)
     ap.add_argument("--workers", type=int, default=0,
@@ -1307,7 +1383,9 @@ def main(argv=None):
               batch_vrp_ls=args.batch_vrp_ls, batch_ls_starts=args.batch_ls_starts,
               batch_ls_rounds=args.batch_ls_rounds,
               batch_vrp_lsr=args.batch_vrp_lsr, batch_lsr_starts=args.batch_lsr_starts,
-              batch_lsr_rounds=args.batch_lsr_rounds, batch_lsr_spread=args.batch_lsr_spread)
+              batch_lsr_rounds=args.batch_lsr_rounds, batch_lsr_spread=args.batch_lsr_spread,
+              batch_vrp_lsf=args.batch_vrp_lsf, batch_lsf_starts=args.batch_lsf_starts,
+              batch_lsf_rounds=args.batch_lsf_rounds)
     srv = serve(app, args.host, args.port)
     print(f"vrpms_amd service on http://{args.host}:{args.port}/api", flush=True)
     try:

@@ -39,7 +39,7 @@ import numpy as np
 from . import core, runners
 from .core import CVRP, OBJ_MAX, OBJ_SUM, TSP, Context
 
-ALGORITHMS = ("bf", "ga", "sa", "aco", "dp", "sp", "tdp", "tdsp", "ls", "lsr", "lso")
+ALGORITHMS = ("bf", "ga", "sa", "aco", "dp", "sp", "tdp", "tdsp", "ls", "lsr", "lso", "lsf")
 # the exact algorithms with kernels of their own: one device, no island model
 # (the exhaustive "bf" shares that with them)
 EXACT_ALGORITHMS = ("dp", "sp", "tdp", "tdsp")
@@ -155,6 +155,16 @@ BATCH_LSR_LDS_BYTES = BATCH_SA_LDS_BYTES
 # A26 by the other mapping (vrp_batch_lsr_spread): the workgroups
 # a request's starts may be spread over; the answers do not depend on it
 BATCH_LSR_MAX_SPREAD = 1024
+# batched VRP multi-start local search over plain separator tours with delta
+# pricing (A28): A26's descent restricted to the tours whose separators alone
+# decide the routes, static matrices only; next to the instance a wavefront
+# keeps two tours, three int32 prefix rows, a segment row and the route tables
+# (vrpms_vrp_batch_lsf_lds gives the bytes for (N, K, wide)); DESIGN.md §4.3v
+# has the largest N per (K, wide).  As for A25, more than BATCH_LSF_MAX_STARTS
+# starts or BATCH_LSF_MAX_ROUNDS rounds is an error, not another path
+BATCH_LSF_MAX_STARTS = 1024
+BATCH_LSF_MAX_ROUNDS = 1000
+BATCH_LSF_LDS_BYTES = BATCH_SA_LDS_BYTES
 # batched TSP multi-start local search with Or-opt and delta pricing (A27): next
 # to the matrix a wavefront keeps two tours and two int32 prefix rows (one on an
 # hour-indexed matrix); vrpms_tsp_batch_lso_lds gives the bytes for (N, H,
@@ -570,6 +580,10 @@ def solve_tsp(algorithm: str, durations, customers, start_node, start_time=0, *,
         raise ValueError('lsr solves the VRP only (a multi-start local search over giant tours '
                          'with route separators); use solve_vrp("lsr") with one vehicle, or sa, '
                          'ga or aco for the TSP')
+    if algorithm == "lsf":
+        raise ValueError('lsf solves the VRP only (a multi-start local search over plain giant '
+                         'tours with route separators); use solve_vrp("lsf") with one vehicle, or '
+                         'lso, sa, ga or aco for the TSP')
     if algorithm == "dp":
         ci = compact_tsp(durations, customers, start_node, start_time)
         _check_dp(ci)
@@ -624,7 +638,13 @@ def solve_vrp(algorithm: str, durations, locations, capacities, start_times,
     a one-request vrp_batch_lsr launch: solve_vrp_lsr_batch's answer for the
     request, its domain batch_lsr_message's.  Its knob `spread` (None, "auto"
     or 1..BATCH_LSR_MAX_SPREAD; batch_lsr_launch) spreads the request's starts
-    over that many workgroups: the same answer, sooner for a lone request."""
+    over that many workgroups: the same answer, sooner for a lone request.
+    "lsf" (spec A28: "lsr" restricted to the plain tours, whose separators
+    alone decide the routes, priced without walking them; static matrices
+    only, the same knobs, limits BATCH_LSF_MAX_STARTS and BATCH_LSF_MAX_ROUNDS,
+    no `spread`) answers with a one-request vrp_batch_lsf launch:
+    solve_vrp_lsf_batch's answer for the request, its domain
+    batch_lsf_message's; an hour-indexed request keeps "lsr"."""
     if algorithm == "dp":
         raise ValueError("dp solves the TSP only (the greedy split of a giant tour does not "
                          "decompose over subsets); use bf, sa, ga or aco for the VRP")
@@ -644,7 +664,7 @@ def solve_vrp(algorithm: str, durations, locations, capacities, start_times,
         ci = compact_vrp(durations, locations, capacities, start_times, ignored_customers,
                          completed_customers)
         _check_tdsp(ci, OBJ_MAX if objective == "max" else OBJ_SUM, knobs.get("upper_bound"))
-    if algorithm in ("ls", "lsr"):
+    if algorithm in ("ls", "lsr", "lsf"):
         if objective not in ("sum", "max"):
             raise ValueError("objective must be 'sum' or 'max'")
         ci = compact_vrp(durations, locations, capacities, start_times, ignored_customers,
@@ -661,7 +681,7 @@ def solve_vrp(algorithm: str, durations, locations, capacities, start_times,
                                            completed_customers)
             out["unvisited"] = [c for c in nodes[1:] if c not in served]
         return out
-    if algorithm in ("ls", "lsr"):   # a one-request launch on one device
+    if algorithm in ("ls", "lsr", "lsf"):   # a one-request launch on one device
         return _solve_single(algorithm, ci, *ls, seed, devices[0] if devices else device, objective,
                              with_unvisited)
     if ci is None:
@@ -1082,7 +1102,7 @@ def solve_vrp_tdsp_batch(requests, *, objective: str = "sum", with_unvisited: bo
 
 
 # ---------------------------------------------------------------------------
-# batched heuristics (A22-A27): one table, one domain, one launch and one loop
+# batched heuristics (A22-A28): one table, one domain, one launch and one loop
 # ---------------------------------------------------------------------------
 @dataclass(frozen=True)
 class Knob:
@@ -1115,6 +1135,8 @@ class HeuristicKind:
     separators: bool = False
     # "<kernel>_spread" takes up to that many workgroups per request; 0: no such form
     max_spread: int = 0
+    # static matrices only: the algorithm that takes the hour-indexed requests
+    static_else: str = ""
     # _check_heuristic applies the int32 guard to a request of no customer
     guard_empty: bool = False
     # (ctx, cis, *the launch's knobs) -> (device buffers after the starts,
@@ -1154,6 +1176,9 @@ HEURISTIC_KINDS = {
     "lsr": HeuristicKind(CVRP, "vrp_batch_lsr", BATCH_LSR_LDS_BYTES,
                          _ls_knobs(BATCH_LSR_MAX_STARTS, BATCH_LSR_MAX_ROUNDS), strict=True,
                          separators=True, max_spread=BATCH_LSR_MAX_SPREAD),
+    "lsf": HeuristicKind(CVRP, "vrp_batch_lsf", BATCH_LSF_LDS_BYTES,
+                         _ls_knobs(BATCH_LSF_MAX_STARTS, BATCH_LSF_MAX_ROUNDS), strict=True,
+                         separators=True, static_else="lsr"),
     "lso": HeuristicKind(TSP, "tsp_batch_lso", BATCH_LSO_LDS_BYTES,
                          _ls_knobs(BATCH_LSO_MAX_STARTS, BATCH_LSO_MAX_ROUNDS,
                                    Knob("moves", 1, 31, 31, "a move mask of {}..{}")), strict=True,
@@ -1186,6 +1211,9 @@ def _domain_message(algorithm: str, ci: CompactInstance, knobs, empty_ok: bool =
         return f"{what} supports 1..{BATCH_SA_MAX_VEHICLES} vehicles ({K} given)"
     if H not in (1, 24):
         return f"{what} needs a static or 24-slice duration matrix ({H} slices given)"
+    if kind.static_else and H != 1:
+        return (f"{what} needs a static duration matrix ({H} slices given); an hour-indexed "
+                f'request keeps "{kind.static_else}"')
     if kind.separators and N + K - 2 > 65535:
         return f"{what} supports at most 65535 tokens ({N + K - 2} given)"
     shape = (N, H, wide) if tsp else (N, K, H, wide)
@@ -1860,6 +1888,72 @@ def solve_vrp_lsr_batch(requests, *, starts: int = 64, rounds: int = 1000, seed:
         raise ValueError(f"rounds must be in 0..{BATCH_LSR_MAX_ROUNDS} ({rounds} given)")
     return _solve_heuristic_batch("lsr", requests, (starts, rounds), seed, device, objective,
                                   with_unvisited, spread)
+
+
+# ---------------------------------------------------------------------------
+# batched VRP multi-start local search over plain separator tours with delta
+# pricing (A28): static small-fleet requests share launches
+# ---------------------------------------------------------------------------
+def batch_lsf_key(ci: CompactInstance, starts: int, rounds: int):
+    """What the instances of one vrp_batch_lsf launch share (next to the
+    objective and the seed): (N, K, H, wide, starts, rounds), H being 1."""
+    return batch_sa_key(ci) + (int(starts), int(rounds))
+
+
+def batch_lsf_message(ci: CompactInstance, starts: int, rounds: int):
+    """The limit of A28's domain this request fails -> its message, or None:
+    a CVRP of at least one customer and at most 65534, 1..64 vehicles, a static
+    matrix (an hour-indexed request is told to keep "lsr"), 1 <= starts <=
+    BATCH_LSF_MAX_STARTS, 0 <= rounds <= BATCH_LSF_MAX_ROUNDS, at most 65535
+    tokens, and an instance that fits BATCH_LSF_LDS_BYTES together with the
+    wavefronts' tours, prefix rows and route tables (vrpms_vrp_batch_lsf_lds;
+    uint16 cells unless an entry is above 65535).  Needs the library, no
+    GPU."""
+    return _domain_message("lsf", ci, (starts, rounds))
+
+
+def batch_lsf_fits(ci: CompactInstance, starts: int, rounds: int) -> bool:
+    """The request is inside A28's domain (batch_lsf_message names no limit).
+    Needs the library, no GPU."""
+    return batch_lsf_message(ci, starts, rounds) is None
+
+
+def batch_lsf_launch(ctx: Context, cis, starts: int, rounds: int, seed: int,
+                     objective: str = "sum"):
+    """One upload and one vrp_batch_lsf launch for compact instances of one
+    batch_lsf_key (each passed batch_guard_message and batch_lsf_fits) ->
+    (tours, veh, durs), as batch_lsr_launch gives them."""
+    return _heuristic_launch("lsf", ctx, cis, (starts, rounds), seed, objective)
+
+
+def solve_vrp_lsf_batch(requests, *, starts: int = 64, rounds: int = 1000, seed: int = 0,
+                        objective: str = "sum", with_unvisited: bool = False,
+                        device: int = 0) -> list:
+    """A multi-start local search over plain separator tours for many static
+    small-fleet VRP requests, the requests sharing launches (spec A28):
+    solve_vrp_lsr_batch's mapping, starts, moves and answer, but a move onto a
+    tour in which some customer would not fit the route its separators give it
+    is no candidate, a start of that kind does not descend, and a candidate is
+    priced from prefix rows instead of a walk along the tour.  Where every
+    vehicle carries the whole demand the dicts are solve_vrp_lsr_batch's.
+    `requests`: solve_vrp_batch's tuples or dicts -> one solve_vrp slot dict per
+    request, solve_vrp("lsf", starts=, rounds=)'s.
+
+    Every request is compacted and passed through batch_guard_message and the
+    domain (batch_lsf_message) on the host before any device is touched; one
+    outside it raises ValueError("request {x}: ...") naming the limit that
+    failed -- for an hour-indexed matrix, that "lsr" takes it.  With no local
+    GPU each request goes to solve_vrp("lsf") on the GPU box.  The requests
+    are grouped by (N, K, wide), one upload and one vrp_batch_lsf launch per
+    group; no customer has solve_vrp's trivial answer."""
+    if objective not in ("sum", "max"):
+        raise ValueError("objective must be 'sum' or 'max'")
+    if not 1 <= int(starts) <= BATCH_LSF_MAX_STARTS:
+        raise ValueError(f"starts must be in 1..{BATCH_LSF_MAX_STARTS} ({starts} given)")
+    if not 0 <= int(rounds) <= BATCH_LSF_MAX_ROUNDS:
+        raise ValueError(f"rounds must be in 0..{BATCH_LSF_MAX_ROUNDS} ({rounds} given)")
+    return _solve_heuristic_batch("lsf", requests, (starts, rounds), seed, device, objective,
+                                  with_unvisited)
 
 
 # ---------------------------------------------------------------------------
