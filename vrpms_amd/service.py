@@ -25,6 +25,7 @@ connection), and a solver exception becomes a 400 {'what': 'Solver error'}.
 from __future__ import annotations
 
 import argparse
+import inspect
 import json
 import sys
 import threading
@@ -457,6 +458,17 @@ class ExactTdspBatcher(ExactBatcher):
         return self._solved(ci, bound=int(bound), objective=_objective(objective))
 
 
+class _on_class_or_instance:
+    """A method bound to the instance it is looked up on, and to the class
+    when looked up there: VrpSaBatcher.accepts(ci) and batcher.accepts(ci)."""
+
+    def __init__(self, fn):
+        self.fn = fn
+
+    def __get__(self, obj, cls):
+        return self.fn.__get__(cls if obj is None else obj)
+
+
 class VrpSaBatcher(TspBatcher):
     """Coalesces concurrent /api/vrp/sa and /solve/vrp/sa requests into one
     `vrp_batch_sa` launch per (node count, fleet size, hour count, cell width,
@@ -468,35 +480,85 @@ class VrpSaBatcher(TspBatcher):
     solver.solve_vrp_sa_batch([request], steps, the app's seed)'s.  It is not
     the unbatched endpoint's answer (four chains here, 1,024 there).  A launch
     returns (tours, [(veh, durs), ...]): the second list rides TspBatcher's
-    per-job duration field."""
+    per-job duration field.
+
+    It is also all that the batchers of the other VRP heuristics do.  A
+    subclass names its ALGORITHM of solver.HEURISTIC_KINDS and the KNOBS its
+    launch takes, which begin with the knobs of the kind's domain: those in
+    JOB (name -> default) travel with a job and end its group key, the others
+    are attributes of the batcher, set by its constructor."""
+
+    ALGORITHM = "sa"
+    KNOBS = ("steps",)
+    JOB = {}
+    spread = None                # the launch's, where the algorithm has a spread form
+
+    def __init__(self, app, window_s: float = 0.005, steps: int = 2000, max_batch: int = 16384,
+                 launch=None):
+        self._start(app, window_s, max_batch, launch, steps=steps)
+
+    def _start(self, app, window_s, max_batch, launch, **own):
+        """What every constructor ends in: the batcher's own knobs become its
+        attributes, one that the domain ranges is refused outside that range
+        (the launch would refuse it: no clamp), then TspBatcher's start."""
+        from . import solver
+        ranged = dict(zip(self.KNOBS, solver.HEURISTIC_KINDS[self.ALGORITHM].knobs))
+        for name, value in own.items():
+            if name in ranged:
+                value = solver.check_range(self.ALGORITHM, ranged[name].name, value, name)
+            setattr(self, name, value)
+        TspBatcher.__init__(self, app, window_s, own.get("steps", 0), max_batch, launch)
 
     @classmethod
-    def accepts(cls, ci) -> bool:
-        """Requests inside A22's LDS domain that pass the int32 guards
-        vrpms_set_instance applies on the unbatched path; anything else takes
-        the unbatched path, so both paths share one error contract."""
-        from . import solver
-        return solver.batch_sa_fits(ci) and solver.batch_guard_message(ci) is None
+    def _job(cls, given, named) -> dict:
+        """A job's knobs: JOB under what a caller gave by position or by name."""
+        if len(given) > len(cls.JOB) or not set(named) <= set(cls.JOB):
+            raise TypeError(f"{cls.__name__}: a job's knobs are {tuple(cls.JOB)}")
+        return {k: int(v) for k, v in {**cls.JOB, **dict(zip(cls.JOB, given)), **named}.items()}
 
-    @staticmethod
-    def group_key(job):
-        from . import solver
-        return solver.batch_sa_key(job["ci"]) + (job["objective"],)
+    @_on_class_or_instance
+    def _knobs(self, job, count=None) -> tuple:
+        """The first `count` (default: all) of KNOBS: the job's, else the batcher's."""
+        return tuple(job[k] if k in job else getattr(self, k) for k in self.KNOBS[:count])
 
-    def solve(self, ci, objective: str = "sum") -> dict:
+    @_on_class_or_instance
+    def accepts(self, ci, *knobs, **named) -> bool:
+        """Requests inside the algorithm's domain, at the job's knobs and the
+        batcher's own (so on the class only where the domain has none of the
+        latter), that pass the int32 guards vrpms_set_instance applies on the
+        unbatched path.  Anything else takes the unbatched path, so both paths
+        share one error contract: a local search's raises the domain's message."""
+        from . import solver
+        domain = len(solver.HEURISTIC_KINDS[self.ALGORITHM].knobs)
+        knobs = self._knobs(self._job(knobs, named), domain)
+        return solver._domain_message(self.ALGORITHM, ci, knobs) is None and \
+            solver.batch_guard_message(ci) is None
+
+    @classmethod
+    def group_key(cls, job):
+        """The shape, the objective, then the job's own knobs."""
+        from . import solver
+        return solver.batch_sa_key(job["ci"]) + (job["objective"],) + tuple(job[k] for k in cls.JOB)
+
+    def solve(self, ci, objective: str = "sum", *knobs, **named) -> dict:
         """Blocks until the request's launch finished -> the VRP slot dict."""
         from . import solver
-        job = {"ci": ci, "done": threading.Event(), "objective": _objective(objective)}
+        job = {"ci": ci, "done": threading.Event(), "objective": _objective(objective),
+               **self._job(knobs, named)}
         self._wait(job)
         veh, durs = job["duration"]
         return solver.sa_result(ci, list(job["tour"]), veh, durs)
 
     def _gpu_launch(self, key, cis, device=None):
+        """-> (tours, [(veh, durs), ...]) of the launch solver has under the
+        algorithm's name when this runs, on `device` (default: the app's first)."""
         from . import solver
         dev = self.devices[0] if device is None else device
+        objective, *job = key[len(key) - len(self.JOB) - 1:]
         with self.app.locks[dev]:
-            tours, veh, durs = solver.batch_sa_launch(solver.context(dev), cis, self.steps,
-                                                      self.app.seed, key[-1])
+            tours, veh, durs = solver.batch_launch(
+                self.ALGORITHM, solver.context(dev), cis, self._knobs(dict(zip(self.JOB, job))),
+                self.app.seed, objective, self.spread)
         return tours, list(zip(veh, durs))
 
 
@@ -513,38 +575,10 @@ class VrpGaBatcher(VrpSaBatcher):
     objective=)'s.  It is NOT the unbatched endpoint's answer, which breeds 8
     islands from another start."""
 
-    pmut = 0.2     # solve_vrp_ga_batch's default
-
-    @classmethod
-    def accepts(cls, ci, pop: int = 256, gens: int = 400) -> bool:
-        """Requests inside A23's domain (LDS, pop <= 256, the generation cap)
-        that pass the int32 guards vrpms_set_instance applies on the unbatched
-        path; anything else takes the unbatched path."""
-        from . import solver
-        return solver.batch_ga_fits(ci, pop, gens) and solver.batch_guard_message(ci) is None
-
-    @staticmethod
-    def group_key(job):
-        from . import solver
-        return solver.batch_sa_key(job["ci"]) + (job["objective"], job["pop"], job["gens"])
-
-    def solve(self, ci, objective: str = "sum", pop: int = 256, gens: int = 400) -> dict:
-        """Blocks until the request's launch finished -> the VRP slot dict."""
-        from . import solver
-        job = {"ci": ci, "done": threading.Event(), "objective": _objective(objective),
-               "pop": int(pop), "gens": int(gens)}
-        self._wait(job)
-        veh, durs = job["duration"]
-        return solver.sa_result(ci, list(job["tour"]), veh, durs)
-
-    def _gpu_launch(self, key, cis, device=None):
-        from . import solver
-        dev = self.devices[0] if device is None else device
-        objective, pop, gens = key[-3:]
-        with self.app.locks[dev]:
-            tours, veh, durs = solver.batch_ga_launch(solver.context(dev), cis, pop, gens, self.pmut,
-                                                      self.app.seed, objective)
-        return tours, list(zip(veh, durs))
+    ALGORITHM = "ga"
+    KNOBS = ("pop", "gens", "pmut")
+    JOB = {"pop": 256, "gens": 400}     # solve_vrp's defaults (solver.ga_knobs)
+    pmut = 0.2                          # solve_vrp_ga_batch's default
 
 
 class VrpAcoBatcher(VrpSaBatcher):
@@ -559,32 +593,12 @@ class VrpAcoBatcher(VrpSaBatcher):
     app's, objective=)'s.  It is NOT the unbatched endpoint's answer, which
     runs 4 colonies."""
 
+    ALGORITHM = "aco"
+    KNOBS = ("ants", "iters")
+
     def __init__(self, app, window_s: float = 0.005, iters: int = 100, ants: int = 64,
                  max_batch: int = 16384, launch=None):
-        from . import solver
-        if not 1 <= int(ants) <= solver.BATCH_ACO_MAX_ANTS:
-            raise ValueError(f"ants must be in 1..{solver.BATCH_ACO_MAX_ANTS} ({ants} given)")
-        if not 1 <= int(iters) <= solver.BATCH_ACO_MAX_ITERATIONS:
-            raise ValueError(f"iters must be in 1..{solver.BATCH_ACO_MAX_ITERATIONS} "
-                             f"({iters} given)")
-        self.ants, self.iters = int(ants), int(iters)
-        super().__init__(app, window_s, steps=0, max_batch=max_batch, launch=launch)
-
-    def accepts(self, ci) -> bool:
-        """Requests inside A24's domain (LDS at the batcher's ants) that pass
-        the int32 guards vrpms_set_instance applies on the unbatched path;
-        anything else takes the unbatched path."""
-        from . import solver
-        return solver.batch_aco_fits(ci, self.ants, self.iters) and \
-            solver.batch_guard_message(ci) is None
-
-    def _gpu_launch(self, key, cis, device=None):
-        from . import solver
-        dev = self.devices[0] if device is None else device
-        with self.app.locks[dev]:
-            tours, veh, durs = solver.batch_aco_launch(solver.context(dev), cis, self.ants,
-                                                       self.iters, self.app.seed, key[-1])
-        return tours, list(zip(veh, durs))
+        self._start(app, window_s, max_batch, launch, ants=ants, iters=iters)
 
 
 class VrpLsBatcher(VrpSaBatcher):
@@ -599,32 +613,12 @@ class VrpLsBatcher(VrpSaBatcher):
     starts=, rounds=, seed=the app's, objective=)'s, which is also the
     unbatched route's at the same knobs and seed."""
 
+    ALGORITHM = "ls"
+    KNOBS = ("starts", "rounds")
+
     def __init__(self, app, window_s: float = 0.005, rounds: int = 1000, starts: int = 64,
                  max_batch: int = 16384, launch=None):
-        from . import solver
-        if not 1 <= int(starts) <= solver.BATCH_LS_MAX_STARTS:
-            raise ValueError(f"starts must be in 1..{solver.BATCH_LS_MAX_STARTS} ({starts} given)")
-        if not 0 <= int(rounds) <= solver.BATCH_LS_MAX_ROUNDS:
-            raise ValueError(f"rounds must be in 0..{solver.BATCH_LS_MAX_ROUNDS} "
-                             f"({rounds} given)")
-        self.starts, self.rounds = int(starts), int(rounds)
-        super().__init__(app, window_s, steps=0, max_batch=max_batch, launch=launch)
-
-    def accepts(self, ci) -> bool:
-        """Requests inside A25's domain (LDS) that pass the int32 guards;
-        anything else takes the unbatched path, which raises the domain's
-        message."""
-        from . import solver
-        return solver.batch_ls_fits(ci, self.starts, self.rounds) and \
-            solver.batch_guard_message(ci) is None
-
-    def _gpu_launch(self, key, cis, device=None):
-        from . import solver
-        dev = self.devices[0] if device is None else device
-        with self.app.locks[dev]:
-            tours, veh, durs = solver.batch_ls_launch(solver.context(dev), cis, self.starts,
-                                                      self.rounds, self.app.seed, key[-1])
-        return tours, list(zip(veh, durs))
+        self._start(app, window_s, max_batch, launch, starts=starts, rounds=rounds)
 
 
 class VrpLsrBatcher(VrpLsBatcher):
@@ -640,33 +634,13 @@ class VrpLsrBatcher(VrpLsBatcher):
     solver.batch_lsr_launch's: how many workgroups a request's starts are
     spread over, which changes a launch's time and no answer."""
 
+    ALGORITHM = "lsr"
+
     def __init__(self, app, window_s: float = 0.005, rounds: int = 1000, starts: int = 64,
                  max_batch: int = 16384, launch=None, spread=None):
         from . import solver
         self.spread = solver.check_lsr_spread(spread)
-        if not 1 <= int(starts) <= solver.BATCH_LSR_MAX_STARTS:
-            raise ValueError(f"starts must be in 1..{solver.BATCH_LSR_MAX_STARTS} ({starts} given)")
-        if not 0 <= int(rounds) <= solver.BATCH_LSR_MAX_ROUNDS:
-            raise ValueError(f"rounds must be in 0..{solver.BATCH_LSR_MAX_ROUNDS} "
-                             f"({rounds} given)")
-        super().__init__(app, window_s, rounds, starts, max_batch=max_batch, launch=launch)
-
-    def accepts(self, ci) -> bool:
-        """Requests inside A26's domain (LDS) that pass the int32 guards;
-        anything else takes the unbatched path, which raises the domain's
-        message."""
-        from . import solver
-        return solver.batch_lsr_fits(ci, self.starts, self.rounds) and \
-            solver.batch_guard_message(ci) is None
-
-    def _gpu_launch(self, key, cis, device=None):
-        from . import solver
-        dev = self.devices[0] if device is None else device
-        with self.app.locks[dev]:
-            tours, veh, durs = solver.batch_lsr_launch(solver.context(dev), cis, self.starts,
-                                                       self.rounds, self.app.seed, key[-1],
-                                                       spread=self.spread)
-        return tours, list(zip(veh, durs))
+        super().__init__(app, window_s, rounds, starts, max_batch, launch)
 
 
 class VrpLsfBatcher(VrpLsBatcher):
@@ -682,31 +656,68 @@ class VrpLsfBatcher(VrpLsBatcher):
     objective=)'s, which is also the unbatched route's at the same knobs and
     seed."""
 
-    def __init__(self, app, window_s: float = 0.005, rounds: int = 1000, starts: int = 64,
-                 max_batch: int = 16384, launch=None):
-        from . import solver
-        if not 1 <= int(starts) <= solver.BATCH_LSF_MAX_STARTS:
-            raise ValueError(f"starts must be in 1..{solver.BATCH_LSF_MAX_STARTS} ({starts} given)")
-        if not 0 <= int(rounds) <= solver.BATCH_LSF_MAX_ROUNDS:
-            raise ValueError(f"rounds must be in 0..{solver.BATCH_LSF_MAX_ROUNDS} "
-                             f"({rounds} given)")
-        super().__init__(app, window_s, rounds, starts, max_batch=max_batch, launch=launch)
+    ALGORITHM = "lsf"
 
-    def accepts(self, ci) -> bool:
-        """Requests inside A28's domain (a static matrix, LDS) that pass the
-        int32 guards; anything else takes the unbatched path, which raises the
-        domain's message."""
-        from . import solver
-        return solver.batch_lsf_fits(ci, self.starts, self.rounds) and \
-            solver.batch_guard_message(ci) is None
 
-    def _gpu_launch(self, key, cis, device=None):
-        from . import solver
-        dev = self.devices[0] if device is None else device
-        with self.app.locks[dev]:
-            tours, veh, durs = solver.batch_lsf_launch(solver.context(dev), cis, self.starts,
-                                                       self.rounds, self.app.seed, key[-1])
-        return tours, list(zip(veh, durs))
+def _coalesce(requests, launches, answer="") -> str:
+    """The help of a --batch-vrp-<algorithm> flag."""
+    return (f"coalesce concurrent small-fleet VRP {requests} into {launches}{answer}; "
+            f"{'it' if answer else 'the answer'} depends on the request alone, not on the batch "
+            f"it rode in")
+
+
+def _coalesce_ls(a, requests, matrix="static or hour-indexed matrix") -> str:
+    return _coalesce(f"{requests} (/solve/vrp/{a}, {matrix}, 1..64 vehicles, an instance that fits "
+                     f"the LDS)", f"vrp_batch_{a} launches of --batch-{a}-starts starts and at most "
+                                  f"--batch-{a}-rounds rounds a descent")
+
+
+# The batched VRP heuristics of App and main(): algorithm -> (its batcher, {a
+# parameter of its constructor: the App keyword that it comes from}, the help
+# of its flag).  For each, App also takes batch_vrp_<algorithm> (off by default)
+# and batch_vrp_<algorithm>_launch and keeps the batcher, or None, as
+# vrp_<algorithm>_batcher; main() has --batch-vrp-<algorithm> and a flag, the
+# keyword with dashes, for every knob here that the algorithm's domain ranges.
+HEURISTIC_BATCHERS = {
+    "sa": (VrpSaBatcher, {"steps": "batch_steps"}, _coalesce(
+        "SA requests (/api/vrp/sa and /solve/vrp/sa, static or hour-indexed matrix, 1..64 "
+        "vehicles, an instance that fits the LDS)", "vrp_batch_sa launches of --batch-steps steps",
+        ": four chains per request, so the answer differs from the unbatched endpoint's")),
+    "ga": (VrpGaBatcher, {}, _coalesce(
+        "GA requests (/api/vrp/ga and /solve/vrp/ga, static or hour-indexed matrix, 1..64 "
+        "vehicles, randomPermutationCount up to 256, iterationCount up to "
+        "solver.BATCH_GA_MAX_GENERATIONS, multiThreaded not true, an instance and population "
+        "that fit the LDS)", "vrp_batch_ga launches",
+        ": one population per request, so the answer differs from the unbatched endpoint's")),
+    "aco": (VrpAcoBatcher, {"iters": "batch_aco_iterations", "ants": "batch_aco_ants"}, _coalesce(
+        "ACO requests (/api/vrp/aco and /solve/vrp/aco, static or hour-indexed matrix, 1..64 "
+        "vehicles, an instance and colony that fit the LDS)",
+        "vrp_batch_aco launches of --batch-aco-ants ants and --batch-aco-iterations iterations",
+        ": one colony per request, so the answer differs from the unbatched endpoint's")),
+    "ls": (VrpLsBatcher, {"starts": "batch_ls_starts", "rounds": "batch_ls_rounds"},
+           _coalesce_ls("ls", "local-search requests")),
+    "lsr": (VrpLsrBatcher, {"starts": "batch_lsr_starts", "rounds": "batch_lsr_rounds",
+                            "spread": "batch_lsr_spread"},
+            _coalesce_ls("lsr", "requests of the local search over separator tours")),
+    "lsf": (VrpLsfBatcher, {"starts": "batch_lsf_starts", "rounds": "batch_lsf_rounds"},
+            _coalesce_ls("lsf", "requests of the local search over plain separator tours",
+                         "static matrix")),
+}
+# what a ranged knob's flag says before the range and the solver constant behind it
+_KNOB_HELP = {"iters": "iterations of a {} launch", "ants": "ants of a {} launch",
+              "starts": "starts of a {} launch",
+              "rounds": "applied moves a descent of a {} launch may take"}
+
+
+def _heuristic_keywords() -> dict:
+    """{App keyword: default} of HEURISTIC_BATCHERS, a knob's default being its
+    constructor's."""
+    out = {}
+    for algorithm, (cls, knobs, _) in HEURISTIC_BATCHERS.items():
+        out.update({f"batch_vrp_{algorithm}": False, f"batch_vrp_{algorithm}_launch": None})
+        defaults = inspect.signature(cls).parameters
+        out.update((keyword, defaults[name].default) for name, keyword in knobs.items())
+    return out
 
 
 # ---------------------------------------------------------------------------
@@ -724,25 +735,23 @@ class App:
     VRP GA endpoint's `multiThreaded` (api/parameters.py:20, the reference's
     only parallelism knob) decides that for its request instead: true runs
     the island model over every device, false one device.  A device listed
-    twice (one GPU standing in for two) is locked once."""
+    twice (one GPU standing in for two) is locked once.
+
+    `heuristics`: the keywords of HEURISTIC_BATCHERS -- batch_vrp_<algorithm>,
+    batch_vrp_<algorithm>_launch and the batchers' knobs (batch_aco_ants,
+    batch_ls_starts, batch_lsr_spread, ...), each at its batcher's default; any
+    other keyword is a TypeError."""
 
     def __init__(self, store, device: int = 0, seed: int = 0, max_seconds: float | None = None,
                  solve=None, batch_tsp: bool = False, batch_window_s: float = 0.005,
                  batch_steps: int = 2000, batch_launch=None, devices=None,
                  island_min_n: int = 150, batch_exact: bool = False, batch_exact_launch=None,
                  batch_exact_vrp_launch=None, batch_exact_tdp_launch=None,
-                 batch_exact_tdsp: bool = False, batch_exact_tdsp_launch=None,
-                 batch_vrp_sa: bool = False, batch_vrp_sa_launch=None,
-                 batch_vrp_ga: bool = False, batch_vrp_ga_launch=None,
-                 batch_vrp_aco: bool = False, batch_vrp_aco_launch=None,
-                 batch_aco_iterations: int = 100, batch_aco_ants: int = 64,
-                 batch_vrp_ls: bool = False, batch_vrp_ls_launch=None,
-                 batch_ls_starts: int = 64, batch_ls_rounds: int = 1000,
-                 batch_vrp_lsr: bool = False, batch_vrp_lsr_launch=None,
-                 batch_lsr_starts: int = 64, batch_lsr_rounds: int = 1000,
-                 batch_lsr_spread=None,
-                 batch_vrp_lsf: bool = False, batch_vrp_lsf_launch=None,
-                 batch_lsf_starts: int = 64, batch_lsf_rounds: int = 1000):
+                 batch_exact_tdsp: bool = False, batch_exact_tdsp_launch=None, **heuristics):
+        options = dict(_heuristic_keywords(), batch_steps=batch_steps)
+        for name in heuristics.keys() - options.keys():
+            raise TypeError(f"App.__init__() got an unexpected keyword argument '{name}'")
+        options.update(heuristics)
         self.store = store
         self.devices = list(devices) if devices else [device]
         self.device = self.devices[0]
@@ -772,34 +781,14 @@ class App:
         self.exact_tdsp_batcher = ExactTdspBatcher(self, batch_window_s,
                                                    launch=batch_exact_tdsp_launch) \
             if batch_exact_tdsp else None
-        # small-fleet VRP SA requests share vrp_batch_sa launches (off by
-        # default: the batched answer is not the unbatched endpoint's)
-        self.vrp_sa_batcher = VrpSaBatcher(self, batch_window_s, batch_steps,
-                                           launch=batch_vrp_sa_launch) \
-            if batch_vrp_sa else None
-
-        # small-fleet VRP GA requests share vrp_batch_ga launches (off by
-        # default: the batched answer is not the unbatched endpoint's)
-        self.vrp_ga_batcher = VrpGaBatcher(self, batch_window_s, launch=batch_vrp_ga_launch) \
-            if batch_vrp_ga else None
-        # small-fleet VRP ACO requests share vrp_batch_aco launches (off by
-        # default: the batched answer is not the unbatched endpoint's)
-        self.vrp_aco_batcher = VrpAcoBatcher(self, batch_window_s, batch_aco_iterations,
-                                             batch_aco_ants, launch=batch_vrp_aco_launch) \
-            if batch_vrp_aco else None
-        # small-fleet VRP local-search requests share vrp_batch_ls launches
-        self.vrp_ls_batcher = VrpLsBatcher(self, batch_window_s, batch_ls_rounds,
-                                           batch_ls_starts, launch=batch_vrp_ls_launch) \
-            if batch_vrp_ls else None
-        # and those over separator tours vrp_batch_lsr launches
-        self.vrp_lsr_batcher = VrpLsrBatcher(self, batch_window_s, batch_lsr_rounds,
-                                             batch_lsr_starts, launch=batch_vrp_lsr_launch,
-                                             spread=batch_lsr_spread) \
-            if batch_vrp_lsr else None
-        # and those over plain separator tours vrp_batch_lsf launches
-        self.vrp_lsf_batcher = VrpLsfBatcher(self, batch_window_s, batch_lsf_rounds,
-                                             batch_lsf_starts, launch=batch_vrp_lsf_launch) \
-            if batch_vrp_lsf else None
+        # small-fleet requests of a VRP heuristic share its vrp_batch_<algorithm>
+        # launches (each off by default: for sa, ga and aco the batched answer
+        # is not the unbatched endpoint's)
+        for algorithm, (cls, knobs, _) in HEURISTIC_BATCHERS.items():
+            own = {name: options[keyword] for name, keyword in knobs.items()}
+            batcher = cls(self, batch_window_s, launch=options[f"batch_vrp_{algorithm}_launch"],
+                          **own) if options[f"batch_vrp_{algorithm}"] else None
+            setattr(self, f"vrp_{algorithm}_batcher", batcher)
 
     def _scheduled(self, problem, algorithm, params, knobs, locations, durations):
         """Run the solve on a device: all of them (in order, as an island
@@ -847,110 +836,29 @@ class App:
                                 params["start_time"] or 0)
         return ci if batcher.accepts(ci) else None
 
-    def _batched_vrp_sa(self, problem, algorithm, params, knobs, locations, durations):
-        """The compact instance when this request rides the VRP SA batcher,
-        else None: the flag is on, the route is vrp / sa, the request names
-        no inline knob of its own and it is inside the batcher's domain."""
-        if self.vrp_sa_batcher is None or (problem, algorithm) != ("vrp", "sa") or \
-                knobs.get("inline"):
-            return None
-        from . import solver
-        ci = solver.compact_vrp(durations, locations, params["capacities"], params["start_times"],
-                                params["ignored_customers"], params["completed_customers"])
-        return ci if self.vrp_sa_batcher.accepts(ci) else None
-
-    def _batched_vrp_ga(self, problem, algorithm, params, knobs, locations, durations):
-        """(compact instance, pop, gens) when this request rides the VRP GA
-        batcher, else None: the flag is on, the route is vrp / ga, the request
-        names no inline knob of its own, its multiThreaded is not true, and
-        its population (at most 256), generations (at most the cap) and
-        instance are inside the batcher's domain."""
-        if self.vrp_ga_batcher is None or (problem, algorithm) != ("vrp", "ga") or \
-                knobs.get("inline") or multi_threaded(knobs.get("multi_threaded")) is True:
-            return None
-        from . import solver
-        pop, gens = solver.ga_knobs(knobs.get("random_permutationCount"),
-                                    knobs.get("iteration_count"))
-        ci = solver.compact_vrp(durations, locations, params["capacities"], params["start_times"],
-                                params["ignored_customers"], params["completed_customers"])
-        return (ci, pop, gens) if self.vrp_ga_batcher.accepts(ci, pop, gens) else None
-
-    def _batched_vrp_aco(self, problem, algorithm, params, knobs, locations, durations):
-        """The compact instance when this request rides the VRP ACO batcher,
-        else None: the flag is on, the route is vrp / aco, the request names
-        no inline knob of its own and it is inside the batcher's domain."""
-        if self.vrp_aco_batcher is None or (problem, algorithm) != ("vrp", "aco") or \
-                knobs.get("inline"):
-            return None
-        from . import solver
-        ci = solver.compact_vrp(durations, locations, params["capacities"], params["start_times"],
-                                params["ignored_customers"], params["completed_customers"])
-        return ci if self.vrp_aco_batcher.accepts(ci) else None
-
-    def _batched_vrp_ls(self, problem, algorithm, params, knobs, locations, durations):
-        """The compact instance when this request rides the VRP local-search
-        batcher, else None: the flag is on, the route is vrp / ls, the request
-        names no inline knob of its own and it is inside the batcher's domain
-        (outside it the unbatched path raises the domain's message)."""
-        if self.vrp_ls_batcher is None or (problem, algorithm) != ("vrp", "ls") or \
-                knobs.get("inline"):
-            return None
-        from . import solver
-        ci = solver.compact_vrp(durations, locations, params["capacities"], params["start_times"],
-                                params["ignored_customers"], params["completed_customers"])
-        return ci if self.vrp_ls_batcher.accepts(ci) else None
-
-    def _batched_vrp_lsr(self, problem, algorithm, params, knobs, locations, durations):
-        """The compact instance when this request rides the batcher of the
-        local search over separator tours, else None: the flag is on, the
-        route is vrp / lsr, the request names no inline knob of its own and it
-        is inside the batcher's domain (outside it the unbatched path raises
-        the domain's message)."""
-        if self.vrp_lsr_batcher is None or (problem, algorithm) != ("vrp", "lsr") or \
-                knobs.get("inline"):
-            return None
-        from . import solver
-        ci = solver.compact_vrp(durations, locations, params["capacities"], params["start_times"],
-                                params["ignored_customers"], params["completed_customers"])
-        return ci if self.vrp_lsr_batcher.accepts(ci) else None
-
-    def _batched_vrp_lsf(self, problem, algorithm, params, knobs, locations, durations):
-        """The compact instance when this request rides the batcher of the
-        local search over plain separator tours, else None: the flag is on,
-        the route is vrp / lsf, the request names no inline knob of its own
-        and it is inside the batcher's domain (outside it the unbatched path
-        raises the domain's message)."""
-        if self.vrp_lsf_batcher is None or (problem, algorithm) != ("vrp", "lsf") or \
-                knobs.get("inline"):
-            return None
-        from . import solver
-        ci = solver.compact_vrp(durations, locations, params["capacities"], params["start_times"],
-                                params["ignored_customers"], params["completed_customers"])
-        return ci if self.vrp_lsf_batcher.accepts(ci) else None
-
     def _batched_vrp(self, problem, algorithm, params, knobs, locations, durations):
-        """A thunk that solves this request on the VRP SA, GA, ACO or one of
-        the local-search batchers, else None."""
+        """A thunk that solves this request on the batcher of its VRP
+        heuristic, else None: the algorithm's flag is on, the request names no
+        inline knob of its own, its multiThreaded (a ga request's) is not true,
+        and its instance -- for ga also its population (at most 256) and
+        generations (at most the cap) -- is inside the batcher's domain
+        (outside it the unbatched path answers, a local search's with the
+        domain's message)."""
+        batcher = getattr(self, f"vrp_{algorithm}_batcher") \
+            if problem == "vrp" and algorithm in HEURISTIC_BATCHERS else None
+        if batcher is None or knobs.get("inline") or \
+                multi_threaded(knobs.get("multi_threaded")) is True:
+            return None
+        from . import solver
+        # the only knobs that travel with a request are ga's, under these names
+        job = solver.ga_knobs(knobs.get("random_permutationCount"),
+                              knobs.get("iteration_count")) if batcher.JOB else ()
+        ci = solver.compact_vrp(durations, locations, params["capacities"], params["start_times"],
+                                params["ignored_customers"], params["completed_customers"])
+        if not batcher.accepts(ci, *job):
+            return None
         objective = knobs.get("objective", "sum")
-        vci = self._batched_vrp_sa(problem, algorithm, params, knobs, locations, durations)
-        if vci is not None:
-            return lambda: self.vrp_sa_batcher.solve(vci, objective)
-        gci = self._batched_vrp_ga(problem, algorithm, params, knobs, locations, durations)
-        if gci is not None:
-            return lambda: self.vrp_ga_batcher.solve(gci[0], objective, gci[1], gci[2])
-        aci = self._batched_vrp_aco(problem, algorithm, params, knobs, locations, durations)
-        if aci is not None:
-            return lambda: self.vrp_aco_batcher.solve(aci, objective)
-        lci = self._batched_vrp_ls(problem, algorithm, params, knobs, locations, durations)
-        if lci is not None:
-            return lambda: self.vrp_ls_batcher.solve(lci, objective)
-        rci = self._batched_vrp_lsr(problem, algorithm, params, knobs, locations, durations)
-        if rci is not None:
-            return lambda: self.vrp_lsr_batcher.solve(rci, objective)
-        fci = self._batched_vrp_lsf(problem, algorithm, params, knobs, locations, durations)
-        if fci is not None:
-            return lambda: self.vrp_lsf_batcher.solve(fci, objective)
-        return None
+        return lambda: batcher.solve(ci, objective, *job)
 
     def _exact_batcher(self, problem, algorithm):
         """The exact batcher of an inline (problem, algorithm), or None."""
@@ -1269,76 +1177,23 @@ def main(argv=None):
                          "(/solve/vrp/tdsp, static or hour-indexed matrix, 1..11 customers, a "
                          "fleet and an upper bound whose state fits the LDS) into vrp_batch_tdsp "
                          "launches; the answers equal the unbatched ones")
-    ap.add_argument("--batch-vrp-sa", action="store_true",
-                    help="coalesce concurrent small-fleet VRP SA requests (/api/vrp/sa and "
-                         "/solve/vrp/sa, static or hour-indexed matrix, 1..64 vehicles, an "
-                         "instance that fits the LDS) into vrp_batch_sa launches of --batch-steps "
-                         "steps: four chains per request, so the answer differs from the "
-                         "unbatched endpoint's; it depends on the request alone, not on the "
-                         "batch it rode in")
-    ap.add_argument("--batch-vrp-ga", action="store_true",
-                    help="coalesce concurrent small-fleet VRP GA requests (/api/vrp/ga and "
-                         "/solve/vrp/ga, static or hour-indexed matrix, 1..64 vehicles, "
-                         "randomPermutationCount up to 256, iterationCount up to "
-                         "solver.BATCH_GA_MAX_GENERATIONS, multiThreaded not true, an instance "
-                         "and population that fit the LDS) into vrp_batch_ga launches: one "
-                         "population per request, so the answer differs from the unbatched "
-                         "endpoint's; it depends on the request alone, not on the batch it "
-                         "rode in")
-    ap.add_argument("--batch-vrp-aco", action="store_true",
-                    help="coalesce concurrent small-fleet VRP ACO requests (/api/vrp/aco and "
-                         "/solve/vrp/aco, static or hour-indexed matrix, 1..64 vehicles, an "
-                         "instance and colony that fit the LDS) into vrp_batch_aco launches of "
-                         "--batch-aco-ants ants and --batch-aco-iterations iterations: one colony "
-                         "per request, so the answer differs from the unbatched endpoint's; it "
-                         "depends on the request alone, not on the batch it rode in")
-    ap.add_argument("--batch-aco-iterations", type=_int_in(1, solver.BATCH_ACO_MAX_ITERATIONS), default=100,
-                    help="iterations of a vrp_batch_aco launch, 1..1000 "
-                         "(solver.BATCH_ACO_MAX_ITERATIONS)")
-    ap.add_argument("--batch-aco-ants", type=_int_in(1, solver.BATCH_ACO_MAX_ANTS), default=64,
-                    help="ants of a vrp_batch_aco launch, 1..256 (solver.BATCH_ACO_MAX_ANTS)")
-    ap.add_argument("--batch-vrp-ls", action="store_true",
-                    help="coalesce concurrent small-fleet VRP local-search requests "
-                         "(/solve/vrp/ls, static or hour-indexed matrix, 1..64 vehicles, an "
-                         "instance that fits the LDS) into vrp_batch_ls launches of "
-                         "--batch-ls-starts starts and at most --batch-ls-rounds rounds a descent; "
-                         "the answer depends on the request alone, not on the batch it rode in")
-    ap.add_argument("--batch-ls-starts", type=_int_in(1, solver.BATCH_LS_MAX_STARTS), default=64,
-                    help="starts of a vrp_batch_ls launch, 1..1024 (solver.BATCH_LS_MAX_STARTS)")
-    ap.add_argument("--batch-ls-rounds", type=_int_in(0, solver.BATCH_LS_MAX_ROUNDS), default=1000,
-                    help="applied moves a descent of a vrp_batch_ls launch may take, 0..1000 "
-                         "(solver.BATCH_LS_MAX_ROUNDS)")
-    ap.add_argument("--batch-vrp-lsr", action="store_true",
-                    help="coalesce concurrent small-fleet VRP requests of the local search over "
-                         "separator tours (/solve/vrp/lsr, static or hour-indexed matrix, 1..64 "
-                         "vehicles, an instance that fits the LDS) into vrp_batch_lsr launches of "
-                         "--batch-lsr-starts starts and at most --batch-lsr-rounds rounds a "
-                         "descent; the answer depends on the request alone, not on the batch it "
-                         "rode in")
-    ap.add_argument("--batch-lsr-starts", type=_int_in(1, solver.BATCH_LSR_MAX_STARTS), default=64,
-                    help="starts of a vrp_batch_lsr launch, 1..1024 (solver.BATCH_LSR_MAX_STARTS)")
-    ap.add_argument("--batch-lsr-rounds", type=_int_in(0, solver.BATCH_LSR_MAX_ROUNDS),
-                    default=1000,
-                    help="applied moves a descent of a vrp_batch_lsr launch may take, 0..1000 "
-                         "(solver.BATCH_LSR_MAX_ROUNDS)")
+    defaults = _heuristic_keywords()
+    for a, (cls, knobs, text) in HEURISTIC_BATCHERS.items():
+        ap.add_argument(f"--batch-vrp-{a}", action="store_true", help=text)
+        # a flag for every knob of the batcher's that the domain ranges
+        ranged = dict(zip(cls.KNOBS, solver.HEURISTIC_KINDS[a].knobs))
+        for name, keyword in knobs.items():
+            if name in ranged:
+                k, (batch, _, word) = ranged[name], keyword.upper().rpartition("_")
+                ap.add_argument("--" + keyword.replace("_", "-"), type=_int_in(k.lo, k.hi),
+                                default=defaults[keyword],
+                                help=f"{_KNOB_HELP[name].format(f'vrp_batch_{a}')}, {k.lo}..{k.hi} "
+                                     f"(solver.{batch}_MAX_{word})")
     ap.add_argument("--batch-lsr-spread", type=_lsr_spread, default=None, metavar="{auto,N}",
                     help="spread the starts of every request of a vrp_batch_lsr launch over N "
                          "workgroups, 1..1024 (solver.BATCH_LSR_MAX_SPREAD), or over as many as "
                          "keep the device busy (auto: solver.batch_lsr_spread); the answers are "
                          "the same, a window that caught few requests answers sooner")
-    ap.add_argument("--batch-vrp-lsf", action="store_true",
-                    help="coalesce concurrent small-fleet VRP requests of the local search over "
-                         "plain separator tours (/solve/vrp/lsf, static matrix, 1..64 vehicles, an "
-                         "instance that fits the LDS) into vrp_batch_lsf launches of "
-                         "--batch-lsf-starts starts and at most --batch-lsf-rounds rounds a "
-                         "descent; the answer depends on the request alone, not on the batch it "
-                         "rode in")
-    ap.add_argument("--batch-lsf-starts", type=_int_in(1, solver.BATCH_LSF_MAX_STARTS), default=64,
-                    help="starts of a vrp_batch_lsf launch, 1..1024 (solver.BATCH_LSF_MAX_STARTS)")
-    ap.add_argument("--batch-lsf-rounds", type=_int_in(0, solver.BATCH_LSF_MAX_ROUNDS),
-                    default=1000,
-                    help="applied moves a descent of a vrp_batch_lsf launch may take, 0..1000 "
-                         "(solver.BATCH_LSF_MAX_ROUNDS)")
     ap.add_argument("--batch-window-ms", type=float, default=5.0)
     ap.add_argument("--batch-steps", type=int, default=2000)
     ap.add_argument("--workers", type=int, default=0,
@@ -1376,16 +1231,9 @@ def main(argv=None):
         return
     app = App(store, device=args.device, seed=args.seed, max_seconds=args.max_seconds,
               batch_tsp=args.batch_tsp, batch_window_s=args.batch_window_ms * 1e-3,
-              batch_steps=args.batch_steps, devices=devices, batch_exact=args.batch_exact,
-              batch_exact_tdsp=args.batch_exact_tdsp, batch_vrp_sa=args.batch_vrp_sa,
-              batch_vrp_ga=args.batch_vrp_ga, batch_vrp_aco=args.batch_vrp_aco,
-              batch_aco_iterations=args.batch_aco_iterations, batch_aco_ants=args.batch_aco_ants,
-              batch_vrp_ls=args.batch_vrp_ls, batch_ls_starts=args.batch_ls_starts,
-              batch_ls_rounds=args.batch_ls_rounds,
-              batch_vrp_lsr=args.batch_vrp_lsr, batch_lsr_starts=args.batch_lsr_starts,
-              batch_lsr_rounds=args.batch_lsr_rounds, batch_lsr_spread=args.batch_lsr_spread,
-              batch_vrp_lsf=args.batch_vrp_lsf, batch_lsf_starts=args.batch_lsf_starts,
-              batch_lsf_rounds=args.batch_lsf_rounds)
+              devices=devices, batch_exact=args.batch_exact,
+              batch_exact_tdsp=args.batch_exact_tdsp,
+              **{k: getattr(args, k) for k in _heuristic_keywords() if hasattr(args, k)})
     srv = serve(app, args.host, args.port)
     print(f"vrpms_amd service on http://{args.host}:{args.port}/api", flush=True)
     try:

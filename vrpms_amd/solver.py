@@ -1237,6 +1237,17 @@ def _check_heuristic(algorithm: str, ci: CompactInstance, knobs):
         raise ValueError(msg)
 
 
+def check_range(algorithm: str, name: str, value, says: str = "") -> int:
+    """int(value) where the table's range of the algorithm's knob `name` holds
+    it, else a ValueError in the words of the batch entry points and of the
+    service's batchers; `says` is the caller's word for the knob where that is
+    not the table's."""
+    k = next(k for k in HEURISTIC_KINDS[algorithm].knobs if k.name == name)
+    if not k.lo <= int(value) <= k.hi:
+        raise ValueError(f"{says or name} must be in {k.lo}..{k.hi} ({value} given)")
+    return int(value)
+
+
 def _check_spread(spread, cap: int):
     """-> None, "auto" or an int in 1..cap; anything else is a ValueError."""
     if spread is None or (isinstance(spread, str) and spread == "auto"):
@@ -1278,7 +1289,7 @@ def _heuristic_launch(algorithm: str, ctx: Context, cis, knobs, seed: int, objec
     return tuple(t.cpu().tolist() for t in rows)
 
 
-def _launch(algorithm: str, ctx, cis, knobs, seed, objective, spread):
+def batch_launch(algorithm: str, ctx, cis, knobs, seed, objective, spread):
     """batch_<algorithm>_launch as the module has it when called (a caller may
     have put its own there), with the arguments that one takes."""
     kind = HEURISTIC_KINDS[algorithm]
@@ -1319,7 +1330,7 @@ def _solve_single(algorithm: str, ci: CompactInstance, values, spread, seed, dev
     """One checked request on a one-request launch; no customer on the host."""
     if ci.n == 0:
         return _heuristic_result(ci, None, with_unvisited)
-    rows = _launch(algorithm, context(device), [ci], values, seed, objective, spread)
+    rows = batch_launch(algorithm, context(device), [ci], values, seed, objective, spread)
     return _heuristic_result(ci, [r[0] for r in rows], with_unvisited)
 
 
@@ -1370,8 +1381,9 @@ def _solve_heuristic_batch(algorithm: str, requests, knobs, seed, device, object
     if groups:
         ctx = context(device)
         for xs in groups.values():
-            rows = _launch(algorithm, ctx, [cis[x] for x in xs],
-                           knobs if launch_knobs is None else launch_knobs, seed, objective, spread)
+            rows = batch_launch(algorithm, ctx, [cis[x] for x in xs],
+                                knobs if launch_knobs is None else launch_knobs, seed, objective,
+                                spread)
             for x, *row in zip(xs, *rows):
                 out[x] = _heuristic_result(cis[x], row, with_unvisited)
     return out
@@ -1678,10 +1690,8 @@ def solve_vrp_ls_batch(requests, *, starts: int = 64, rounds: int = 1000, seed: 
     solve_vrp's trivial answer."""
     if objective not in ("sum", "max"):
         raise ValueError("objective must be 'sum' or 'max'")
-    if not 1 <= int(starts) <= BATCH_LS_MAX_STARTS:
-        raise ValueError(f"starts must be in 1..{BATCH_LS_MAX_STARTS} ({starts} given)")
-    if not 0 <= int(rounds) <= BATCH_LS_MAX_ROUNDS:
-        raise ValueError(f"rounds must be in 0..{BATCH_LS_MAX_ROUNDS} ({rounds} given)")
+    check_range("ls", "starts", starts)
+    check_range("ls", "rounds", rounds)
     return _solve_heuristic_batch("ls", requests, (starts, rounds), seed, device, objective,
                                   with_unvisited)
 
@@ -1776,12 +1786,9 @@ def solve_tsp_lso_batch(requests, *, starts: int = 64, rounds: int = 1000, moves
     the host.  `spread` is batch_lso_launch's, applied to every group's launch:
     it changes which kernels run, never a dict."""
     spread = check_lso_spread(spread)
-    if not 1 <= int(starts) <= BATCH_LSO_MAX_STARTS:
-        raise ValueError(f"starts must be in 1..{BATCH_LSO_MAX_STARTS} ({starts} given)")
-    if not 0 <= int(rounds) <= BATCH_LSO_MAX_ROUNDS:
-        raise ValueError(f"rounds must be in 0..{BATCH_LSO_MAX_ROUNDS} ({rounds} given)")
-    if not 1 <= int(moves) <= 31:
-        raise ValueError(f"moves must be in 1..31 ({moves} given)")
+    check_range("lso", "starts", starts)
+    check_range("lso", "rounds", rounds)
+    check_range("lso", "moves", moves)
     return _solve_heuristic_batch("lso", requests, (starts, rounds, moves), seed, device,
                                   spread=spread)
 
@@ -1882,10 +1889,8 @@ def solve_vrp_lsr_batch(requests, *, starts: int = 64, rounds: int = 1000, seed:
     if objective not in ("sum", "max"):
         raise ValueError("objective must be 'sum' or 'max'")
     spread = check_lsr_spread(spread)
-    if not 1 <= int(starts) <= BATCH_LSR_MAX_STARTS:
-        raise ValueError(f"starts must be in 1..{BATCH_LSR_MAX_STARTS} ({starts} given)")
-    if not 0 <= int(rounds) <= BATCH_LSR_MAX_ROUNDS:
-        raise ValueError(f"rounds must be in 0..{BATCH_LSR_MAX_ROUNDS} ({rounds} given)")
+    check_range("lsr", "starts", starts)
+    check_range("lsr", "rounds", rounds)
     return _solve_heuristic_batch("lsr", requests, (starts, rounds), seed, device, objective,
                                   with_unvisited, spread)
 
@@ -1948,10 +1953,8 @@ def solve_vrp_lsf_batch(requests, *, starts: int = 64, rounds: int = 1000, seed:
     group; no customer has solve_vrp's trivial answer."""
     if objective not in ("sum", "max"):
         raise ValueError("objective must be 'sum' or 'max'")
-    if not 1 <= int(starts) <= BATCH_LSF_MAX_STARTS:
-        raise ValueError(f"starts must be in 1..{BATCH_LSF_MAX_STARTS} ({starts} given)")
-    if not 0 <= int(rounds) <= BATCH_LSF_MAX_ROUNDS:
-        raise ValueError(f"rounds must be in 0..{BATCH_LSF_MAX_ROUNDS} ({rounds} given)")
+    check_range("lsf", "starts", starts)
+    check_range("lsf", "rounds", rounds)
     return _solve_heuristic_batch("lsf", requests, (starts, rounds), seed, device, objective,
                                   with_unvisited)
 
