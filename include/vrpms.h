@@ -834,6 +834,40 @@ int vrpms_vrp_batch_lsr_spread(vrpms_ctx* ctx, const int32_t* d_mats, const int3
                                uint64_t work_bytes, uint16_t* d_tours, uint64_t* d_keys,
                                int32_t* d_durs, int8_t* d_veh, int32_t* d_info, void* stream);
 
+/* vrpms_vrp_batch_lsf by vrpms_vrp_batch_lsr_spread's mapping (DESIGN.md
+ * §4.3x): the same requests, buffers and arguments as vrpms_vrp_batch_lsf, and
+ * per request the identical d_tours, d_keys, d_durs, d_veh and d_info rows,
+ * refusal rows included -- A28 fixes the starts, the rounds and the least
+ * (key, s), not which threads run them.  A request's S starts are spread over
+ * min(G, S) WORKGROUPS, workgroup g descending the starts g, g + G, ..., and a
+ * workgroup's 256 threads price one round of one plain tour together from the
+ * wavefronts' rows (thread t the move ids [t per, (t + 1) per), per =
+ * ceil(2 L (L - 1) / 256)), one workgroup barrier a round.  Each workgroup
+ * leaves its best (key, s, capped count, tour) in the workspace; a second
+ * launch on the same stream, one workgroup per request, takes the least
+ * (key, s), sums the capped counts and writes the outputs.
+ * vrpms_vrp_batch_lsf_spread_lds gives either launch's dynamic-LDS bytes for
+ * (N, K, wide) (host only, no context): never more than
+ * vrpms_vrp_batch_lsf_lds of the same shape, so A28's domain holds.
+ * vrpms_vrp_batch_lsf_spread_work gives the workspace bytes of R requests at G
+ * workgroups each, R * G * (16 + 2 * align8(N + K - 2)) (host only;
+ * VRPMS_EINVAL for R < 0, a shape outside vrpms_vrp_batch_lsf_lds's, G outside
+ * 1..65535 or R * G above 2^31 - 1).  d_work: work_bytes bytes of device
+ * memory, 8-byte aligned, at least vrpms_vrp_batch_lsf_spread_work(R, N, K,
+ * min(G, S)); its contents before and after the call mean nothing.
+ * Asynchronous on `stream`.  R = 0 launches nothing.  VRPMS_EINVAL, with
+ * nothing launched and nothing written, for everything vrpms_vrp_batch_lsf
+ * refuses, G outside 1..65535, a NULL, misaligned or too small workspace with
+ * R > 0, or R * min(G, S) above 2^31 - 1. */
+int vrpms_vrp_batch_lsf_spread_lds(int32_t N, int32_t K, int32_t wide, uint64_t* bytes);
+int vrpms_vrp_batch_lsf_spread_work(int32_t R, int32_t N, int32_t K, int32_t G, uint64_t* bytes);
+int vrpms_vrp_batch_lsf_spread(vrpms_ctx* ctx, const int32_t* d_mats, const int32_t* d_demand,
+                               const int32_t* d_cap, const int32_t* d_start, int32_t R, int32_t N,
+                               int32_t K, int32_t H, int32_t objective, int32_t wide, int32_t S,
+                               int32_t rounds, uint64_t seed, int32_t G, void* d_work,
+                               uint64_t work_bytes, uint16_t* d_tours, uint64_t* d_keys,
+                               int32_t* d_durs, int8_t* d_veh, int32_t* d_info, void* stream);
+
 /* Throughput mode of a multi-start local search for the TSP with Or-opt moves
  * and delta pricing: R independent TSP requests of
  * one node count N >= 2 (n = N - 1 customers, node 0 the start node), one hour

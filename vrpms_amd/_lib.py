@@ -139,6 +139,11 @@ SIGNATURES = {
     "vrpms_vrp_batch_lsr_spread": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32,
                                               _i32, _i32, _i32, _u64, _i32, _vp, _u64, _vp, _vp, _vp,
                                               _vp, _vp, _vp]),
+    "vrpms_vrp_batch_lsf_spread_lds": (_c.c_int, [_i32, _i32, _i32, _c.POINTER(_u64)]),
+    "vrpms_vrp_batch_lsf_spread_work": (_c.c_int, [_i32, _i32, _i32, _i32, _c.POINTER(_u64)]),
+    "vrpms_vrp_batch_lsf_spread": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32,
+                                              _i32, _i32, _i32, _u64, _i32, _vp, _u64, _vp, _vp, _vp,
+                                              _vp, _vp, _vp]),
     "vrpms_tsp_batch_lso_lds": (_c.c_int, [_i32, _i32, _i32, _c.POINTER(_u64)]),
     "vrpms_tsp_batch_lso": (_c.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _u64,
                                        _vp, _vp, _vp, _vp, _vp]),

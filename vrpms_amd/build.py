@@ -20,7 +20,7 @@ SOURCES = ["capi.hip", "eval.hip", "eval_staged.hip", "eval_words.hip", "search.
            "vrp_batch_sp.hip", "tsp_batch_tdp.hip", "vrp_batch_tdsp.hip",
            "vrp_batch_sa.hip", "vrp_batch_ga.hip", "vrp_batch_aco.hip",
            "vrp_batch_ls.hip", "vrp_batch_lsr.hip", "vrp_batch_lsr_spread.hip",
-           "vrp_batch_lsf.hip",
+           "vrp_batch_lsf.hip", "vrp_batch_lsf_spread.hip",
            "tsp_batch_lso.hip", "tsp_batch_lso_spread.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950",

@@ -168,6 +168,27 @@ def vrp_batch_lsr_spread_work(R: int, N: int, K: int, G: int) -> int:
     return _bytes("vrpms_vrp_batch_lsr_spread_work", R, N, K, G)
 
 
+def vrp_batch_lsf_spread_lds(N: int, K: int, H: int, wide) -> int:
+    """vrpms_vrp_batch_lsf_spread_lds: the dynamic-LDS bytes of either launch
+    of vrp_batch_lsf_spread for N nodes, K vehicles and a uint16 (`wide`
+    false) or int32 (`wide` true) static matrix; never more than
+    vrp_batch_lsf_lds of the same shape.  H is taken so that the call reads
+    like the other _lds functions and must be 1.  Host only: needs the
+    library, no GPU."""
+    if int(H) != 1:
+        raise ValueError(f"vrp_batch_lsf_spread_lds: H must be 1 ({H} given): an hour-indexed "
+                         "matrix keeps vrp_batch_lsr_spread")
+    return _bytes("vrpms_vrp_batch_lsf_spread_lds", N, K, wide)
+
+
+def vrp_batch_lsf_spread_work(R: int, N: int, K: int, G: int) -> int:
+    """vrpms_vrp_batch_lsf_spread_work: the workspace bytes of a
+    vrp_batch_lsf_spread launch of R requests at G workgroups each,
+    R * G * (16 + 2 * align8(N + K - 2)).  Host only: needs the library, no
+    GPU."""
+    return _bytes("vrpms_vrp_batch_lsf_spread_work", R, N, K, G)
+
+
 def tdp_words(start: int, horizon: int) -> int:
     """Hour words of one A16 row: the words from the start's hour to the one
     of start + horizon."""
@@ -1015,6 +1036,28 @@ class Context:
                                                 nstarts)
         out = self._batch_out(R, N - 1 + K - 1, K, info=True)
         check(self.lib.vrpms_vrp_batch_lsr_spread(
+            self._ctx, mats.data_ptr(), demand.data_ptr(), caps.data_ptr(), starts.data_ptr(), R, N,
+            K, H, int(objective), int(bool(wide)), int(nstarts), int(rounds), _u64(seed), G,
+            work.data_ptr(), work_bytes, *(t.data_ptr() for t in out), self.stream()))
+        return out
+
+    def vrp_batch_lsf_spread(self, mats, demand, caps, starts, objective: int, nstarts: int,
+                             rounds: int, seed: int, groups: int, wide=None):
+        """vrp_batch_lsf by vrp_batch_lsr_spread's mapping:
+        the same arguments (H = 1 only) and the identical five tensors, but a
+        request's `nstarts` starts are spread over min(`groups`, nstarts)
+        workgroups (`groups` in 1..65535) whose 256 threads each price one
+        round of one plain tour together, and a second launch selects the
+        least (key, start) per request.  For few requests that occupies
+        R * groups workgroups instead of R.  The workspace
+        (vrp_batch_lsf_spread_work) is allocated here, from torch's caching
+        allocator, which keeps it alive for the stream's queued work.
+        Asynchronous on the current stream."""
+        mats, R, H, N, K, wide = self._vrp_batch_args(mats, demand, caps, starts, wide)
+        G, work, work_bytes = self._spread_work(vrp_batch_lsf_spread_work, R, (N, K), groups,
+                                                nstarts)
+        out = self._batch_out(R, N - 1 + K - 1, K, info=True)
+        check(self.lib.vrpms_vrp_batch_lsf_spread(
             self._ctx, mats.data_ptr(), demand.data_ptr(), caps.data_ptr(), starts.data_ptr(), R, N,
             K, H, int(objective), int(bool(wide)), int(nstarts), int(rounds), _u64(seed), G,
             work.data_ptr(), work_bytes, *(t.data_ptr() for t in out), self.stream()))

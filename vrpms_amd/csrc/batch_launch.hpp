@@ -1,8 +1,8 @@
 // Host-side code the batched solvers share.  The exact ones (tsp_batch_dp,
 // vrp_batch_sp, tsp_batch_tdp, vrp_batch_tdsp): a team of T threads owns one
 // request and a 256-thread workgroup holds 256 / T requests.  The heuristic
-// ones (vrp_batch_sa, _ga, _aco, _ls, _lsr, _lsr_spread, _lsf, tsp_batch_lso,
-// _lso_spread): a workgroup owns a request whose instance lives in LDS
+// ones (vrp_batch_sa, _ga, _aco, _ls, _lsr, _lsr_spread, _lsf, _lsf_spread,
+// tsp_batch_lso, _lso_spread): a workgroup owns a request whose instance lives in LDS
 // (batch_stage.hpp has the layout); their argument checks, the LDS refusal,
 // the choice of the kernel's matrix type and the launch are below.
 #pragma once

@@ -1,6 +1,7 @@
 // What the one-workgroup-per-request VRP kernels share (vrp_batch_sa.hip, A22;
 // vrp_batch_ga.hip, A23; vrp_batch_aco.hip, A24; vrp_batch_ls.hip, A25;
-// vrp_batch_lsr.hip and vrp_batch_lsr_spread.hip, A26): the sizes of a request's
+// vrp_batch_lsr.hip and vrp_batch_lsr_spread.hip, A26; vrp_batch_lsf.hip and
+// vrp_batch_lsf_spread.hip, A28): the sizes of a request's
 // instance in LDS -- one description for the host, which sizes the launch, and
 // for a kernel that carves by it (vrp_batch_sa so far; DESIGN.md §4.3u has why
 // the others keep their own) -- staging it with the entry check on the way, the

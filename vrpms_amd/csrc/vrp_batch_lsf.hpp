@@ -1,4 +1,5 @@
-// What vrp_batch_lsf.hip (A28) adds to vrp_batch_lsr's descent
+// What vrp_batch_lsf.hip and vrp_batch_lsf_spread.hip (A28, DESIGN.md §4.3v,
+// §4.3x) add to vrp_batch_lsr's descent
 // (A26): the rows a wavefront keeps of its current PLAIN tour -- a tour of n
 // customers and K - 1 separators in which the customers between separator
 // g - 1 and separator g weigh at most cap[g], so that the separators alone
@@ -259,7 +260,96 @@ VRPMS_DEV uint64_t lsf_price(const Mat& D, const int32_t* cap, const LsfRows& r,
   return w.ok ? cvrp_key(0, (uint32_t)nsum, (uint32_t)w.mx, objective) : ~0ull;
 }
 
-// the shape checks of both entry points: vrp_batch_lsr's on a static matrix
+// The 256-thread forms: one descent per workgroup at a time (vrp_batch_lsf_spread.hip).
+//
+// A wavefront's own parts there, behind the instance: BatchLsfParts' less the
+// best end tour, which lives in the workspace.  The [2][4] round records
+// follow the four wavefronts' parts.
+template <typename I>
+struct BatchLsfSpreadParts {
+  I row_words, tab_words, ppad, spad, gpad;
+  __host__ __device__ BatchLsfSpreadParts(I L, I K) {
+    const BatchLsfParts<I> f(L, K);
+    row_words = f.row_words;
+    tab_words = f.tab_words;
+    ppad = f.ppad;
+    spad = f.spad;
+    gpad = f.gpad;
+  }
+  __host__ __device__ I words() const { return 3 * row_words + 5 * tab_words; }
+  __host__ __device__ I halves() const { return ppad + spad; }
+  __host__ __device__ I wave_bytes() const { return 4 * words() + 2 * halves() + gpad; }
+};
+
+inline size_t batch_lsf_spread_lds(int N, int K, int wide) {
+  return batch_inst_bytes(N, K, 1, wide) +
+         4 * BatchLsfSpreadParts<size_t>((size_t)(N - 1 + K - 1), (size_t)K).wave_bytes() +
+         2 * 4 * sizeof(BatchLsRec);
+}
+
+// One steepest descent of the whole workgroup (four wavefronts, `sh` from
+// batch_ls_share_wg) on one PLAIN tour of L >= 2 tokens with key ck, duration
+// sum `sum` and longest route `dmax`: vrp_batch_lsf_kernel's rounds, the thread
+// pricing its share with lsf_price.  As in batch_ls_descend_wg and
+// lso_descend_wg every wavefront holds its own copy of the padded tour and of
+// its rows -- equal on entry, and they stay equal, since each applies the same
+// move and rebuilds its rows from the same tour -- so a round has one barrier:
+// the wavefronts' records meet in rec[parity][wave] and each takes the least
+// (key, wave), which is the least (key, typ, i, j) because the id ranges ascend
+// with the thread.  A thread's running bound starts at ck and lsf_price may
+// answer a candidate whose key is not below it with the bound itself: such a
+// key is not below ck, or not below a key the same thread holds at a lower id,
+// so the thread would not have taken it and no winner is withheld.  A thread
+// without a candidate below ck sends ck; a round whose least key is ck ends
+// the descent.  `parity` alternates with every barrier of the kernel past
+// staging, over all its descents (batch_ls.hpp has the argument).  ck, `rounds`,
+// the records and so every branch here are the same in all four wavefronts --
+// the caller enters with a plainness all four agree on --; all of them reach
+// every barrier.  -> the end tour's key.
+template <typename Mat>
+VRPMS_DEV uint64_t lsf_descend_wg(const Mat& D, const int32_t* dem, const int32_t* cap, const LsfRows& rows,
+                                  int L, int K, uint64_t ck, int sum, int dmax, int objective, int rounds,
+                                  const BatchLsShare& sh, int wave, int lane, BatchLsRec* rec, int& parity,
+                                  int& capped) {
+  uint16_t* A = rows.P + 1;
+  for (int applied = 0;; ++applied) {
+    if (applied >= rounds) {   // stopped unproven
+      ++capped;
+      break;
+    }
+    Move m = sh.m0, lm = sh.m0;
+    uint64_t lk = ck;   // only a key below the tour's is of use
+    for (int c = 0; c < sh.cnt; ++c) {
+      const uint64_t k = lsf_price(D, cap, rows, L, sum, objective, m, lk);
+      if (k < lk) {
+        lk = k;
+        lm = m;
+      }
+      batch_ls_next(m, L);
+    }
+    int bl;
+    const uint64_t wk = wave_argmin_lane(lk, bl);
+    BatchLsRec* mine = rec + 4 * parity;
+    if (lane == bl) mine[wave] = BatchLsRec{wk, lm.typ, (uint16_t)lm.i, (uint16_t)lm.j};
+    __syncthreads();
+    int bw = 0;
+    for (int w = 1; w < 4; ++w)
+      if (mine[w].key < mine[bw].key) bw = w;   // the lowest wavefront among equal keys
+    const BatchLsRec best = mine[bw];
+    parity ^= 1;
+    if (!(readlane_u64(best.key, 0) < ck)) break;   // a local optimum
+    Move mb;
+    mb.typ = (uint32_t)__builtin_amdgcn_readfirstlane((int)best.typ);
+    mb.i = __builtin_amdgcn_readfirstlane((int)best.i);
+    mb.j = __builtin_amdgcn_readfirstlane((int)best.j);
+    batch_ls_apply(A, mb, lane);
+    sum = lsf_rows(D, dem, rows, L, K, lane, dmax);
+    ck = cvrp_key(0, (uint32_t)sum, (uint32_t)dmax, objective);
+  }
+  return ck;
+}
+
+// the shape checks of every lsf entry point: vrp_batch_lsr's on a static matrix
 inline int batch_lsf_check(const char* who, int32_t N, int32_t K, int32_t H, int32_t wide) {
   if (const int rc = batch_lsr_check(who, N, K, H, wide)) return rc;
   return batch_check_static(who, H, "vrpms_vrp_batch_lsr");

@@ -970,7 +970,9 @@ class App:
         solver.TDP_MAX_CUSTOMERS customers, hour-indexed matrices too; knob
         "upper_bound") or "lso" (multi-start local search with Or-opt, spec A27;
         knobs "starts", "rounds", "moves" and "spread": the workgroups the
-        starts are spread over, the same body sooner), or, for vrp only, "sp" (exact set partitioning, up to solver.SP_MAX_CUSTOMERS customers and 64 vehicles
+        starts are spread over, the same body sooner), or, for vrp only, "lsr"
+        and "lsf" (multi-start local searches over separator tours, spec A26 and
+        A28; knobs "starts", "rounds" and "spread", the latter as for "lso"), "sp" (exact set partitioning, up to solver.SP_MAX_CUSTOMERS customers and 64 vehicles
         on a static matrix) or "tdsp" (exact time-expanded partition DP, up
         to solver.TDSP_MAX_CUSTOMERS customers and 64 vehicles, hour-indexed
         matrices and per-vehicle start times; knob "upper_bound":

@@ -165,6 +165,9 @@ BATCH_LSR_MAX_SPREAD = 1024
 BATCH_LSF_MAX_STARTS = 1024
 BATCH_LSF_MAX_ROUNDS = 1000
 BATCH_LSF_LDS_BYTES = BATCH_SA_LDS_BYTES
+# A28 by the other mapping (vrp_batch_lsf_spread): the workgroups
+# a request's starts may be spread over; the answers do not depend on it
+BATCH_LSF_MAX_SPREAD = 1024
 # batched TSP multi-start local search with Or-opt and delta pricing (A27): next
 # to the matrix a wavefront keeps two tours and two int32 prefix rows (one on an
 # hour-indexed matrix); vrpms_tsp_batch_lso_lds gives the bytes for (N, H,
@@ -641,10 +644,12 @@ def solve_vrp(algorithm: str, durations, locations, capacities, start_times,
     over that many workgroups: the same answer, sooner for a lone request.
     "lsf" (spec A28: "lsr" restricted to the plain tours, whose separators
     alone decide the routes, priced without walking them; static matrices
-    only, the same knobs, limits BATCH_LSF_MAX_STARTS and BATCH_LSF_MAX_ROUNDS,
-    no `spread`) answers with a one-request vrp_batch_lsf launch:
-    solve_vrp_lsf_batch's answer for the request, its domain
-    batch_lsf_message's; an hour-indexed request keeps "lsr"."""
+    only, the same knobs, limits BATCH_LSF_MAX_STARTS and BATCH_LSF_MAX_ROUNDS)
+    answers with a one-request vrp_batch_lsf launch: solve_vrp_lsf_batch's
+    answer for the request, its domain batch_lsf_message's; an hour-indexed
+    request keeps "lsr".  Its knob `spread` (None, "auto" or
+    1..BATCH_LSF_MAX_SPREAD; batch_lsf_launch) is "lsr"'s: the same answer by
+    vrp_batch_lsf_spread, sooner for a lone request."""
     if algorithm == "dp":
         raise ValueError("dp solves the TSP only (the greedy split of a giant tour does not "
                          "decompose over subsets); use bf, sa, ga or aco for the VRP")
@@ -1135,6 +1140,10 @@ class HeuristicKind:
     separators: bool = False
     # "<kernel>_spread" takes up to that many workgroups per request; 0: no such form
     max_spread: int = 0
+    # batch_launch names `spread` to the algorithm's launch even when none was
+    # asked for; False: only when one was ("lsf", whose launch had no such
+    # keyword at first, and whose callers without one call it as they did)
+    spread_always: bool = True
     # static matrices only: the algorithm that takes the hour-indexed requests
     static_else: str = ""
     # _check_heuristic applies the int32 guard to a request of no customer
@@ -1178,7 +1187,8 @@ HEURISTIC_KINDS = {
                          separators=True, max_spread=BATCH_LSR_MAX_SPREAD),
     "lsf": HeuristicKind(CVRP, "vrp_batch_lsf", BATCH_LSF_LDS_BYTES,
                          _ls_knobs(BATCH_LSF_MAX_STARTS, BATCH_LSF_MAX_ROUNDS), strict=True,
-                         separators=True, static_else="lsr"),
+                         separators=True, max_spread=BATCH_LSF_MAX_SPREAD, spread_always=False,
+                         static_else="lsr"),
     "lso": HeuristicKind(TSP, "tsp_batch_lso", BATCH_LSO_LDS_BYTES,
                          _ls_knobs(BATCH_LSO_MAX_STARTS, BATCH_LSO_MAX_ROUNDS,
                                    Knob("moves", 1, 31, 31, "a move mask of {}..{}")), strict=True,
@@ -1294,7 +1304,8 @@ def batch_launch(algorithm: str, ctx, cis, knobs, seed, objective, spread):
     have put its own there), with the arguments that one takes."""
     kind = HEURISTIC_KINDS[algorithm]
     args = tuple(knobs) + (seed,) + ((objective,) if kind.problem == CVRP else ())
-    more = dict(spread=spread) if kind.max_spread else {}
+    more = dict(spread=spread) if kind.max_spread and (kind.spread_always or spread is not None) \
+        else {}
     return globals()[f"batch_{algorithm}_launch"](ctx, cis, *args, **more)
 
 
@@ -1923,17 +1934,37 @@ def batch_lsf_fits(ci: CompactInstance, starts: int, rounds: int) -> bool:
     return batch_lsf_message(ci, starts, rounds) is None
 
 
+def check_lsf_spread(spread):
+    """`spread` as batch_lsf_launch takes it -> None, "auto" or an int in
+    1..BATCH_LSF_MAX_SPREAD; anything else is a ValueError."""
+    return _check_spread(spread, BATCH_LSF_MAX_SPREAD)
+
+
+def batch_lsf_spread(R: int, S: int, cus: int) -> int:
+    """The "auto" policy: the workgroups per request that vrp_batch_lsf_spread
+    gives a launch of R requests of S starts on a device of `cus` compute
+    units, min(S, max(1, 16 cus // R)), batch_lsr_spread's.  1 means
+    vrp_batch_lsf itself, one workgroup per request.  DESIGN §4.3x has what
+    was measured of the factor for this kernel."""
+    return _auto_spread(R, S, cus)
+
+
 def batch_lsf_launch(ctx: Context, cis, starts: int, rounds: int, seed: int,
-                     objective: str = "sum"):
+                     objective: str = "sum", spread=None):
     """One upload and one vrp_batch_lsf launch for compact instances of one
     batch_lsf_key (each passed batch_guard_message and batch_lsf_fits) ->
-    (tours, veh, durs), as batch_lsr_launch gives them."""
-    return _heuristic_launch("lsf", ctx, cis, (starts, rounds), seed, objective)
+    (tours, veh, durs), as batch_lsr_launch gives them.  `spread`: None -- the
+    default -- is that launch; an int in 1..BATCH_LSF_MAX_SPREAD takes
+    vrp_batch_lsf_spread at that many workgroups per request (1: one workgroup
+    per request, its 256 threads on one descent at a time); "auto" takes
+    batch_lsf_spread's for the launch's size and the device, and vrp_batch_lsf
+    when that is 1.  The rows are the same whichever it is."""
+    return _heuristic_launch("lsf", ctx, cis, (starts, rounds), seed, objective, spread)
 
 
 def solve_vrp_lsf_batch(requests, *, starts: int = 64, rounds: int = 1000, seed: int = 0,
                         objective: str = "sum", with_unvisited: bool = False,
-                        device: int = 0) -> list:
+                        device: int = 0, spread=None) -> list:
     """A multi-start local search over plain separator tours for many static
     small-fleet VRP requests, the requests sharing launches (spec A28):
     solve_vrp_lsr_batch's mapping, starts, moves and answer, but a move onto a
@@ -1950,13 +1981,16 @@ def solve_vrp_lsf_batch(requests, *, starts: int = 64, rounds: int = 1000, seed:
     failed -- for an hour-indexed matrix, that "lsr" takes it.  With no local
     GPU each request goes to solve_vrp("lsf") on the GPU box.  The requests
     are grouped by (N, K, wide), one upload and one vrp_batch_lsf launch per
-    group; no customer has solve_vrp's trivial answer."""
+    group; no customer has solve_vrp's trivial answer.  `spread` is
+    batch_lsf_launch's, applied to every group's launch: it changes which
+    kernels run, never a dict."""
     if objective not in ("sum", "max"):
         raise ValueError("objective must be 'sum' or 'max'")
+    spread = check_lsf_spread(spread)
     check_range("lsf", "starts", starts)
     check_range("lsf", "rounds", rounds)
     return _solve_heuristic_batch("lsf", requests, (starts, rounds), seed, device, objective,
-                                  with_unvisited)
+                                  with_unvisited, spread)
 
 
 # ---------------------------------------------------------------------------
